@@ -20,6 +20,8 @@ per step.  `python bench.py --gpus N` with N > 1 and no RANK in the environment 
 script is a rank.  Default at N > 1 = BASELINE configs[3]: global batch 1024 split over the ranks (strong scaling,
 north_star's ">= 6x at 8 GPUs"); `--batch B` with N > 1 = B utterances per GPU (weak scaling); `--global-batch G`
 any other total.  `--dry-run` runs the launcher, the sharding and the collectives on CPU (gloo) without kernels.
+`--dump-outputs DIR` (e.g. bench_outputs/) writes what the last timed step computed as DIR/<name>.npy (dump_outputs); the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -490,6 +492,33 @@ def inference_from_files(tr, n_utt=4096, batch=128):
         torch.cuda.empty_cache()
 
 
+DUMP_ENH_ROWS = 32                # enhanced signals written by --dump-outputs: a fixed, seeded sample of the batch's rows (B = 256: 8 MB)
+
+
+def dump_outputs(d, last, tr):
+    """--dump-outputs DIR: what the last timed step computed, copied off the device after the timed region - the step's return values
+    (G loss, D loss, [B, n_metrics] targets), the enhanced signals of a fixed, seeded sample of rows and the G / D weights the step's
+    optimiser updates left.  Float32 throughout (float64 stays float64); about 18 MB at the default workload."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    lg, ld, tgt = last
+    enh = tr._last_enh
+    rows = np.sort(np.random.default_rng(0).choice(enh.shape[0], min(DUMP_ENH_ROWS, enh.shape[0]), replace=False))
+    arrays = {'g_loss': lg, 'd_loss': ld, 'targets': tgt, 'enhanced_sample': enh[torch.from_numpy(rows).to(enh.device)],
+              'g_weights': tr.G.flat_parameters().flat, 'd_weights': tr.D.flat_parameters().flat}
+    os.makedirs(d, exist_ok=True)
+    files, total = {}, 0
+    for name, t in arrays.items():
+        x = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        x = x.astype(np.float64 if x.dtype == np.float64 else np.float32)
+        np.save(os.path.join(d, name + '.npy'), x)
+        files[name] = list(x.shape)
+        total += x.nbytes
+    assert total <= 64 << 20, "--dump-outputs: %d bytes" % total
+    return {'dir': d, 'arrays': files, 'bytes': total, 'enhanced_rows': rows.tolist()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -513,7 +542,12 @@ def main():
                          'pre-enhanced (DRC) example, 6 D-steps (2 examples x 3 passes, train_nele.py:342-426); reported as "epoch_equivalent"')
     ap.add_argument('--precision', default='bf16', choices=['f32', 'bf16'],
                     help='MFMA operand type of the discriminator conv forward / data-gradient passes (f32 accumulate; BASELINE configs[1] names bf16)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last timed step returned (G loss, D loss, targets), a seeded sample of its '
+                         'enhanced signals and the updated G / D weights as DIR/<name>.npy (float32; rank 0 only)')
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
     if a.gpus > 1 and 'RANK' not in os.environ:
         sys.exit(launch_ranks(a.gpus, sys.argv[1:]))              # before torch is imported: this process never touches a GPU
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -624,11 +658,12 @@ def main():
         if a.breakdown:
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
             ev[0].record(); f = tr.features(cw, nw)
-            ev[1].record(); tr.g_step(f['clean_band'], f['noise_band'])
+            ev[1].record(); lg = tr.g_step(f['clean_band'], f['noise_band'])
             ev[2].record(); enh = tr.generate(f['clean_band'], f['noise_band'], f['clean_spec'])
             ev[3].record(); tgt = tr.true_metrics(cw, enh, nw)
-            ev[4].record(); tr.d_step(tr.d_inputs(enh, f['noise_band'], f['clean_band']), tgt)
+            ev[4].record(); ld = tr.d_step(tr.d_inputs(enh, f['noise_band'], f['clean_band']), tgt)
             ev[5].record(); stage_ev.append(ev)
+            tr._last_enh, last = enh, (lg, ld, tgt)
         else:
             last = one_step()
     tr._flush_d()                       # (several ranks: the last step's D update is deferred under the NEXT step's features; there is none)
@@ -640,6 +675,7 @@ def main():
         assert bool(torch.isfinite(lg_)) and bool(torch.isfinite(ld_)) and bool(torch.isfinite(tgt_).all()), "non-finite loss / targets in the timed region"
         assert bool(torch.isfinite(tr.G.flat_parameters().flat).all()) and bool(torch.isfinite(tr.D.flat_parameters().flat).all()), "non-finite weights"
         status = tr.check_status(raise_on_error=True)
+    dumped = dump_outputs(a.dump_outputs, last, tr) if (a.dump_outputs and rank == 0) else None
     rank_ms = None
     if world > 1:
         # per-rank clocks of the same timed region (the line's ms_per_step is their maximum): a slow rank, a rank that waited in the
@@ -763,6 +799,8 @@ def main():
         }
         if allreduce_ms is not None:
             out['allreduce_ms_per_step'] = allreduce_ms
+        if dumped is not None:
+            out['dumped_outputs'] = dumped
         if prof_w:
             # D.conv5 weight gradient: dW[64][3888] = dY^T im2col(X), an MFMA-bound GEMM (arithmetic intensity ~1000 FLOP/B)
             w_ms = sum(e0.elapsed_time(e1) for e0, e1, _ in prof_w) / len(prof_w)
