@@ -39,7 +39,8 @@ int nele_stream_occupy(int workgroups, int lds_bytes, double microseconds, void*
 
 /* Measurement hook (no reference counterpart): HIP-event timing of single kernels that are launched from inside multi-kernel entry
  * points, on the stream they run on.  nele_profile_begin(tags) arms it for the launch sites whose tag is in the comma-separated list
- * (e.g. "eigh_tridiag_cluster,haspi_bank_gain_kernel"; NULL disarms); nele_profile_collect_tag waits for the recorded launches of one
+ * (e.g. "eigh_tridiag_cluster,haspi_bank_gain_kernel"; NULL disarms; a leading "+" arms the listed tags beside the armed ones, each
+ * with an empty list again); nele_profile_collect_tag waits for the recorded launches of one
  * tag and writes their durations in milliseconds (returns how many; stays armed); nele_profile_collect = the first tag, then disarm. */
 int nele_profile_begin(const char* tags);
 int nele_profile_collect_tag(const char* tag, float* ms_out, int max_n);
@@ -71,7 +72,8 @@ int nele_plan_run(void* plan, void* const* streams_host, int nstreams, const lon
 /* Slot declarations: what a call must provide behind slot k (bytes of device memory; 0 = a scalar slot; nullable != 0: the pointer may be
  * NULL).  nele_plan_run refuses a NULL in a declared non-optional slot; nele_plan_run_sized also takes the sizes of the caller's buffers
  * (sizes_host[k] bytes behind slots_host[k]) and refuses one that is shorter than what the plan touches.  Plans built by
- * nele_gen_plan_build / nele_disc_plan_build come fully declared; a recorded plan is declared by its recorder. */
+ * nele_gen_plan_build / nele_disc_plan_build (and the _plans_ forms) come fully declared; a plan made with nele_plan_create is declared by
+ * its maker. */
 int nele_plan_declare_slot(void* plan, int slot, long long bytes, int nullable);
 long long nele_plan_slot_bytes(void* plan, int slot);
 int nele_plan_run_sized(void* plan, void* const* streams_host, int nstreams, const long long* slots_host, const long long* sizes_host, int nslots);
@@ -116,6 +118,18 @@ float* nele_disc_workspace_ddin(void* workspace, int B, int T, int cin, int bf16
 int nele_disc_plan_build(int B, int T, int cin, int nout, int bf16, int train, int need_din, int weight_grads, int overlap_wgrad,
                          const float* params_flat, float* grads_flat, const void* const* sn_uv_host, void* workspace, long long workspace_bytes,
                          void* stream, void** fwd_out, void** bwd_out);
+/* The same job tables in the form model.py runs them, each one optional (NULL: not built).  prep_out: the weight preparation as a plan of
+ * its own - G: the layouts, no slots; D: spectral norm + sigma + layouts, slot 0 = the number of power iterations (0 or 1) - and the
+ * forward plan starts at the first layer.  zero_fill != 0 zeroes the workspace first (on `stream`); 0 adds tables over a workspace that
+ * is already in use (another backward form of D, a G backward plan with the weight gradients on the other stream layout). */
+int nele_gen_plans_build(int B, int T, int bf16, int need_bwd, int overlap_wgrad, const float* params_flat, float* grads_flat, void* workspace,
+                         long long workspace_bytes, int zero_fill, void* stream, void** prep_out, void** fwd_out, void** bwd_out);
+int nele_disc_plans_build(int B, int T, int cin, int nout, int bf16, int need_din, int weight_grads, int overlap_wgrad, const float* params_flat,
+                          float* grads_flat, const void* const* sn_uv_host, void* workspace, long long workspace_bytes, int zero_fill, void* stream,
+                          void** prep_out, void** fwd_out, void** bwd_out);
+/* One buffer of a discriminator workspace (tests): "act0".."act4", "gbuf0".."gbuf4", "pooled", "gbuf16", "ddin" -> device pointer and *elsize (2: bfloat16,
+ * 4: float32), or NULL where the layout of this shape / precision has no such buffer. */
+void* nele_disc_workspace_buffer(void* workspace, int B, int T, int cin, int bf16, const char* name, int* elsize);
 /* Hand-over events between the streams of a pass (hipEvent, timing disabled), recordable as plan operations */
 int nele_event_create(void** event_out);
 int nele_event_destroy(void* event);

@@ -188,19 +188,29 @@ void nele_prof_mark(hipStream_t s) {
     g_prof_ev[g_prof_cur].push_back(e);
 }
 
+// "+a,b": arm a and b beside the tags already armed (each of them starts an empty list again); without the "+" the new list replaces
+// the armed one
 extern "C" int nele_profile_begin(const char* tags) {
-    for (auto& v : g_prof_ev)
-        for (hipEvent_t e : v) (void)hipEventDestroy(e);
-    g_prof_ev.clear();
-    g_prof_tags.clear();
+    const bool add = tags && tags[0] == '+';
+    if (!add) {
+        for (auto& v : g_prof_ev)
+            for (hipEvent_t e : v) (void)hipEventDestroy(e);
+        g_prof_ev.clear();
+        g_prof_tags.clear();
+    }
     g_prof_cur = -1;
     if (tags) {
-        std::string all(tags), cur;
+        std::string all(tags + (add ? 1 : 0)), cur;
         for (size_t k = 0; k <= all.size(); ++k) {
-            if (k == all.size() || all[k] == ',') { if (!cur.empty()) g_prof_tags.push_back(cur); cur.clear(); }
-            else cur.push_back(all[k]);
+            if (k == all.size() || all[k] == ',') {
+                if (!cur.empty()) {
+                    const int i = prof_index(cur.c_str());
+                    if (i < 0) { g_prof_tags.push_back(cur); g_prof_ev.emplace_back(); }
+                    else { for (hipEvent_t e : g_prof_ev[i]) (void)hipEventDestroy(e); g_prof_ev[i].clear(); }
+                }
+                cur.clear();
+            } else cur.push_back(all[k]);
         }
-        g_prof_ev.resize(g_prof_tags.size());
     }
     return NELE_OK;
 }

@@ -2144,12 +2144,15 @@ extern "C" int nele_conv_span(const float* A, const float* Wfrag, const float* b
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_span_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_span_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
     }
-    switch (p.NT) {
+    // measurement hook: "span_N<N>_K<Ktot>" times one layer's launch (D.conv5 forward in float32 mode: span_N64_K3888)
+    char ptag[48] = "";
+    if (nele_prof_armed()) snprintf(ptag, sizeof(ptag), "span_N%d_K%d", N, p.g.Ktot);
+    NELE_PROF(ptag, s, switch (p.NT) {
         case 1: hipLaunchKernelGGL(conv_span_kernel<1>, dim3(gx), dim3(256), lds, s, p); break;
         case 2: hipLaunchKernelGGL(conv_span_kernel<2>, dim3(gx), dim3(256), lds, s, p); break;
         case 3: hipLaunchKernelGGL(conv_span_kernel<3>, dim3(gx), dim3(256), lds, s, p); break;
         default: hipLaunchKernelGGL(conv_span_kernel<4>, dim3(gx), dim3(256), lds, s, p); break;
-    }
+    });
     NELE_CHECK_LAUNCH("nele_conv_span");
     return NELE_OK;
 }

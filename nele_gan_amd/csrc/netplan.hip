@@ -1,12 +1,12 @@
 // Plan builders: the generator's and the discriminators' forward / backward passes as job tables made INSIDE the library
 // (nele_gen_fwd / nele_gen_bwd / nele_disc_fwd / nele_disc_bwd are callable from any host language).
 //
-// Until round 5 a plan could only be produced by the Python mirror's recorder hooking its own per-layer loop (nele_gan_amd/model.py):
-// which kernels, layouts, workspaces and stream hand-overs make up a pass of model.py:83-98 / 118-132 and their autograd was host-language
-// knowledge.  nele_gen_plan_build / nele_disc_plan_build state it here: given the batch shape, the operand precision and the model's flat
-// parameter / gradient buffers they lay every activation, weight layout and temporary out in ONE caller-provided workspace and return the
-// forward and backward job tables over this library's own per-layer entry points - the same kernels in the same order on the same
-// streams as the mirror's loop (tests/test_netplan_gpu.py: bit-identical to the module path in both precisions).
+// Given the batch shape, the operand precision and the model's flat parameter / gradient buffers, the builders lay every activation, weight
+// layout and temporary out in ONE caller-provided workspace and return the job tables over this library's own per-layer entry points:
+// which kernels, layouts and stream hand-overs make up a pass of model.py:83-98 / 118-132 and their autograd is stated here only.
+// nele_gen_plan_build / nele_disc_plan_build return a forward plan that starts with the weight preparation; nele_gen_plans_build /
+// nele_disc_plans_build (what nele_gan_amd/model.py runs) return that preparation as a plan of its own and build further backward forms
+// over a workspace that is already in use (zero_fill = 0).
 //
 // Parameter order of the flat buffers = torch's nn.Module.parameters() order of the reference modules (model.py:43-82, 101-116):
 //   G: for each of the 6 Conv1d blocks {conv.weight [Cout][Cin][K], conv.bias [Cout], cLN.gain0 [Cout], cLN.bias0 [Cout]}, fc1.weight, fc1.bias, fc2.weight, fc2.bias
@@ -155,7 +155,7 @@ void g_layout(int B, int T, bool bf16, bool need_bwd, void* base, GWs& w) {
     const int dims[8][4] = {{256, 5 * 128, 128, 5 * 256}, {256, 7 * 256, 256, 7 * 256}, {256, 7 * 256, 256, 7 * 256}, {256, 7 * 256, 256, 7 * 256},
                             {256, 7 * 256, 256, 7 * 256}, {64, 5 * 256, 256, 5 * 64}, {64, 64, 64, 64}, {64, 64, 64, 64}};
     for (int q = 0; q < 8; ++q) { w.wf[q] = a.f32((long long)dims[q][0] * dims[q][1]); w.wb[q] = a.f32((long long)dims[q][2] * dims[q][3]); }
-    w.fused_ok = true;
+    w.fused_ok = NELE_SWITCH_INT("NELE_G_FUSED", 1) != 0;           // =0: the per-layer kernels in bf16 mode too (A/B)
     for (int l = 0; l < 6; ++l) w.fused_ok = w.fused_ok && nele_glayer16_supported(G_LAYERS[l].cin, G_LAYERS[l].cout, G_LAYERS[l].k);
     w.fused = bf16 && w.fused_ok && (!need_bwd || T >= 32);
     if (bf16) {
@@ -389,7 +389,7 @@ int d_layout(int B, int T, int cin0, bool bf16, void* base, DWs& w) {
         w.cins[l] = l == 0 ? 4 : D_CONVS[l - 1][0];
     }
     (void)cin0;
-    w.c16 = bf16;
+    w.c16 = bf16 && NELE_SWITCH_INT("NELE_D_CONV16", 1);             // =0: float32 activations in memory, the round-2 kernels (A/B)
     for (int l = 1; l < 5 && w.c16; ++l)
         w.c16 = nele_conv16_supported((int)M_of(B, w.gf[l]), D_CONVS[l][0], w.gf[l].a, w.gf[l].KH, w.gf[l].KW) &&
                 nele_conv16_supported((int)M_of(B, w.gb[l]), w.cins[l], w.gb[l].a, w.gb[l].KH, w.gb[l].KW) &&
@@ -405,7 +405,7 @@ int d_layout(int B, int T, int cin0, bool bf16, void* base, DWs& w) {
         w.span16_f[l] = nele_conv_span_bf16_supported((int)M_of(B, w.gf[l]), co, w.gf[l].a, w.gf[l].KH, w.gf[l].KW) != 0;
         w.span16_b[l] = nele_conv_span_bf16_supported((int)M_of(B, w.gb[l]), w.cins[l], w.gb[l].a, w.gb[l].KH, w.gb[l].KW) != 0;
     }
-    w.grad16_ok = !w.c16 && nele_conv_span_bf16_a16_supported((int)M_of(B, w.gb[4]), w.cins[4], w.gb[4].a, w.gb[4].KH, w.gb[4].KW) &&
+    w.grad16_ok = NELE_SWITCH_INT("NELE_D_GRAD16", 1) && !w.c16 && nele_conv_span_bf16_a16_supported((int)M_of(B, w.gb[4]), w.cins[4], w.gb[4].a, w.gb[4].KH, w.gb[4].KW) &&
                   nele_conv_wgrad_bf16_d16_supported((int)M_of(B, w.gw[4]), D_CONVS[4][0], w.gw[4].a, w.gw[4].KH, w.gw[4].KW);
     if (bf16 && w.grad16_ok) w.gbuf16 = a.bf16(w.gbuf[4].elems);
     w.P = w.dims[5][0] * w.dims[5][1];
@@ -435,11 +435,11 @@ const void* const* d_mlp_ptrs(Builder& b, const DWs& w, const float* par, const 
     return b.host(arr, 9);
 }
 
-// _DiscriminatorBase._prepare_inline: spectral norm (power iteration in training mode) + sigma + every weight layout of this shape / mode
-void d_prepare(Builder& b, const DWs& w, const float* par, const DParams& pp, const void* const* uv, int cin, bool bf16, bool train) {
+// spectral norm (n_iter power iterations: 1 in training mode) + sigma + every weight layout of this shape / mode
+void d_prepare(Builder& b, const DWs& w, const float* par, const DParams& pp, const void* const* uv, int cin, bool bf16, Arg n_iter) {
     const void* sp[24]; int sd[16];
     for (int l = 0; l < 8; ++l) { sp[3 * l] = par + pp.w[l]; sp[3 * l + 1] = uv[2 * l]; sp[3 * l + 2] = uv[2 * l + 1]; sd[2 * l] = pp.N[l]; sd[2 * l + 1] = pp.K[l]; }
-    b.add("nele_spectral_norm", 0, {P(b.host(sp, 24)), P(b.host(sd, 16)), I(8), P(w.sigma), I(train ? 1 : 0)});
+    b.add("nele_spectral_norm", 0, {P(b.host(sp, 24)), P(b.host(sd, 16)), I(8), P(w.sigma), n_iter});
     const float* sig = reinterpret_cast<const float*>(w.sigma.p);
     if (bf16) {
         const void* pj[20]; int dj[25]; const void* fj[20]; int ej[40]; const void* cj[16]; int gj[32];
@@ -620,35 +620,114 @@ extern "C" long long nele_gen_workspace_bytes(int B, int T, int bf16, int need_b
     return (long long)w.bytes;
 }
 
+namespace {
+
+// one job table; on failure every table made before it by the same build call is released
+int finish_plan(Builder& b, int nslots, std::initializer_list<long long> slot_bytes, std::initializer_list<int> nullable, void** out) {
+    void* h = nullptr;
+    const int st = b.finish(nslots, &h);
+    if (st) return st;
+    int k = 0;
+    auto nl = nullable.begin();
+    for (long long v : slot_bytes) { nele_plan_declare_slot(h, k++, v, *nl); ++nl; }
+    *out = h;
+    return NELE_OK;
+}
+
+struct Built {                                       // the tables of one build call: released unless the call succeeds
+    void** outs[3] = {nullptr, nullptr, nullptr};
+    bool ok = false;
+    ~Built() {
+        if (ok) return;
+        for (void** o : outs)
+            if (o && *o) { (void)nele_plan_destroy(*o); *o = nullptr; }
+    }
+};
+
+// The generator's tables over one workspace, each optional: prep_out = the weight layouts (no slots); fold_prep: the forward plan starts
+// with them, otherwise at the first layer.
+int gen_build(const char* fn, int B, int T, int bf16, int need_bwd, int overlap_wgrad, const float* params_flat, float* grads_flat, void* workspace,
+              long long workspace_bytes, int zero_fill, void* stream, bool fold_prep, void** prep_out, void** fwd_out, void** bwd_out) {
+    GWs w;
+    g_layout(B, T, bf16 != 0, need_bwd != 0, workspace, w);
+    if (workspace_bytes < (long long)w.bytes) return nele_set_error(NELE_ERR_WORKSPACE, "%s: workspace too small (%lld < %lld)", fn, workspace_bytes, (long long)w.bytes);
+    // zero rows in front of / behind the time axis, zero carry slots: written once, kept by the kernels
+    if (zero_fill && hipMemsetAsync(workspace, 0, w.bytes, as_stream(stream)) != hipSuccess) return nele_set_error(NELE_ERR_HIP, "%s: hipMemsetAsync failed", fn);
+    const GParams pp = g_params();
+    const long long io = (long long)B * T * 64 * 4;
+    Built out;
+    if (prep_out) {
+        out.outs[0] = prep_out;
+        Builder b;
+        g_prep_weights(b, w, params_flat, pp, bf16 != 0);
+        if (const int st = finish_plan(b, 0, {}, {}, prep_out)) return st;
+    }
+    if (fwd_out) {
+        out.outs[1] = fwd_out;
+        Builder b;
+        g_forward(b, w, params_flat, pp, B, T, bf16 != 0, need_bwd != 0, fold_prep);
+        if (const int st = finish_plan(b, 4, {io, io, io}, {0, 0, 0}, fwd_out)) return st;
+    }
+    if (bwd_out) {
+        out.outs[2] = bwd_out;
+        Builder b;
+        g_backward(b, w, params_flat, grads_flat, pp, B, T, bf16 != 0, overlap_wgrad != 0);
+        if (const int st = finish_plan(b, 2, {io, io}, {0, 0}, bwd_out)) return st;
+    }
+    out.ok = true;
+    return NELE_OK;
+}
+
+// The discriminator's tables over one workspace, each optional: prep_out = spectral norm + weight layouts, slot 0 = the number of power
+// iterations (0 or 1); fold_prep: the forward plan starts with them (`train` power iterations), otherwise at the first layer.
+int disc_build(const char* fn, int B, int T, int cin, int nout, int bf16, int train, int need_din, int weight_grads, int overlap_wgrad, const float* params_flat,
+               float* grads_flat, const void* const* sn_uv_host, void* workspace, long long workspace_bytes, int zero_fill, void* stream, bool fold_prep,
+               void** prep_out, void** fwd_out, void** bwd_out) {
+    DWs w;
+    if (const int st = d_layout(B, T, cin, bf16 != 0, workspace, w)) return st;
+    if (workspace_bytes < (long long)w.bytes) return nele_set_error(NELE_ERR_WORKSPACE, "%s: workspace too small (%lld < %lld)", fn, workspace_bytes, (long long)w.bytes);
+    if (zero_fill && hipMemsetAsync(workspace, 0, w.bytes, as_stream(stream)) != hipSuccess) return nele_set_error(NELE_ERR_HIP, "%s: hipMemsetAsync failed", fn);
+    const DParams pp = d_params(cin, nout);
+    const long long din_bytes = (long long)B * 64 * T * 4 * 4, sc_bytes = (long long)B * nout * 4;
+    Built out;
+    if (prep_out) {
+        out.outs[0] = prep_out;
+        Builder b;
+        d_prepare(b, w, params_flat, pp, sn_uv_host, cin, bf16 != 0, S(0));
+        if (const int st = finish_plan(b, 1, {0}, {0}, prep_out)) return st;
+    }
+    if (fwd_out) {
+        out.outs[1] = fwd_out;
+        Builder b;
+        if (fold_prep) d_prepare(b, w, params_flat, pp, sn_uv_host, cin, bf16 != 0, I(train ? 1 : 0));
+        d_forward(b, w, params_flat, pp, B, T, nout, bf16 != 0);
+        if (const int st = finish_plan(b, 3, {din_bytes, (long long)B * 4, sc_bytes}, {0, 1, 0}, fwd_out)) return st;
+    }
+    if (bwd_out) {
+        out.outs[2] = bwd_out;
+        Builder b;
+        d_backward(b, w, params_flat, grads_flat, pp, sn_uv_host, B, T, cin, nout, bf16 != 0, need_din != 0, weight_grads != 0, overlap_wgrad != 0);
+        if (const int st = finish_plan(b, 4, {sc_bytes, sc_bytes, (long long)B * 4, din_bytes}, {0, 0, 1, 0}, bwd_out)) return st;
+    }
+    out.ok = true;
+    return NELE_OK;
+}
+
+}  // namespace
+
 extern "C" int nele_gen_plan_build(int B, int T, int bf16, int need_bwd, int overlap_wgrad, const float* params_flat, float* grads_flat, void* workspace,
                                    long long workspace_bytes, void* stream, void** fwd_out, void** bwd_out) {
     NELE_CHECK_ARG(B > 0 && T > 0 && params_flat && workspace && fwd_out && (!need_bwd || (grads_flat && bwd_out)), "nele_gen_plan_build: bad arguments");
-    GWs w;
-    g_layout(B, T, bf16 != 0, need_bwd != 0, workspace, w);
-    if (workspace_bytes < (long long)w.bytes) return nele_set_error(NELE_ERR_WORKSPACE, "nele_gen_plan_build: workspace too small (%lld < %lld)", workspace_bytes, (long long)w.bytes);
-    // zero rows in front of / behind the time axis, zero carry slots: written once, kept by the kernels
-    if (hipMemsetAsync(workspace, 0, w.bytes, as_stream(stream)) != hipSuccess) return nele_set_error(NELE_ERR_HIP, "nele_gen_plan_build: hipMemsetAsync failed");
-    const GParams pp = g_params();
-    const long long io = (long long)B * T * 64 * 4;
-    {
-        Builder b;
-        g_forward(b, w, params_flat, pp, B, T, bf16 != 0, need_bwd != 0, true);
-        void* h = nullptr;
-        const int st = b.finish(4, &h);
-        if (st) return st;
-        nele_plan_declare_slot(h, 0, io, 0); nele_plan_declare_slot(h, 1, io, 0); nele_plan_declare_slot(h, 2, io, 0);
-        *fwd_out = h;
-    }
-    if (need_bwd) {
-        Builder b;
-        g_backward(b, w, params_flat, grads_flat, pp, B, T, bf16 != 0, overlap_wgrad != 0);
-        void* h = nullptr;
-        const int st = b.finish(2, &h);
-        if (st) { (void)nele_plan_destroy(*fwd_out); *fwd_out = nullptr; return st; }
-        nele_plan_declare_slot(h, 0, io, 0); nele_plan_declare_slot(h, 1, io, 0);
-        *bwd_out = h;
-    } else if (bwd_out) *bwd_out = nullptr;
-    return NELE_OK;
+    if (!need_bwd && bwd_out) *bwd_out = nullptr;
+    return gen_build("nele_gen_plan_build", B, T, bf16, need_bwd, overlap_wgrad, params_flat, grads_flat, workspace, workspace_bytes, 1, stream, true, nullptr,
+                     fwd_out, need_bwd ? bwd_out : nullptr);
+}
+
+extern "C" int nele_gen_plans_build(int B, int T, int bf16, int need_bwd, int overlap_wgrad, const float* params_flat, float* grads_flat, void* workspace,
+                                    long long workspace_bytes, int zero_fill, void* stream, void** prep_out, void** fwd_out, void** bwd_out) {
+    NELE_CHECK_ARG(B > 0 && T > 0 && params_flat && workspace && (!bwd_out || (need_bwd && grads_flat)), "nele_gen_plans_build: bad arguments");
+    return gen_build("nele_gen_plans_build", B, T, bf16, need_bwd, overlap_wgrad, params_flat, grads_flat, workspace, workspace_bytes, zero_fill, stream, false,
+                     prep_out, fwd_out, bwd_out);
 }
 
 extern "C" long long nele_disc_workspace_bytes(int B, int T, int cin, int bf16) {
@@ -665,36 +744,36 @@ extern "C" float* nele_disc_workspace_ddin(void* workspace, int B, int T, int ci
     return reinterpret_cast<float*>(w.ddin.p);
 }
 
+// One buffer of a discriminator workspace (tests): "act0".."act4" (layer outputs), "gbuf0".."gbuf4" (their zero-bordered gradients),
+// "pooled" [B][64], "gbuf16" (the bf16 pooling gradient, bf16 mode), "ddin".  -> its device pointer and *elsize (2: bfloat16, 4: float32), or NULL where this layout has no such buffer.
+extern "C" void* nele_disc_workspace_buffer(void* workspace, int B, int T, int cin, int bf16, const char* name, int* elsize) {
+    DWs w;
+    if (!workspace || !name || B <= 0 || T < 21 || d_layout(B, T, cin, bf16 != 0, workspace, w)) return nullptr;
+    const Buf* b = nullptr;
+    if (!strncmp(name, "act", 3) && name[3] >= '0' && name[3] <= '4' && !name[4]) b = &w.act[name[3] - '0'];
+    else if (!strncmp(name, "gbuf", 4) && name[4] >= '0' && name[4] <= '4' && !name[5]) b = &w.gbuf[name[4] - '0'];
+    else if (!strcmp(name, "pooled")) b = &w.pooled;
+    else if (!strcmp(name, "gbuf16")) b = &w.gbuf16;
+    else if (!strcmp(name, "ddin")) b = &w.ddin;
+    if (!b || !b->p) return nullptr;
+    if (elsize) *elsize = b->b16 ? 2 : 4;
+    return b->p;
+}
+
 extern "C" int nele_disc_plan_build(int B, int T, int cin, int nout, int bf16, int train, int need_din, int weight_grads, int overlap_wgrad, const float* params_flat,
                                     float* grads_flat, const void* const* sn_uv_host, void* workspace, long long workspace_bytes, void* stream, void** fwd_out,
                                     void** bwd_out) {
     NELE_CHECK_ARG(B > 0 && T >= 21 && cin >= 1 && cin <= 4 && nout >= 1 && nout <= 4 && params_flat && sn_uv_host && workspace && fwd_out && (!bwd_out || grads_flat),
                    "nele_disc_plan_build: bad arguments (T >= 21, cin 1..4, nout 1..4)");
-    DWs w;
-    { const int st = d_layout(B, T, cin, bf16 != 0, workspace, w); if (st) return st; }
-    if (workspace_bytes < (long long)w.bytes) return nele_set_error(NELE_ERR_WORKSPACE, "nele_disc_plan_build: workspace too small (%lld < %lld)", workspace_bytes, (long long)w.bytes);
-    if (hipMemsetAsync(workspace, 0, w.bytes, as_stream(stream)) != hipSuccess) return nele_set_error(NELE_ERR_HIP, "nele_disc_plan_build: hipMemsetAsync failed");
-    const DParams pp = d_params(cin, nout);
-    const long long din_bytes = (long long)B * 64 * T * 4 * 4, sc_bytes = (long long)B * nout * 4;
-    {
-        Builder b;
-        d_prepare(b, w, params_flat, pp, sn_uv_host, cin, bf16 != 0, train != 0);
-        d_forward(b, w, params_flat, pp, B, T, nout, bf16 != 0);
-        void* h = nullptr;
-        const int st = b.finish(3, &h);
-        if (st) return st;
-        nele_plan_declare_slot(h, 0, din_bytes, 0); nele_plan_declare_slot(h, 1, (long long)B * 4, 1); nele_plan_declare_slot(h, 2, sc_bytes, 0);
-        *fwd_out = h;
-    }
-    if (bwd_out) {
-        Builder b;
-        d_backward(b, w, params_flat, grads_flat, pp, sn_uv_host, B, T, cin, nout, bf16 != 0, need_din != 0, weight_grads != 0, overlap_wgrad != 0);
-        void* h = nullptr;
-        const int st = b.finish(4, &h);
-        if (st) { (void)nele_plan_destroy(*fwd_out); *fwd_out = nullptr; return st; }
-        nele_plan_declare_slot(h, 0, sc_bytes, 0); nele_plan_declare_slot(h, 1, sc_bytes, 0); nele_plan_declare_slot(h, 2, (long long)B * 4, 1);
-        nele_plan_declare_slot(h, 3, din_bytes, 0);
-        *bwd_out = h;
-    }
-    return NELE_OK;
+    return disc_build("nele_disc_plan_build", B, T, cin, nout, bf16, train, need_din, weight_grads, overlap_wgrad, params_flat, grads_flat, sn_uv_host, workspace,
+                      workspace_bytes, 1, stream, true, nullptr, fwd_out, bwd_out);
+}
+
+extern "C" int nele_disc_plans_build(int B, int T, int cin, int nout, int bf16, int need_din, int weight_grads, int overlap_wgrad, const float* params_flat,
+                                     float* grads_flat, const void* const* sn_uv_host, void* workspace, long long workspace_bytes, int zero_fill, void* stream,
+                                     void** prep_out, void** fwd_out, void** bwd_out) {
+    NELE_CHECK_ARG(B > 0 && T >= 21 && cin >= 1 && cin <= 4 && nout >= 1 && nout <= 4 && params_flat && sn_uv_host && workspace && (!bwd_out || grads_flat),
+                   "nele_disc_plans_build: bad arguments (T >= 21, cin 1..4, nout 1..4)");
+    return disc_build("nele_disc_plans_build", B, T, cin, nout, bf16, 0, need_din, weight_grads, overlap_wgrad, params_flat, grads_flat, sn_uv_host, workspace,
+                      workspace_bytes, zero_fill, stream, false, prep_out, fwd_out, bwd_out);
 }

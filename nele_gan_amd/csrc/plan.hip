@@ -5,9 +5,8 @@
 // handful of pointers (the batch's inputs and outputs) and counters.  Driven from the host language one call at a time, a B = 32
 // GAN_epoch step spent 3.6 of its 5.6 ms in ~300 foreign-function calls.  A PLAN is that sequence recorded once per shape -
 // op code + arguments, each argument either a constant or "slot k + offset" of a small array supplied per call - and nele_plan_run
-// enqueues it with ONE call: same kernels, same order, same streams and hand-over events, bit-identical results.  The host mirror
-// (nele_gan_amd/_lib.py: PlanRecorder) builds plans by recording its own per-layer loop the first time a shape is seen, so the layer
-// logic exists once.  Not a HIP graph: the per-call pointers stay free (torch allocates outputs per step), nothing is captured, and the
+// enqueues it with ONE call: same kernels, same order, same streams and hand-over events, bit-identical results.  The generator's and
+// the discriminators' plans are built by csrc/netplan.hip, so the layer logic exists once.  Not a HIP graph: the per-call pointers stay free (torch allocates outputs per step), nothing is captured, and the
 // launches go to whatever streams the caller passes.
 #include "common.h"
 #include "../../include/nele_hip.h"

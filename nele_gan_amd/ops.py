@@ -7,9 +7,6 @@ import torch
 from . import _lib
 from ._lib import c_float, c_int, c_longlong, c_void_p, call, declare, ptr, stream
 
-EPI_NONE, EPI_BIAS, EPI_BIAS_LRELU, EPI_MASK_LRELU_GRAD, EPI_BIAS_EXPTANH = 0, 1, 2, 3, 4
-SLOPE = 0.3  # nn.LeakyReLU(0.3), model.py:79,112
-
 _P = c_void_p
 _SIGS = {
     'nele_conv_gemm': [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, ctypes.POINTER(c_int), _P],
@@ -89,24 +86,6 @@ _lib.lib.nele_conv_wgrad_workspace_floats.restype = c_longlong
 _lib._SIGS['nele_conv_wgrad_workspace_floats'] = _lib.lib.nele_conv_wgrad_workspace_floats.argtypes
 
 
-class Geom:
-    """ConvGeom of csrc/dense.hip: how output position (b,ho,wo) maps into the channels-last input
-    buffer [B][H][W][C] and the output buffer [B][OH][OW][OC]."""
-
-    def __init__(self, H, W, C, Hout, Wout, KH, KW, OH, OW, OC, ih0=0, iw0=0, oh0=0, ow0=0):
-        self.KH, self.KW = KH, KW
-        self.Hout, self.Wout = Hout, Wout
-        self.Ktot = KH * KW * C
-        vals = [H, W, C, ih0, iw0, Hout, Wout, KW * C, W * C, self.Ktot, OH, OW, OC, oh0, ow0]
-        self.arr = (c_int * 15)(*vals)
-
-
-# Module-level test knobs (tests monkeypatch them; nothing reads the environment): False = the discriminator keeps float32 activations /
-# a float32 pooling gradient in memory - the round-2 kernels, which remain the path for geometries the bf16-in-memory kernels decline.
-CONV16 = True
-GRAD16 = True
-
-
 def side_stream(device):
     """A new side stream - or, with NELE_SERIAL=1 (diagnostic: every kernel then runs alone and a rocprofv3 kernel trace shows
     isolated durations), the current stream itself, which serialises the whole step.
@@ -160,188 +139,21 @@ def streams_on_distinct_queues(device, n, have=()):
     return out
 
 
-class Events:
-    """Hand-over events between the streams of one pass, created once per buffer set and addressed by position: a recorded plan
-    (_lib.PlanRecorder) holds their handles, so the n-th fork of a pass must always use the n-th event."""
-
-    def __init__(self):
-        self.ev = []
-        self.k = 0
-
-    def start(self):
-        self.k = 0
-
-    def next(self):
-        if self.k == len(self.ev):
-            h = c_void_p()
-            _lib.check(_lib.lib.nele_event_create(ctypes.byref(h)), 'nele_event_create')
-            self.ev.append(h)
-        self.k += 1
-        return self.ev[self.k - 1]
-
-    def __del__(self):
-        try:
-            for h in self.ev:
-                _lib.lib.nele_event_destroy(h)
-        except Exception:
-            pass
-
-
-def hand_over(events, src, dst):
-    """stream ``dst`` waits for everything enqueued on stream ``src`` so far (two plan-recordable library calls)."""
-    ev = events.next()
-    call('nele_event_record', ev, c_void_p(src.cuda_stream))
-    call('nele_stream_wait_event', ev, c_void_p(dst.cuda_stream))
-
-
-def vec_add_(dst, src):
-    """dst += src (float32, same length) as a plan-recordable library call."""
-    call('nele_vec_add', c_void_p(dst.data_ptr()), c_void_p(src.data_ptr()), dst.numel(), stream())
-
-
-def plans_enabled():
-    """Passes are replayed from recorded job tables unless switched off (_lib.PLANS) or a torch-event profile of single launches is armed."""
-    return _lib.PLANS and PROFILE is None
-
-
-def rng(t):
-    """(address, bytes) of a tensor for PlanRecorder's dynamic slots"""
-    return (t.data_ptr(), t.numel() * t.element_size())
-
-
-# bench.py sets PROFILE = {tag: [(start_event, end_event), ...]} to time one tagged kernel with HIP events
-# recorded on the stream the kernel is launched on (torch's current stream).
+# bench.py sets PROFILE = {tag: [], ...} to time single launches of the discriminator in float32 mode: while it is set, every forward pass
+# of a discriminator appends (start, end, work) for its conv5 launch to PROFILE[profile_prefix + 'D.conv5.fwd'] and every backward pass
+# for conv5's weight gradient to PROFILE['D.conv5.wgrad'], when those lists exist; start.elapsed_time(end) is the launch's duration in ms
+# (the library's HIP-event hook, collected - synchronising - right after the pass).
 PROFILE = None
 
 
-def conv_gemm(A, Wg, bias, aux, out, B, N, epi, g, tag=None, bf16=False):
-    M = B * g.Hout * g.Wout
-    prof = PROFILE is not None and tag in PROFILE
-    if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    call('nele_conv_gemm_bf16' if (bf16 and N > 48) else 'nele_conv_gemm', ptr(A), ptr(Wg), ptr(bias), ptr(aux), ptr(out), M, N, epi, SLOPE, g.arr, stream())
-    if prof:
-        e1.record()
-        PROFILE[tag].append((e0, e1, 2.0 * M * N * g.Ktot))
+class Ms:
+    """A measured duration with torch.cuda.Event's interface: Ms(0).elapsed_time(Ms(ms)) == ms."""
 
+    def __init__(self, ms):
+        self.ms = ms
 
-def span_supported(B, N, g):
-    return bool(_lib.lib.nele_conv_span_supported(B * g.Hout * g.Wout, N, g.arr, g.KH, g.KW))
-
-
-def frag_floats(N, Ktot):
-    return (Ktot // 8) * ((N + 15) // 16) * 128
-
-
-def weight_prep_frag(Wg, N, Ktot, Wfrag):
-    call('nele_weight_prep_frag', ptr(Wg), N, Ktot, ptr(Wfrag), stream())
-
-
-def conv_span(A, Wfrag, bias, aux, out, B, N, epi, g, tag=None):
-    M = B * g.Hout * g.Wout
-    prof = PROFILE is not None and tag in PROFILE
-    if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    call('nele_conv_span', ptr(A), ptr(Wfrag), ptr(bias), ptr(aux), ptr(out), M, N, epi, SLOPE, g.arr, g.KH, g.KW, A.numel(), stream())
-    if prof:
-        e1.record()
-        PROFILE[tag].append((e0, e1, 2.0 * M * N * g.Ktot))
-
-
-def span16_supported(B, N, g):
-    return bool(_lib.lib.nele_conv_span_bf16_supported(B * g.Hout * g.Wout, N, g.arr, g.KH, g.KW))
-
-
-def grad16_supported(B, N_dgrad, g_dgrad, N_wgrad, g_wgrad):
-    """Can this layer's output gradient live in memory as bfloat16?  (data gradient on the span kernel, weight gradient on the tile kernel)"""
-    if not GRAD16:
-        return False
-    return bool(_lib.lib.nele_conv_span_bf16_a16_supported(B * g_dgrad.Hout * g_dgrad.Wout, N_dgrad, g_dgrad.arr, g_dgrad.KH, g_dgrad.KW)) and \
-        bool(_lib.lib.nele_conv_wgrad_bf16_d16_supported(B * g_wgrad.Hout * g_wgrad.Wout, N_wgrad, g_wgrad.arr, g_wgrad.KH, g_wgrad.KW))
-
-
-def frag16_elems(N, seglen, KH):
-    return int(_lib.lib.nele_weight_frag16_elems(N, seglen, KH))
-
-
-def weight_prep_frag16(Wg, N, Ktot, seglen, KH, Wfrag):
-    call('nele_weight_prep_frag16', ptr(Wg), N, Ktot, seglen, KH, ptr(Wfrag), stream())
-
-
-def conv_span_bf16(A, Wfrag, bias, aux, out, B, N, epi, g, tag=None):
-    """A float32, or bfloat16 (nele_conv_span_bf16_a16: the span kernel only)."""
-    M = B * g.Hout * g.Wout
-    prof = PROFILE is not None and tag in PROFILE
-    if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    call('nele_conv_span_bf16_a16' if A.dtype == torch.bfloat16 else 'nele_conv_span_bf16', ptr(A), ptr(Wfrag), ptr(bias), ptr(aux), ptr(out), M, N, epi, SLOPE,
-         g.arr, g.KH, g.KW, A.numel(), stream())
-    if prof:
-        e1.record()
-        PROFILE[tag].append((e0, e1, 2.0 * M * N * g.Ktot))
-
-
-def conv16_supported(B, N, g):
-    """Can this layer run on the bf16-activation tile kernel (csrc/conv16.hip)?"""
-    if not CONV16:
-        return False
-    return bool(_lib.lib.nele_conv16_supported(B * g.Hout * g.Wout, N, g.arr, g.KH, g.KW))
-
-
-def wgrad_tile_supported(B, N, g):
-    """Does this layer's weight gradient run on the 2-D tile kernel (the one that takes bf16 operands from memory)?"""
-    return bool(_lib.lib.nele_conv_wgrad_bf16_d16_supported(B * g.Hout * g.Wout, N, g.arr, g.KH, g.KW))
-
-
-def conv16_pointwise_fwd(din, Wf, bias, out16):
-    """D's first layer (1 x 1, 4 -> 8 channels) on the packed float32 input, bf16 activation out."""
-    M = din.numel() // 4
-    call('nele_conv16_pointwise_fwd', ptr(din), ptr(Wf), ptr(bias), ptr(out16), M, 8, SLOPE, stream())
-
-
-def conv16_wfrag_elems(N, seglen, KH):
-    return int(_lib.lib.nele_conv16_wfrag_elems(N, seglen, KH))
-
-
-def conv16(A16, Wfrag, bias, aux16, out, B, N, epi, g, tag=None):
-    """Conv2d forward / data gradient on bfloat16 activations: A16 [B][H][W][C] bf16, out bf16 or float32 (by its dtype),
-    aux16 = forward activation (bf16) for the LeakyReLU mask of a data gradient."""
-    M = B * g.Hout * g.Wout
-    if A16.dtype != torch.bfloat16 or (aux16 is not None and aux16.dtype != torch.bfloat16):
-        raise ValueError('conv16: activations must be bfloat16')
-    prof = PROFILE is not None and tag in PROFILE
-    if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    call('nele_conv16', ptr(A16), ptr(Wfrag), ptr(bias), ptr(aux16), ptr(out), int(out.dtype == torch.bfloat16), M, N, epi, SLOPE, g.arr, g.KH, g.KW,
-         stream())
-    if prof:
-        e1.record()
-        PROFILE[tag].append((e0, e1, 2.0 * M * N * g.Ktot))
-
-
-def conv16_gap_parts(N, g):
-    """Pooled partial sums per image that conv16_gap writes for this geometry (0: unsupported)"""
-    return int(_lib.lib.nele_conv16_gap_parts(N, g.arr, g.KH, g.KW))
-
-
-def conv16_gap(A16, Wfrag, bias, out16, B, N, g, wvalid, gap_part, tag=None):
-    """The last conv layer with the global average pooling fused (model.py:109,121-123): out16 = bf16(LeakyReLU(conv + bias)),
-    gap_part [B][parts][N] float64 pooled partial sums over each image's valid columns."""
-    M = B * g.Hout * g.Wout
-    if A16.dtype != torch.bfloat16 or out16.dtype != torch.bfloat16 or gap_part.dtype != torch.float64:
-        raise ValueError('conv16_gap: bfloat16 activations and float64 partial sums')
-    prof = PROFILE is not None and tag in PROFILE
-    if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    call('nele_conv16_gap', ptr(A16), ptr(Wfrag), ptr(bias), ptr(out16), M, N, SLOPE, g.arr, g.KH, g.KW, ptr(wvalid), ptr(gap_part), stream())
-    if prof:
-        e1.record()
-        PROFILE[tag].append((e0, e1, 2.0 * M * N * g.Ktot))
+    def elapsed_time(self, other):
+        return other.ms
 
 
 def glayer16_supported(cin, cout, k):
@@ -351,36 +163,6 @@ def glayer16_supported(cin, cout, k):
 
 def glayer16_wfrag_elems(cin, cout, k):
     return int(_lib.lib.nele_glayer16_wfrag_elems(cin, cout, k))
-
-
-def wgrad_workspace_floats(B, N, g):
-    M = B * g.Hout * g.Wout
-    return int(_lib.lib.nele_conv_wgrad_workspace_floats(M, N, g.Ktot, None))
-
-
-def conv_wgrad(A, dOut, ws, B, N, g, Cvalid, dW, db, accumulate=True, bf16=False, tag=None):
-    M = B * g.Hout * g.Wout
-    prof = PROFILE is not None and tag in PROFILE
-    if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    fn = 'nele_conv_wgrad_bf16' if bf16 else 'nele_conv_wgrad'
-    if dOut.dtype == torch.bfloat16:
-        if not bf16:
-            raise ValueError('conv_wgrad: a bfloat16 output gradient needs bf16=True')
-        fn = 'nele_conv_wgrad_bf16_a16d16' if A.dtype == torch.bfloat16 else 'nele_conv_wgrad_bf16_d16'
-    elif A.dtype == torch.bfloat16:
-        raise ValueError('conv_wgrad: a bfloat16 activation needs a bfloat16 output gradient')
-    call(fn, ptr(A), ptr(dOut), ptr(ws), ws.numel(), M, N, g.arr, g.KH, g.KW, Cvalid, ptr(dW), ptr(db), int(accumulate), stream())
-    if prof:
-        e1.record()
-        # algorithmic bytes: the input and the output gradient read once (float32), the weight gradient written once
-        PROFILE[tag].append((e0, e1, 4.0 * (B * g.arr[0] * g.arr[1] * g.arr[2] + M * N + N * g.Ktot)))
-
-
-def weight_prep(Wt, sigma, N, Cvalid, C, KH, KW, Wf, Wb):
-    call('nele_weight_prep', ptr(Wt), ptr(sigma), N, Cvalid, C, KH, KW, ptr(Wf), ptr(Wb), stream())
-
 
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, guard=None):
     if guard is not None:

@@ -281,80 +281,134 @@ def test_bf16_tile_kernels_on_ragged_frame_counts(mods, T):
         assert (a[i] * b[i]).sum() > 0.9999 * np.linalg.norm(a[i]) * np.linalg.norm(b[i]), i
 
 
-def test_bf16_pooling_gradient_buffer_gives_the_float32_buffers_gradients(mods, monkeypatch):
+# ------------------------------------------------------------------ A/B forms of the discriminator's / generator's passes (libnele_hip_ab.so)
+_AB_CHILD = r'''
+import sys, ctypes, numpy as np, torch
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + '/tests')
+from nele_gan_amd import model, _lib
+from weights_recipe import seeded_state_arrays
+
+def load_recipe(module, seed):
+    sd = module.state_dict()
+    arrs = seeded_state_arrays([(k, tuple(v.shape)) for k, v in sd.items()], seed)
+    module.load_state_dict({k: torch.from_numpy(v) for k, v in arrs.items()})
+    return module.cuda()
+
+def d_buffer(D, name, shape):
+    """a buffer of D's (only) workspace as float32, and its element size in memory (the library reports where it lives)"""
+    (B, T, _, prec), ws = next(iter(D._bufs.items()))
+    es = ctypes.c_int(0)
+    p = _lib.lib.nele_disc_workspace_buffer(ws.buf.data_ptr(), B, T, 3, int(prec == 'bf16'), name.encode(), ctypes.byref(es))
+    if not p:
+        return None, 0
+    off, n = p - ws.buf.data_ptr(), int(np.prod(shape))
+    t = ws.buf[off:off + n * es.value].view(torch.bfloat16 if es.value == 2 else torch.float32)
+    return t.float().view(shape).cpu().numpy(), es.value
+
+out = {}
+which = sys.argv[3]
+if which == 'G':
+    for B, T in [(1, 30), (2, 40), (3, 251), (2, 501), (1, 600)]:
+        g = torch.Generator().manual_seed(7)
+        x, y = torch.rand(B, T, 64, generator=g).cuda(), torch.rand(B, T, 64, generator=g).cuda()
+        gw = torch.randn(B, T, 64, generator=g).cuda()
+        G = load_recipe(model.Generator_Conv1D_cLN(), 101)
+        G.precision = 'bf16'
+        mask = G(x, y)
+        G.flat_parameters().grad.zero_()
+        (mask * gw).sum().backward()
+        G.eval()
+        with torch.no_grad():
+            me = G(x, y)
+        for k, v in (('mask', mask), ('grad', G.flat_parameters().grad), ('eval', me)):
+            out['%d_%d_%s' % (B, T, k)] = v.detach().cpu().numpy()
+else:
+    B, T = 3, 251
+    torch.manual_seed(5 if which == 'grad16' else 6)
+    x = torch.rand(B, 3, 64, T, device='cuda') * 2
+    D = load_recipe(model.Discriminator(), 33 if which == 'grad16' else 34)
+    D.precision = 'bf16'
+    D.eval()
+    xin = x.clone().requires_grad_(True)
+    score = D(xin)
+    score.pow(2).sum().backward()
+    out['score'], out['din'] = score.detach().cpu().numpy(), xin.grad.cpu().numpy()
+    for k, p in D.named_parameters():
+        out['p.' + k] = p.grad.cpu().numpy()
+    dims, H, W = [], 64, T
+    for co, k in ((8, 1), (16, 3), (32, 5), (48, 7), (64, 9)):
+        H, W = H - k + 1, W - k + 1
+        dims.append((B, H, W, co, k - 1))
+    for l, (b, h, w, co, p) in enumerate(dims):
+        out['act%d' % l], out['act%d_es' % l] = d_buffer(D, 'act%d' % l, (b, h, w, co))
+        out['gbuf%d_es' % l] = d_buffer(D, 'gbuf%d' % l, (b, h + 2 * p, w + 2 * p, co))[1]
+    out['pooled'] = d_buffer(D, 'pooled', (B, 64))[0]
+    b, h, w, co, p = dims[-1]
+    out['gbuf16_es'] = d_buffer(D, 'gbuf16', (b, h + 2 * p, w + 2 * p, co))[1]
+np.savez(sys.argv[2], **out)
+'''
+
+
+def _ab_run(tmp_path, which, **flags):
+    import subprocess
+    import sys
+    from conftest import ab_env
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = []
+    for flag in ('1', '0'):
+        out = str(tmp_path / ('%s_%s.npz' % (which, flag)))
+        env = ab_env(**{k: (v if v is not None else flag) for k, v in flags.items()})
+        subprocess.run([sys.executable, '-c', _AB_CHILD, root, out, which], check=True, env=env, timeout=300)
+        res.append(dict(np.load(out)))
+    return res
+
+
+def test_ab_bf16_pooling_gradient_buffer_gives_the_float32_buffers_gradients(tmp_path):
     """bf16 mode stores the last conv layer's output gradient (the pooling gradient) as bfloat16 where the span / tile kernels take it
     (nele_gap_mlp_bwd_var16 -> nele_conv_span_bf16_a16 + nele_conv_wgrad_bf16_d16).  Both consumers round that operand to bf16 anyway, so
     everything the data-gradient chain produces - the input gradient and every other layer's weight gradient - must be BIT-identical to the
-    float32-buffer path (ops.GRAD16 = False), conv5's weight gradient too (same bf16 operands, same accumulation order); only conv5's bias
+    float32-buffer path (NELE_D_GRAD16=0), conv5's weight gradient too (same bf16 operands, same accumulation order); only conv5's bias
     gradient sums bf16-rounded instead of float32 values - and since the pooling gradient takes just two values per (utterance, channel),
-    that rounding does not average out: up to 2^-8 relative, inside the documented bf16-mode tolerance (3e-2)."""
-    from nele_gan_amd import ops
-    B, T = 3, 251
-    torch.manual_seed(5)
-    x = torch.rand(B, 3, 64, T, device='cuda') * 2
-    res = {}
-    monkeypatch.setattr(ops, 'CONV16', False)        # the round-2 kernels (float32 activations in memory): the fallback for geometries conv16 declines
-    for flag in ('1', '0'):
-        monkeypatch.setattr(ops, 'GRAD16', flag == '1')
-        D = load_recipe(mods.Discriminator(), 33)
-        D.precision = 'bf16'
-        D.eval()
-        xin = x.clone().requires_grad_(True)
-        D(xin).pow(2).sum().backward()
-        bf = next(iter(D._bufs.values()))
-        assert bf.grad16_ok == (flag == '1') and (bf.gbuf16 is not None) == (flag == '1')
-        res[flag] = (xin.grad.clone(), {k: p.grad.clone() for k, p in D.named_parameters() if p.grad is not None})
-    assert ops.grad16_supported.__doc__
-    gin1, g1 = res['1']
-    gin0, g0 = res['0']
-    assert torch.equal(gin1, gin0)
-    for k in g0:
-        if k.endswith('layers.4.bias') or k.endswith('layers.4.conv.bias'):
-            torch.testing.assert_close(g1[k], g0[k], rtol=4e-3, atol=4e-3 * float(g0[k].abs().max()))
+    that rounding does not average out: up to 2^-8 relative, inside the documented bf16-mode tolerance (3e-2).  Both runs keep float32
+    activations in memory (NELE_D_CONV16=0: the round-2 kernels, the fallback for geometries conv16 declines)."""
+    r1, r0 = _ab_run(tmp_path, 'grad16', NELE_D_CONV16='0', NELE_D_GRAD16=None)
+    assert r1['gbuf16_es'] == 2 and r0['gbuf16_es'] == 0                 # the workspace holds the bf16 pooling gradient only with the switch on
+    assert r1['act1_es'] == r0['act1_es'] == 4
+    assert np.array_equal(r1['din'], r0['din'])
+    for k in (k for k in r0 if k.startswith('p.')):
+        if k.endswith('layers.4.bias'):
+            np.testing.assert_allclose(r1[k], r0[k], rtol=4e-3, atol=4e-3 * float(np.abs(r0[k]).max()))
         else:
-            assert torch.equal(g1[k], g0[k]), k
+            assert np.array_equal(r1[k], r0[k]), k
 
 
-def test_bf16_activations_in_memory_change_nothing_but_the_bias_gradients(mods, monkeypatch):
+def test_ab_bf16_activations_in_memory_change_nothing_but_the_bias_gradients(tmp_path):
     """Round 3: in bf16 mode the activations of conv1..conv4 and the output gradients of conv2..conv5 are STORED as bfloat16
     (csrc/conv16.hip; nele_conv_wgrad_bf16_a16d16).  Every consumer of those tensors rounded them to bf16 while staging them, so the MFMA
-    operands are the same numbers as with float32 buffers (ops.CONV16 = False: the round-2 kernels), accumulated over k in the same order:
+    operands are the same numbers as with float32 buffers (NELE_D_CONV16=0: the round-2 kernels), accumulated over k in the same order:
     scores and input gradient must be BIT-identical, the weight gradients equal up to their summation order (round 4, see below).  Only the bias gradients of conv2..conv5 sum bf16-rounded
-    instead of float32 output gradients (the same documented effect as for conv5 in round 2)."""
-    from nele_gan_amd import ops
-    B, T = 3, 251
-    torch.manual_seed(6)
-    x = torch.rand(B, 3, 64, T, device='cuda') * 2
-    res = {}
-    for flag in ('1', '0'):
-        monkeypatch.setattr(ops, 'CONV16', flag == '1')
-        D = load_recipe(mods.Discriminator(), 34)
-        D.precision = 'bf16'
-        D.eval()
-        xin = x.clone().requires_grad_(True)
-        score = D(xin)
-        score.pow(2).sum().backward()
-        bf = next(iter(D._bufs.values()))
-        assert bf.c16 == (flag == '1')
-        assert (bf.act[0].dtype == torch.bfloat16) == (flag == '1') and (bf.act[4].dtype == torch.bfloat16) == (flag == '1') and bf.gbuf[0].dtype == torch.float32
-        res[flag] = (score.detach().clone(), xin.grad.clone(), {k: p.grad.clone() for k, p in D.named_parameters() if p.grad is not None},
-                     [a.float().clone() for a in bf.act], bf.pooled.clone())
-    s1, gin1, g1, a1, p1 = res['1']
-    s0, gin0, g0, a0, p0 = res['0']
+    instead of float32 output gradients (the same documented effect as for conv5 in round 2).  What the workspace stores - dtypes,
+    activations, pooled features - is read at the offsets the library reports (nele_disc_workspace_buffer)."""
+    r1, r0 = _ab_run(tmp_path, 'conv16', NELE_D_CONV16=None)
+    for r, c16 in ((r1, True), (r0, False)):
+        assert all(r['act%d_es' % l] == (2 if c16 else 4) for l in range(5))          # conv1..conv5 activations bf16 exactly in conv16 mode
+        assert r['gbuf0_es'] == 4 and all(r['gbuf%d_es' % l] == (2 if c16 else 4) for l in range(1, 5))
     # the pooling fused into conv5's epilogue (per-wave float64 partial sums of the float32 results) against the separate pooling pass
-    torch.testing.assert_close(p1, p0, rtol=1e-6, atol=1e-7)
+    np.testing.assert_allclose(r1['pooled'], r0['pooled'], rtol=1e-6, atol=1e-7)
     for l in range(5):                                      # activations: what is stored is the bf16 rounding of what the float32 path stores
-        assert torch.equal(a1[l], a0[l].bfloat16().float()), 'activation of conv%d' % (l + 1)      # (conv5 too: pooled from the float32 results in the conv kernel)
-    assert torch.equal(s1, s0) and torch.equal(gin1, gin0)
-    for k in g0:
-        if '.bias' in k and k.startswith('layers.') and not k.startswith('layers.0.'):
-            torch.testing.assert_close(g1[k], g0[k], rtol=8e-3, atol=8e-3 * float(g0[k].abs().max()))
-        elif 'weight' in k and k.startswith('layers.') and not k.startswith('layers.0.'):
+        a0 = torch.from_numpy(r0['act%d' % l]).bfloat16().float().numpy()
+        assert np.array_equal(r1['act%d' % l], a0), 'activation of conv%d' % (l + 1)   # (conv5 too: pooled from the float32 results in the conv kernel)
+    assert np.array_equal(r1['score'], r0['score']) and np.array_equal(r1['din'], r0['din'])
+    for k in (k for k in r0 if k.startswith('p.')):
+        n = k[2:]
+        if '.bias' in n and n.startswith('layers.') and not n.startswith('layers.0.'):
+            np.testing.assert_allclose(r1[k], r0[k], rtol=8e-3, atol=8e-3 * float(np.abs(r0[k]).max()))
+        elif 'weight' in n and n.startswith('layers.') and not n.startswith('layers.0.'):
             # round 4: with both operands bf16 in memory the weight gradients of conv2..conv5 run on conv_wgrad_dma_kernel (several kernel
             # rows per workgroup, other position-tile groups): the same bf16 products, float32 sums in another order
-            torch.testing.assert_close(g1[k], g0[k], rtol=0, atol=4e-6 * float(g0[k].abs().max()))
+            np.testing.assert_allclose(r1[k], r0[k], rtol=0, atol=4e-6 * float(np.abs(r0[k]).max()))
         else:
-            assert torch.equal(g1[k], g0[k]), k
+            assert np.array_equal(r1[k], r0[k]), k
 
 
 @pytest.mark.parametrize('B,T', [(1, 21), (2, 37), (1, 52), (2, 53), (3, 85), (2, 149)])
@@ -451,87 +505,95 @@ def test_fused_generator_layer_against_torch_float64(mods, B, T, cin, cout, K):
     assert float((d.double() - (ry - bias.double())).abs().max()) <= 2e-5 * scale
 
 
+@pytest.fixture(scope='module')
+def fused_runs(tmp_path_factory):
+    """the generator in bf16 mode with the fused layer kernels (NELE_G_FUSED=1) and with the per-layer kernels (0), every shape below"""
+    return _ab_run(tmp_path_factory.mktemp('gfused'), 'G', NELE_G_FUSED=None)
+
+
 @pytest.mark.parametrize('B,T', [(1, 30), (2, 40), (3, 251), (2, 501), (1, 600)])
-def test_fused_generator_equals_per_layer_kernels_in_bf16_mode(mods, B, T):
+def test_fused_generator_equals_per_layer_kernels_in_bf16_mode(fused_runs, B, T):
     """Generator_Conv1D_cLN in bf16 mode: the fused layer path (bf16 activations in memory) against the per-layer kernels (float32
-    activations rounded while staged).  The same bf16 products; the float32 sums run in another order, so a layer's activations differ
+    activations rounded while staged; NELE_G_FUSED=0 in the A/B library).  The same bf16 products; the float32 sums run in another order, so a layer's activations differ
     in the last float32 bits and a few of them round to the neighbouring bf16 value (2^-8 relative) on their way into the next layer:
     the masks (exp(3.2 tanh(.)) of the sixth layer's output) agree to a fraction of the bf16-against-float32 tolerance (6e-2, test above).
     A difference d between two float32 values flips their bf16 rounding with probability d / 2^-8, so a relative difference d becomes
     sqrt(d 2^-8) one layer on: measured 2e-7, 4e-6, 8e-5, 3e-4, 7e-4, 1.3e-3 over the six layers (the bf16-against-float32 difference
     of the same tensors: 2e-3 .. 6e-3).  The backward pass consumes the float32 copies the fused forward pass writes and amplifies the
     forward difference as it amplifies bf16's (LeakyReLU kinks, tanh'): gradients 3e-2 apart where bf16 and float32 are 8e-2 apart."""
-    g = torch.Generator().manual_seed(7)
-    x, y = torch.rand(B, T, 64, generator=g).cuda(), torch.rand(B, T, 64, generator=g).cuda()
-    gw = torch.randn(B, T, 64, generator=g).cuda()
-    res = {}
-    for fused in (False, True):
-        G = load_recipe(mods.Generator_Conv1D_cLN(), 101)
-        G.precision = 'bf16'
-        G.fused = fused
-        mask = G(x, y)
-        G.flat_parameters().grad.zero_()
-        (mask * gw).sum().backward()
-        G.eval()
-        with torch.no_grad():
-            me = G(x, y)
-        res[fused] = (mask.detach().clone(), G.flat_parameters().grad.clone(), me.clone())
-    a, b = res[False], res[True]
+    r1, r0 = fused_runs
+    a, b = [[torch.from_numpy(r['%d_%d_%s' % (B, T, k)]) for k in ('mask', 'grad', 'eval')] for r in (r0, r1)]
     assert float((a[0] - b[0]).abs().max()) <= 1e-2 * float(a[0].abs().max())
     assert float((a[0] - b[0]).norm()) <= 1e-2 * float(a[0].norm())
     assert float((a[2] - b[2]).abs().max()) <= 1e-2 * float(a[2].abs().max())
     if T >= 32:
         assert torch.equal(b[0], b[2])                                    # train- and eval-mode forward passes of the fused path: the same kernels
-    else:                                                                 # below 32 frames a training pass keeps the per-layer kernels (model._fused_for)
+    else:                                                                 # below 32 frames a training pass keeps the per-layer kernels (csrc/netplan.hip g_layout)
         assert torch.equal(b[0], a[0]) and float((b[0] - b[2]).abs().max()) <= 1e-2 * float(b[0].abs().max())
     assert float((a[1] - b[1]).norm()) <= 6e-2 * float(a[1].norm())
 
 
-# ------------------------------------------------------------------ round 5: composite entry points (recorded job tables, csrc/plan.hip)
+# ------------------------------------------------------------------ composite entry points (library-built job tables, csrc/netplan.hip)
 @pytest.mark.parametrize('prec', ['f32', 'bf16'])
-def test_recorded_plans_replay_bit_identically(mods, prec):
-    """nele_gen_fwd / nele_gen_bwd / nele_disc_fwd / nele_disc_bwd enqueue the job table that the host mirror recorded from its own per-layer
-    loop the first time a shape came by.  Call-by-call (_lib.PLANS = False), the recording pass and every replay must give the same bits:
-    masks, scores, input gradients and the flat parameter gradients of G and D, over two different batches (the per-call pointers - inputs,
-    outputs, carry tokens - are the plan's slots), with D's weight gradients on (D-step) and off (G-step) and a padded batch."""
-    from nele_gan_amd import _lib
+def test_every_plan_form_is_independent_of_the_forms_run_before(mods, prec):
+    """The modules keep one workspace per (shape, precision, slot, mode) and every job table the library built over it: G's weight
+    preparation, training and evaluation forward passes and backward pass, D's preparation, forward pass (with and without per-utterance
+    frames) and its three backward forms - D-step (no input gradient), G-step (input gradient), G-step without weight gradients - the
+    later ones built over a workspace already in use.  Each form run on modules that have already run all the others must give the bits
+    of the same form on fresh modules: masks, scores, input gradients and the flat parameter gradients."""
     B, T = 3, 300                                                          # two strips of the fused generator layers
     g = torch.Generator().manual_seed(11)
     batches = [(torch.rand(B, T, 64, generator=g).cuda(), torch.rand(B, T, 64, generator=g).cuda(), torch.randn(B, T, 64, generator=g).cuda(),
                 torch.rand(B, 64, T, 4, generator=g).cuda(), torch.randn(B, 3, generator=g).cuda()) for _ in range(3)]
     frames = torch.tensor([300, 180, 251], dtype=torch.int32, device='cuda')
 
-    def run(plans):
-        _lib.PLANS = plans
-        try:
-            G = load_recipe(mods.Generator_Conv1D_cLN(), 101)
-            D = load_recipe(mods.Discriminator(), 202)
-            G.precision = D.precision = prec
-            out = []
-            for it, (x, y, gw, din, ds) in enumerate(batches):
-                mask = G(x, y)
-                G.flat_parameters().grad.zero_()
-                (mask * gw).sum().backward()
-                d_in = din.clone().requires_grad_(True)
-                D.weight_grad_enabled = it != 1                            # the G-step form in between
-                D.flat_parameters().grad.zero_()
-                score = D.forward_packed(d_in, frames if it == 2 else None)
-                (score * ds).sum().backward()
-                D.weight_grad_enabled = True
-                out.append([t.detach().clone() for t in (mask, G.flat_parameters().grad, score, d_in.grad, D.flat_parameters().grad)])
-            with torch.no_grad():
-                G.eval()
-                out.append([G(batches[0][0], batches[0][1]).clone(), G(batches[1][0], batches[1][1]).clone()])
-            nplans = sum(len(b.plans) for b in G._bufs.values()) + sum(len(b.plans) for b in D._bufs.values())
-            return out, nplans
-        finally:
-            _lib.PLANS = True
+    def g_train(G, D, k):
+        x, y, gw = batches[k][:3]
+        mask = G(x, y)
+        G.flat_parameters().grad.zero_()
+        (mask * gw).sum().backward()
+        return [mask.detach().clone(), G.flat_parameters().grad.clone()]
 
-    live, n0 = run(False)
-    rec, n1 = run(True)
-    assert n0 == 0 and n1 >= 6                                             # G fwd (train, eval) + bwd, D fwd (2 forms) + bwd (3 forms)
-    for a, b in zip(live, rec):
-        for u, v in zip(a, b):
+    def g_eval(G, D, k):
+        G.eval()
+        with torch.no_grad():
+            m = G(batches[k][0], batches[k][1]).clone()
+        G.train()
+        return [m]
+
+    def d_pass(need_din, wgrad, fr):
+        def run(G, D, k):
+            din, ds = batches[k][3:]
+            d_in = din.clone().requires_grad_(need_din)
+            D.weight_grad_enabled = wgrad
+            D.flat_parameters().grad.zero_()
+            score = D.forward_packed(d_in, fr)
+            (score * ds).sum().backward()
+            D.weight_grad_enabled = True
+            return [score.detach().clone(), D.flat_parameters().grad.clone()] + ([d_in.grad.clone()] if need_din else [])
+        return run
+
+    forms = [(g_train, 0), (d_pass(True, True, None), 0), (d_pass(True, False, frames), 1), (d_pass(False, True, frames), 2), (g_eval, 1),
+             (g_train, 1), (d_pass(True, True, frames), 2), (d_pass(False, True, None), 0)]
+
+    def modules():
+        G = load_recipe(mods.Generator_Conv1D_cLN(), 101)
+        D = load_recipe(mods.Discriminator(), 202)
+        D.eval()                                                           # (sigma from the stored u, v: no state carried between forms)
+        G.precision = D.precision = prec
+        return G, D
+
+    G, D = modules()
+    for f, k in forms:
+        f(G, D, k)
+    shared = [f(G, D, k) for f, k in forms]
+    assert sorted(len(w.plans) for w in G._bufs.values()) == [2, 3]      # eval: prep + fwd; training: prep + fwd + bwd
+    assert [len(w.plans) for w in D._bufs.values()] == [5]                # prep + fwd + the three backward forms
+    for (f, k), got in zip(forms, shared):
+        G1, D1 = modules()
+        want = f(G1, D1, k)
+        assert len(want) == len(got)
+        for u, v in zip(want, got):
             assert torch.equal(u, v)
 
 

@@ -64,9 +64,10 @@ def test_multistream_step_is_bit_identical_to_the_staged_sequence(precision):
     assert all(x == 0 for x in a.check_status().values())
 
 
-def test_delayed_side_streams_do_not_change_the_step():
+def test_delayed_side_streams_change_neither_the_step_nor_its_buffers():
     """Every cross-stream hand-over of canonical_step is ordered by events only.  Holding a side stream back (a 25 ms spin kernel in front
-    of D.prepare / of the clean-feature branch) must not change anything; and the flat parameter buffers must stay where they are
+    of D.prepare / of the clean-feature branch) must not change anything; and the flat parameter buffers, the modules' workspaces and the
+    job tables built over them must stay where they are
     (round 2: GanTrainer('cuda') handed an index-less device to D.prepare, torch.device('cuda') != torch.device('cuda:0') made every
     cache look stale, and D's parameters were re-homed into a fresh flat buffer on the side stream twice per step)."""
     from nele_gan_amd import audio_util as au
@@ -91,11 +92,15 @@ def test_delayed_side_streams_do_not_change_the_step():
             au.stft_band = orig_stft
         assert float(r1[0]) == float(r0[0]) and float(r1[1]) == float(r0[1]) and torch.equal(r1[2], r0[2]), which
         tr.D.prepare = orig_prepare
-        p0 = (tr.D.flat_parameters().flat.data_ptr(), tr.G.flat_parameters().flat.data_ptr(), tr.D._w['sigma'].data_ptr())
+        # nothing is reallocated or rebuilt across steps: the same parameter buffers, workspaces and job tables
+        def held():
+            return (tr.D.flat_parameters().flat.data_ptr(), tr.G.flat_parameters().flat.data_ptr(),
+                    [(k, w.buf.data_ptr(), dict(w.plans)) for m in (tr.D, tr.G) for k, w in m._bufs.items()])
+        p0 = held()
         tr.canonical_step(cw, nw)
         torch.cuda.synchronize()
-        assert p0 == (tr.D.flat_parameters().flat.data_ptr(), tr.G.flat_parameters().flat.data_ptr(), tr.D._w['sigma'].data_ptr())
-        assert len(tr.D._bufs) == 1 and len(tr.G._bufs) == 1
+        assert p0 == held()
+        assert len(tr.D._bufs) == 1 and len(tr.G._bufs) == 2                 # D; G's training and evaluation (generate) workspaces
 
 
 @pytest.mark.parametrize('what', ['all', 'features'])

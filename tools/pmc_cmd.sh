@@ -1,6 +1,6 @@
 #!/bin/bash
 # PMC summary of the kernels of ONE stand-alone python command (each kernel alone on the GPU):
-#   tools/pmc_cmd.sh "<kernel-name substrings, |-separated>" tools/conv16_check.py 256 5f
+#   tools/pmc_cmd.sh "<kernel-name substrings, |-separated>" tools/d_check.py 256
 # MFMA-busy, LDS-busy, bank-conflict share, wait fractions, and the clock the chip held (GRBM_GUI_ACTIVE / 8 XCDs / duration).
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; PAT=$1; shift
 for set in "SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_WAIT_INST_LDS" "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INST_CYCLES_VMEM" "GRBM_GUI_ACTIVE" "FETCH_SIZE" "WRITE_SIZE"; do
