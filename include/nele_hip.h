@@ -98,10 +98,15 @@ int nele_disc_bwd(void* plan, const float* dscore, const float* score, const int
  * (B, T, precision) which holds every activation, weight layout and temporary of both passes: the backward plan reads what the forward
  * plan left there.  *_plan_build zero-fills the workspace on `stream` (padding rows, zero borders, carry slots) and returns the plans;
  * run them with nele_gen_fwd / nele_gen_bwd / nele_disc_fwd / nele_disc_bwd (or nele_plan_run[_sized]) and release them with
- * nele_plan_destroy.  bf16 != 0: bf16 MFMA operands / float32 accumulate (BASELINE configs[1]); 0: float32 operands.
+ * nele_plan_destroy.  bf16 = precision code: NELE_PREC_F32 (0) float32 operands; NELE_PREC_BF16 (1, and any other value but 2) bf16 MFMA
+ * operands / float32 accumulate (BASELINE configs[1]); NELE_PREC_BF16X3 (2) split-operand bf16 products (hi*hi + hi*lo + lo*hi) for every
+ * k > 1 convolution pass, float32 activations, the float32 kernels for G's Linear layers, D.layers.0 and what the split kernels decline.
  * need_bwd: the forward plan keeps what a backward pass needs (and bwd_out is built).  overlap_wgrad != 0: weight gradients run on
  * side streams beside the data-gradient chain - streams_host then needs 2 (G) / 3 (D) streams - else everything on streams_host[0].
  * Gradients ACCUMULATE into grads_flat (zero it per optimiser step, as optimizer.zero_grad()). */
+#define NELE_PREC_F32 0
+#define NELE_PREC_BF16 1
+#define NELE_PREC_BF16X3 2
 long long nele_gen_param_count(void);
 int nele_gen_param_layout(long long* offsets_host, int n /* >= 28 */);
 long long nele_gen_workspace_bytes(int B, int T, int bf16, int need_bwd);
@@ -265,6 +270,21 @@ int nele_conv_span_bf16(const float* A, const void* Wfrag, const float* bias, co
                         float slope, const int* geom_host, int KH, int KW, long long a_elems, void* stream);
 int nele_conv_wgrad(const float* A, const float* dOut, float* workspace, long long workspace_floats, int M, int N,
                     const int* geom_host, int KH, int KW, int Cvalid, float* dW, float* db, int accumulate, void* stream);
+/* Split-operand (bf16x3) forms: x = hi + lo, hi = bf16(x), lo = bf16(x - hi); every k-step issues lo*hi + hi*lo + hi*hi on the bf16 matrix
+ * cores into float32 accumulators (float32-grade products).  Activations / gradients are float32 in memory and split while staged.
+ * nele_weight_prep_frag16x3: the hi and the lo fragment streams of Wg (each nele_weight_frag16_elems(N, seglen, KH) bf16 elements, the
+ * layout of nele_weight_prep_frag16); _batch: ptrs [3*jobs] = (Wg, Whi, Wlo), dims [4*jobs] = (N, Ktot, seglen, KH), jobs <= 16.
+ * nele_conv_span_bf16x3: nele_conv_span_bf16's contract with Whi / Wlo; the Conv1d strip kernel (KH = 1) or the 2-D tile kernel, rows
+ * Wout >= 32 (nele_conv_span_bf16x3_supported; NELE_ERR_UNSUPPORTED otherwise).  nele_conv_wgrad_bf16x3: nele_conv_wgrad_bf16's contract;
+ * layers its split tile kernel declines (nele_conv_wgrad_bf16x3_supported == 0) run on the float32 kernel. */
+int nele_weight_prep_frag16x3(const float* Wg, int N, int Ktot, int seglen, int KH, void* Whi, void* Wlo, void* stream);
+int nele_weight_prep_frag16x3_batch(const void* const* ptrs_host, const int* dims_host, int jobs, void* stream);
+int nele_conv_span_bf16x3_supported(int M, int N, const int* geom_host, int KH, int KW);
+int nele_conv_span_bf16x3(const float* A, const void* Whi, const void* Wlo, const float* bias, const float* aux, float* out, int M, int N,
+                          int epi, float slope, const int* geom_host, int KH, int KW, long long a_elems, void* stream);
+int nele_conv_wgrad_bf16x3_supported(int M, int N, const int* geom_host, int KH, int KW);
+int nele_conv_wgrad_bf16x3(const float* A, const float* dOut, float* workspace, long long workspace_floats, int M, int N,
+                           const int* geom_host, int KH, int KW, int Cvalid, float* dW, float* db, int accumulate, void* stream);
 /* The pooling gradient of D's last conv layer (autograd of model.py:124-126) stored as bf16: its two consumers - the layer's data and
  * weight gradients - round their operands to bf16 anyway, and the data gradient re-stages it once per kernel row.  Same layouts and zero
  * border as the float32 buffer; only for geometries that run on the span kernel / the 2-D weight-gradient tile kernel

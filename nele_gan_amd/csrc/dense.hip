@@ -307,6 +307,27 @@ __global__ void weight_frag_kernel(const float* __restrict__ Wg, int N, int Ktot
     }
 }
 
+// Split of 8 float32 values into hi = bf16(x) and lo = bf16(x - float(hi)) (bf16x3 mode): x - hi is exact in float32, so
+// hi + lo carries 16 significand bits and hi*hi + hi*lo + lo*hi misses only the lo*lo term (~2^-16 relative).
+__device__ __forceinline__ void split_bf16x8(const float4& a, const float4& c, bf16x8& hi, bf16x8& lo) {
+    const float x[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const __bf16 h = (__bf16)x[q];
+        hi[q] = h;
+        lo[q] = (__bf16)(x[q] - (float)h);
+    }
+}
+__device__ __forceinline__ void split_bf16x4(const float4& a, bf16x4& hi, bf16x4& lo) {
+    const float x[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const __bf16 h = (__bf16)x[q];
+        hi[q] = h;
+        lo[q] = (__bf16)(x[q] - (float)h);
+    }
+}
+
 // ------------------------------------------------------------------------------------------ span-staged conv, bf16 operands
 // Same structure as conv_span_kernel with bf16 operands and float32 accumulation (v_mfma_f32_16x16x32_bf16): the input
 // span is converted to bf16 while it is staged in LDS; a lane's A fragment is 8 consecutive channels (one ds_read_b128),
@@ -757,6 +778,208 @@ __global__ __launch_bounds__(256) void conv_tile16_kernel(Tile16Args p) {
 #endif
 }
 
+// Split-operand form of conv_tile16_kernel (bf16x3 mode): the halo is staged twice (hi = bf16(x), lo = bf16(x - hi)), each weight chunk
+// carries the hi and the lo fragments (p.Wfrag, wlo: the same layout), and every k-step issues lo*hi, hi*lo, then hi*hi.  Twice the halo
+// bytes of the bf16 kernel: tile heights 4 and 2, weight chunks of at most TILE16_SBMAX_X3 steps (tile16x3_lds).
+#define TILE16_SBMAX_X3 4
+template <int TN, int TH>
+__global__ __launch_bounds__(256) void conv_tile16x3_kernel(Tile16Args p, const __bf16* wlo) {
+    extern __shared__ __attribute__((aligned(16))) __bf16 halo[];    // hi [TH+KH-1][RS] + 64, lo [TH+KH-1][RS] + 64, weight chunk hi [SB][TN][64][8], lo
+    const ConvGeom& g = p.g;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
+    int wo0, ho0, b;
+    {
+        const int ntw = (g_wout(p) + TILE16_TW - 1) / TILE16_TW, nth = (g_hout(p) + TH - 1) / TH;
+        const int per = (int)((gridDim.x + 7) >> 3);
+        const int tile = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
+        if (tile >= p.ntiles) return;
+        const int tw_i = tile % ntw, rem = tile / ntw;
+        wo0 = tw_i * TILE16_TW; ho0 = (rem % nth) * TH; b = rem / nth;
+    }
+    const int wcols = TILE16_TW + p.KW - 1;
+    const int RS = wcols * g.C;
+    const int nrows = TH + p.KH - 1;
+    const int hi0 = ho0 + g.ih0, wi0 = wo0 + g.iw0;
+    const int vcols = max(0, min(wcols, g.W - wi0));
+    const float* abase = p.A + (((size_t)b * g.H + hi0) * g.W + wi0) * g.C;
+    const int HL = nrows * RS + 64;                    // elements of one halo image
+    __bf16* halo_lo = halo + HL;
+    const int SB = p.SB, cps = p.steps_per_seg / SB, nchunk = p.KH * cps;
+    const int cfrag = SB * TN * 64;
+    __bf16* wbuf = halo + 2 * HL;
+    __bf16* wbuf_lo = wbuf + ((cfrag + 255) >> 8) * 2048;   // (the stores below fill whole groups of 256 fragments)
+
+    auto stage_row = [&](int r) {
+        const bool rin = hi0 + r < g.H;
+        const float* src = abase + (size_t)r * g.W * g.C;
+        const int nval = rin ? vcols * g.C : 0;
+        for (int e = tid * 8; e < RS; e += 2048) {
+            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+            float4 a = z, c = z;
+            if (e < nval) { a = *reinterpret_cast<const float4*>(src + e); c = *reinterpret_cast<const float4*>(src + e + 4); }
+            bf16x8 vh, vl;
+            split_bf16x8(a, c, vh, vl);
+            *reinterpret_cast<bf16x8*>(halo + r * RS + e) = vh;
+            *reinterpret_cast<bf16x8*>(halo_lo + r * RS + e) = vl;
+        }
+    };
+    for (int r = 0; r < TH; ++r) stage_row(r);
+    if (tid < 64)
+        for (int r = TH; r <= nrows; ++r) { halo[r * RS + tid] = (__bf16)0.f; halo_lo[r * RS + tid] = (__bf16)0.f; }
+
+    constexpr int NBR = (TILE16_SBMAX_X3 * TN + 3) / 4;
+    bf16x8 breg[NBR], bregl[NBR];
+    const int nq = (cfrag + 255) >> 8;
+    const bf16x8* wp = reinterpret_cast<const bf16x8*>(p.Wfrag) + tid;
+    const bf16x8* wpl = reinterpret_cast<const bf16x8*>(wlo) + tid;
+    auto wload = [&]() {
+#pragma unroll
+        for (int q = 0; q < NBR; ++q)
+            if (q < nq) { breg[q] = wp[256 * q]; bregl[q] = wpl[256 * q]; }
+        wp += cfrag; wpl += cfrag;
+    };
+    auto wstore = [&]() {
+#pragma unroll
+        for (int q = 0; q < NBR; ++q)
+            if (q < nq) { reinterpret_cast<bf16x8*>(wbuf)[tid + 256 * q] = breg[q]; reinterpret_cast<bf16x8*>(wbuf_lo)[tid + 256 * q] = bregl[q]; }
+    };
+    wload();
+    wstore();
+
+    int pb[TH];
+    unsigned valid = 0;
+#pragma unroll
+    for (int i = 0; i < TH; ++i) {
+        const int c = (wave - i) & 3;
+        pb[i] = i * RS + (16 * c + li) * g.C + 8 * lg;
+        if (ho0 + i < g.Hout && wo0 + 16 * c < g.Wout) valid |= 1u << i;
+    }
+    f32x4 acc[TH][TN];
+#pragma unroll
+    for (int i = 0; i < TH; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    __syncthreads();
+
+    float4 r0a, r0c, r1a, r1c;
+    r0a = r0c = r1a = r1c = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int e0 = tid * 8, e1 = tid * 8 + 2048;
+    int rnval = 0;
+    const bf16x8* wl = reinterpret_cast<const bf16x8*>(wbuf) + lane;
+    const bf16x8* wll = reinterpret_cast<const bf16x8*>(wbuf_lo) + lane;
+    for (int c = 0; c < nchunk; ++c) {
+        const int kh = c / cps, s0 = (c - kh * cps) * SB;
+        const bool seg_first = (s0 == 0), seg_last = (s0 + SB == p.steps_per_seg);
+        if (c + 1 < nchunk) wload();
+        if (seg_first && kh + 1 < p.KH) {              // issue the loads of halo row TH + kh
+            const int r = TH + kh;
+            const bool rin = hi0 + r < g.H;
+            const float* src = rin ? abase + (size_t)r * g.W * g.C : abase;
+            const int nval = rin ? vcols * g.C : 0;
+            const int emax = max(vcols * g.C - 8, 0);
+            const float* s0p = src + min(e0, emax);
+            const float* s1p = src + min(e1, emax);
+            r0a = *reinterpret_cast<const float4*>(s0p); r0c = *reinterpret_cast<const float4*>(s0p + 4);
+            r1a = *reinterpret_cast<const float4*>(s1p); r1c = *reinterpret_cast<const float4*>(s1p + 4);
+            rnval = nval;
+        }
+        const int hoff = kh * RS + s0 * 32;
+        auto ldfrag = [&](int u, bf16x8 (&af)[TH], bf16x8 (&bfr)[TN], bf16x8 (&afl)[TH], bf16x8 (&bfl)[TN]) {
+#pragma unroll
+            for (int j = 0; j < TN; ++j) { bfr[j] = wl[(u * TN + j) * 64]; bfl[j] = wll[(u * TN + j) * 64]; }
+#pragma unroll
+            for (int i = 0; i < TH; ++i) {
+                af[i] = *reinterpret_cast<const bf16x8*>(halo + hoff + pb[i] + u * 32);
+                afl[i] = *reinterpret_cast<const bf16x8*>(halo_lo + hoff + pb[i] + u * 32);
+            }
+        };
+        auto mm = [&](const bf16x8 (&af)[TH], const bf16x8 (&bfr)[TN], const bf16x8 (&afl)[TH], const bf16x8 (&bfl)[TN]) {
+#pragma unroll
+            for (int i = 0; i < TH; ++i) {
+                if (valid & (1u << i)) {
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) {             // the small terms first, then hi*hi
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afl[i], bfr[j], acc[i][j], 0, 0, 0);
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfl[j], acc[i][j], 0, 0, 0);
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+                    }
+                }
+            }
+        };
+        bf16x8 a0[TH], b0[TN], a1[TH], b1[TN], a0l[TH], b0l[TN], a1l[TH], b1l[TN];
+        ldfrag(0, a0, b0, a0l, b0l);
+        int u = 0;
+        for (; u + 1 < SB; u += 2) {                   // fragments double buffered in registers: step u + 1 is read under step u's MFMAs
+            ldfrag(u + 1, a1, b1, a1l, b1l);
+            mm(a0, b0, a0l, b0l);
+            ldfrag(min(u + 2, SB - 1), a0, b0, a0l, b0l);
+            mm(a1, b1, a1l, b1l);
+        }
+        if (u < SB) mm(a0, b0, a0l, b0l);
+        if (c + 1 < nchunk) {
+            __syncthreads();                           // every wave is done with this weight chunk
+            wstore();
+            if (seg_last && kh + 1 < p.KH) {           // publish halo row TH + kh for the next kernel row
+                const int off = (TH + kh) * RS;
+                const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (!(e0 < rnval)) { r0a = z; r0c = z; }
+                if (!(e1 < rnval)) { r1a = z; r1c = z; }
+                if (e0 < RS) {
+                    bf16x8 vh, vl;
+                    split_bf16x8(r0a, r0c, vh, vl);
+                    *reinterpret_cast<bf16x8*>(halo + off + e0) = vh;
+                    *reinterpret_cast<bf16x8*>(halo_lo + off + e0) = vl;
+                }
+                if (e1 < RS) {
+                    bf16x8 vh, vl;
+                    split_bf16x8(r1a, r1c, vh, vl);
+                    *reinterpret_cast<bf16x8*>(halo + off + e1) = vh;
+                    *reinterpret_cast<bf16x8*>(halo_lo + off + e1) = vl;
+                }
+            }
+            __syncthreads();
+        }
+    }
+
+    // ---- epilogue: as conv_tile16_kernel (each wave transposes its position tiles through 4 KB of the dead halo)
+    __syncthreads();
+    float* ep = reinterpret_cast<float*>(halo) + wave * (16 * 68);
+    constexpr int NQ = TN * 4;
+#pragma unroll
+    for (int i = 0; i < TH; ++i) {
+        if (!(valid & (1u << i))) continue;
+        const int c = (wave - i) & 3;
+        const int ho = ho0 + i;
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) ep[(4 * lg + reg) * 68 + 16 * j + li] = acc[i][j][reg];
+#pragma unroll
+        for (int q = 0; q < TN; ++q) {
+            const int idx = q * 64 + lane, pr = idx / NQ, cq = idx - pr * NQ;
+            const int wo = wo0 + 16 * c + pr, n = 4 * cq;
+            if (wo < g.Wout && n < p.N) {
+                float4 v = *reinterpret_cast<const float4*>(&ep[pr * 68 + n]);
+                const size_t o_off = (((size_t)b * g.OH + ho + g.oh0) * g.OW + wo + g.ow0) * g.OC + n;
+                if (p.epi == EPI_BIAS || p.epi == EPI_BIAS_LRELU || p.epi == EPI_BIAS_EXPTANH) {
+                    v.x += p.bias[n]; v.y += p.bias[n + 1]; v.z += p.bias[n + 2]; v.w += p.bias[n + 3];
+                }
+                if (p.epi == EPI_BIAS_LRELU) {
+                    v.x = v.x > 0.f ? v.x : p.slope * v.x; v.y = v.y > 0.f ? v.y : p.slope * v.y;
+                    v.z = v.z > 0.f ? v.z : p.slope * v.z; v.w = v.w > 0.f ? v.w : p.slope * v.w;
+                } else if (p.epi == EPI_MASK_LRELU_GRAD) {
+                    const float4 x = *reinterpret_cast<const float4*>(p.aux + (((size_t)b * g.Hout + ho) * g.Wout + wo) * g.OC + n);
+                    v.x = x.x > 0.f ? v.x : p.slope * v.x; v.y = x.y > 0.f ? v.y : p.slope * v.y;
+                    v.z = x.z > 0.f ? v.z : p.slope * v.z; v.w = x.w > 0.f ? v.w : p.slope * v.w;
+                } else if (p.epi == EPI_BIAS_EXPTANH) {
+                    v.x = expf(3.2f * tanhf(v.x)); v.y = expf(3.2f * tanhf(v.y)); v.z = expf(3.2f * tanhf(v.z)); v.w = expf(3.2f * tanhf(v.w));
+                }
+                *reinterpret_cast<float4*>(p.out + o_off) = v;
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------ Conv1d / Linear tile kernel, bf16
 // The generator's causal Conv1d layers (and any KH = 1 conv): M = B*T is small (8032 rows at B = 32), K = k*C is long (up to
 // 1792) and N up to 256, so the generic GEMM ran 504 tiny workgroups with a barrier every 32 k-values (46 us per layer).  Here a
@@ -999,6 +1222,233 @@ __global__ __launch_bounds__(256) void conv1d_tile16_kernel(Tile16Args p) {
 #ifdef C1_PROF
     if (tid == 0) { for (int q_ = 0; q_ < 5; ++q_) atomicAdd(&c1_prof[q_], c1_acc[q_]); atomicAdd(&c1_prof[5], 1ull); }
 #endif
+}
+
+// Split-operand form of conv1d_tile16_kernel (bf16x3 mode): the strip is staged twice, hi = bf16(x) and lo = bf16(x - hi), the weight
+// chunks carry a hi and a lo fragment stream (p.Wfrag, wlo: the same layout), and every k-step issues lo*hi, hi*lo, then hi*hi into the
+// float32 accumulators.  Twice the strip and weight bytes of the bf16 kernel: weight chunks of at most C1D_SBMAX_X3 steps, no N-chunk walk.
+#define C1D_SBMAX_X3 5
+template <int TN>
+__global__ __launch_bounds__(256) void conv1d_tile16x3_kernel(Tile16Args p, const __bf16* wlo) {
+    extern __shared__ __attribute__((aligned(16))) __bf16 halo[];    // hi [RS] + 64 slack, lo [RS] + 64, then two weight slots (hi, lo chunks)
+    const ConvGeom& g = p.g;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
+    // 1-D grid, XCD-aware: the N-chunk workgroups of one input strip (they stage the same strip) get ids of one XCD
+    int wo0, nb, bz;
+    {
+        const int nchN = p.ntiles;                        // N chunks per strip (host)
+        const int gx = (g.Wout + C1D_TW - 1) / C1D_TW;
+        const int w = (int)blockIdx.x, slot = w >> 3;
+        const int strip = (slot / nchN) * 8 + (w & 7);
+        nb = slot % nchN;
+        if (strip >= gx * p.SBH) return;
+        wo0 = (strip % gx) * C1D_TW; bz = strip / gx;
+    }
+    const int b = bz / g.Hout, ho = bz - b * g.Hout;
+    const int wcols = C1D_TW + p.KW - 1;
+    const int CP = g.C + (((g.C & (g.C - 1)) == 0) ? C1D_PAD(g.C) : 0);   // position stride in LDS (see C1D_PAD; padded only for powers of two)
+    const int lgC = (CP == g.C) ? 30 : __ffs(g.C) - 1;
+    const int RS = wcols * CP;
+    const int wi0 = wo0 + g.iw0;
+    const int vcols = max(0, min(wcols, g.W - wi0));
+    const float* src = p.A + (((size_t)b * g.H + ho + g.ih0) * g.W + wi0) * g.C;
+    __bf16* wbuf = halo + 2 * (RS + 64);
+    __bf16* halo_lo = halo + RS + 64;
+    const int SB = p.SB, nchunk = p.steps_per_seg / SB;
+    const int cfrag = SB * TN * 64;
+    {   // stage the input strip (float32 -> bf16), zero beyond the input
+        // groups of six 32-byte pieces per thread with all their loads in flight together: a load - convert - store loop paid a memory
+        // latency per piece (17 pieces for a 256-channel strip: 16 k of the workgroup's 92 k clocks)
+        const int nval = vcols * g.C, ntot = wcols * g.C;
+        constexpr int SG = 6;
+        for (int e0 = tid * 8; e0 < ntot; e0 += 2048 * SG) {
+            float4 ra[SG], rc[SG];
+            const int emax = max(nval - 8, 0);                  // (unconditional loads from clamped addresses: a test around a load makes the compiler wait for it at once)
+#pragma unroll
+            for (int q = 0; q < SG; ++q) {
+                const int e = min(e0 + 2048 * q, emax);
+                ra[q] = *reinterpret_cast<const float4*>(src + e); rc[q] = *reinterpret_cast<const float4*>(src + e + 4);
+            }
+#pragma unroll
+            for (int q = 0; q < SG; ++q) {
+                const int e = e0 + 2048 * q;
+                if (e >= ntot) continue;
+                bf16x8 v;
+                bf16x8 vl;
+                const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+                split_bf16x8(e < nval ? ra[q] : z, e < nval ? rc[q] : z, v, vl);
+                const int px = (CP == g.C) ? 0 : e / g.C;
+                *reinterpret_cast<bf16x8*>(halo + e + px * (CP - g.C)) = v;
+                *reinterpret_cast<bf16x8*>(halo_lo + e + px * (CP - g.C)) = vl;
+            }
+        }
+        if (tid < 64) halo[RS + tid] = (__bf16)0.f;
+        if (tid < 64) halo_lo[RS + tid] = (__bf16)0.f;
+    }
+    // weight chunk c: steps [c SB, (c+1) SB) x this workgroup's TN n-tiles (stride NT tiles per step in the fragment stream)
+    // Weight chunks travel global -> registers -> LDS TWO chunks ahead (two register sets, two LDS slots): with one wave per SIMD and one
+    // workgroup per CU nothing else covers a memory latency, and a chunk's MFMAs (SB x 2 x TN x 16 cycles) are shorter than one - fetched
+    // one chunk ahead through one slot, every chunk ended in a wait for its successor and two barriers (122 us per layer at B = 256 for
+    // 16 us of MFMA issue).  Chunk c + 2 is requested at the top of chunk c, chunk c + 1 is written to the other slot after chunk c's MFMAs,
+    // ONE barrier per chunk.
+    constexpr int NBR = (C1D_SBMAX_X3 * TN + 3) / 4;
+    bf16x8 bregA[NBR], bregB[NBR], bregAl[NBR], bregBl[NBR];
+    const int nq = (cfrag + 255) >> 8;
+    const int wsl = (cfrag * 8 + 2047) & ~2047;           // elements per LDS weight slot (a slot: the hi chunk, then the lo chunk)
+    const int wslot = 2 * wsl;
+    const bf16x8* wsrc = nullptr;
+    const bf16x8* wsrc_lo = nullptr;
+    int woff[NBR];                                       // fragment offsets inside a chunk: the same for every chunk
+#pragma unroll
+    for (int q = 0; q < NBR; ++q) {
+        const int f = min(tid + 256 * q, cfrag - 1), u = f / (TN * 64), r = f - u * (TN * 64);
+        woff[q] = u * p.NT * 64 + r;
+    }
+    auto wload = [&](int c, bf16x8 (&breg)[NBR], bf16x8 (&bregl)[NBR]) {
+        const bf16x8* wc = wsrc + (size_t)c * SB * p.NT * 64;
+#pragma unroll
+        for (int q = 0; q < NBR; ++q)
+            if (q < nq) breg[q] = wc[woff[q]];
+        {
+            const bf16x8* wcl = wsrc_lo + (size_t)c * SB * p.NT * 64;
+#pragma unroll
+            for (int q = 0; q < NBR; ++q)
+                if (q < nq) bregl[q] = wcl[woff[q]];
+        }
+    };
+    auto wstore = [&](int slot, const bf16x8 (&breg)[NBR], const bf16x8 (&bregl)[NBR]) {
+#pragma unroll
+        for (int q = 0; q < NBR; ++q)
+            if (q < nq) reinterpret_cast<bf16x8*>(wbuf + slot * wslot)[tid + 256 * q] = breg[q];
+        {
+#pragma unroll
+            for (int q = 0; q < NBR; ++q)
+                if (q < nq) reinterpret_cast<bf16x8*>(wbuf + slot * wslot + wsl)[tid + 256 * q] = bregl[q];
+        }
+    };
+    // this wave's two position tiles: columns 16 (wave + 4 t)
+    int pb[2];
+    unsigned valid = 0;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int c = wave + 4 * t;
+        pb[t] = (16 * c + li) * CP + 8 * lg;
+        if (wo0 + 16 * c < g.Wout) valid |= 1u << t;
+    }
+    // Large batches (every CU has strips of its own): ONE workgroup per strip walks all N / 64 output-channel chunks over the strip it
+    // staged instead of four workgroups staging the same strip (128 + k - 1 input positions x C channels, converted to bf16).  The
+    // epilogue then transposes through its own LDS scratch (behind the weight chunk), not through the strip.
+    const int nb_end = nb + p.ncl;
+    float* epbase = (p.ncl > 1) ? reinterpret_cast<float*>(wbuf + 2 * wslot) : reinterpret_cast<float*>(halo);
+    wsrc = reinterpret_cast<const bf16x8*>(p.Wfrag) + (size_t)nb * 4 * 64;
+    wsrc_lo = reinterpret_cast<const bf16x8*>(wlo) + (size_t)nb * 4 * 64;
+    wload(0, bregA, bregAl);                              // (the first two chunks of every later N chunk are requested under the epilogue before it)
+    if (nchunk > 1) wload(1, bregB, bregBl);
+    for (; nb < nb_end; ++nb) {
+    wstore(0, bregA, bregAl);
+    f32x4 acc[2][TN];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    __syncthreads();
+    auto chunk = [&](int c, bf16x8 (&bcur)[NBR], bf16x8 (&bnext)[NBR], bf16x8 (&bcurl)[NBR], bf16x8 (&bnextl)[NBR]) {   // bcur held chunk c (already in LDS), bnext holds chunk c + 1
+        const bf16x8* wl = reinterpret_cast<const bf16x8*>(wbuf + (c & 1) * wslot) + lane;
+        const bf16x8* wll = reinterpret_cast<const bf16x8*>(wbuf + (c & 1) * wslot + wsl) + lane;
+        if (c + 2 < nchunk) wload(c + 2, bcur, bcurl);
+        const __bf16* hk = halo;
+        const int ug0 = c * SB;                            // k-step ug: elements [32 ug, 32 ug + 32) of the im2col row
+        // fragments double buffered in registers: the ds_reads of step u + 1 are issued before the MFMAs of step u (one wave per SIMD and
+        // one workgroup per CU here: nothing else hides an LDS round trip per k-step)
+        auto ldfrag = [&](int u, bf16x8 (&af)[2], bf16x8 (&bfr)[TN], bf16x8 (&afl)[2], bf16x8 (&bfrl)[TN]) {
+#pragma unroll
+            for (int j = 0; j < TN; ++j) bfr[j] = wl[(u * TN + j) * 64];
+            const int k0 = (ug0 + u) * 32;
+            const int koff = k0 + (k0 >> lgC) * (CP - g.C);     // = tap * CP + channel offset (C is a power of two whenever CP != C)
+#pragma unroll
+            for (int i = 0; i < 2; ++i) af[i] = *reinterpret_cast<const bf16x8*>(hk + pb[i] + koff);
+#pragma unroll
+            for (int j = 0; j < TN; ++j) bfrl[j] = wll[(u * TN + j) * 64];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) afl[i] = *reinterpret_cast<const bf16x8*>(halo_lo + pb[i] + koff);
+        };
+        auto mm = [&](const bf16x8 (&af)[2], const bf16x8 (&bfr)[TN], const bf16x8 (&afl)[2], const bf16x8 (&bfrl)[TN]) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                if (valid & (1u << i)) {
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) {          // the small terms first, then hi*hi
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afl[i], bfr[j], acc[i][j], 0, 0, 0);
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfrl[j], acc[i][j], 0, 0, 0);
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+                    }
+                }
+            }
+        };
+        bf16x8 a0[2], b0[TN], a1[2], b1[TN], a0l[2], b0l[TN], a1l[2], b1l[TN];
+        ldfrag(0, a0, b0, a0l, b0l);
+        int u = 0;
+        for (; u + 1 < SB; u += 2) {
+            ldfrag(u + 1, a1, b1, a1l, b1l);
+            mm(a0, b0, a0l, b0l);
+            ldfrag(min(u + 2, SB - 1), a0, b0, a0l, b0l);
+            mm(a1, b1, a1l, b1l);
+        }
+        if (u < SB) mm(a0, b0, a0l, b0l);
+        if (c + 1 < nchunk) {
+            wstore((c + 1) & 1, bnext, bnextl);            // its slot was last read in chunk c - 1, behind that chunk's barrier
+            __syncthreads();
+        }
+    };
+    for (int c = 0; c < nchunk; c += 2) {
+        chunk(c, bregA, bregB, bregAl, bregBl);
+        if (c + 1 < nchunk) chunk(c + 1, bregB, bregA, bregBl, bregAl);
+    }
+    // ---- epilogue through LDS (float4 stores along the channels)
+    if (nb + 1 < nb_end) {                                 // every chunk of this N chunk has left the registers: the next one's first two come in now
+        wsrc = reinterpret_cast<const bf16x8*>(p.Wfrag) + (size_t)(nb + 1) * 4 * 64;
+        wsrc_lo = reinterpret_cast<const bf16x8*>(wlo) + (size_t)(nb + 1) * 4 * 64;
+        wload(0, bregA, bregAl);
+        if (nchunk > 1) wload(1, bregB, bregBl);
+    }
+    __syncthreads();
+    float* ep = epbase + wave * (16 * 68);
+    constexpr int NQ = TN * 4;
+    const int n0 = nb * 64;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        if (!(valid & (1u << i))) continue;
+        const int c = wave + 4 * i;
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) ep[(4 * lg + reg) * 68 + 16 * j + li] = acc[i][j][reg];
+#pragma unroll
+        for (int q = 0; q < TN; ++q) {
+            const int idx = q * 64 + lane, pr = idx / NQ, cq = idx - pr * NQ;
+            const int wo = wo0 + 16 * c + pr, n = n0 + 4 * cq;
+            if (wo < g.Wout && n < p.N) {
+                float4 v = *reinterpret_cast<const float4*>(&ep[pr * 68 + 4 * cq]);
+                const size_t o_off = (((size_t)b * g.OH + ho + g.oh0) * g.OW + wo + g.ow0) * g.OC + n;
+                if (p.epi == EPI_BIAS || p.epi == EPI_BIAS_LRELU || p.epi == EPI_BIAS_EXPTANH) {
+                    v.x += p.bias[n]; v.y += p.bias[n + 1]; v.z += p.bias[n + 2]; v.w += p.bias[n + 3];
+                }
+                if (p.epi == EPI_BIAS_LRELU) {
+                    v.x = v.x > 0.f ? v.x : p.slope * v.x; v.y = v.y > 0.f ? v.y : p.slope * v.y;
+                    v.z = v.z > 0.f ? v.z : p.slope * v.z; v.w = v.w > 0.f ? v.w : p.slope * v.w;
+                } else if (p.epi == EPI_MASK_LRELU_GRAD) {
+                    const float4 x = *reinterpret_cast<const float4*>(p.aux + (((size_t)b * g.Hout + ho) * g.Wout + wo) * g.OC + n);
+                    v.x = x.x > 0.f ? v.x : p.slope * v.x; v.y = x.y > 0.f ? v.y : p.slope * v.y;
+                    v.z = x.z > 0.f ? v.z : p.slope * v.z; v.w = x.w > 0.f ? v.w : p.slope * v.w;
+                } else if (p.epi == EPI_BIAS_EXPTANH) {
+                    v.x = expf(3.2f * tanhf(v.x)); v.y = expf(3.2f * tanhf(v.y)); v.z = expf(3.2f * tanhf(v.z)); v.w = expf(3.2f * tanhf(v.w));
+                }
+                *reinterpret_cast<float4*>(p.out + o_off) = v;
+            }
+        }
+    }
+    if (nb + 1 < nb_end) __syncthreads();                  // the next chunk's first weights replace this chunk's last ones
+    }
 }
 
 // Wg [N][Ktot] f32 -> bf16 fragment-major [KH*sps][NT][64][8], sps = ceil(seglen/32); element (ks = kh*sps + s, j, lane, e) =
@@ -1705,6 +2155,192 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tile16_kernel(WgradTileArgs
                 if (kcol[jj] >= 0) part[(size_t)n * p.Kfull + kcol[jj]] = acc[i][jj][reg];
         }
     if (want_bias) {                                      // fold the 16 threads that share an n quad
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < 4; ++q) bred[dp0][4 * dnq + q] = bq[q];
+        __syncthreads();
+        if (tid < 64 && tid < p.N) {
+            float sum = 0.f;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) sum += bred[q][tid];
+            p.bpart[(size_t)grp * Nfull + n0 + tid] = sum;
+        }
+    }
+}
+
+// Split-operand form of conv_wgrad_tile16_kernel for float32 operands (bf16x3 mode): the input rows and the dOut tile are staged as hi and
+// lo images (twice the LDS of the bf16 kernel: one workgroup per CU), and every reduction step issues lo*hi, hi*lo, then hi*hi.  The bias
+// gradient is summed from the float32 dOut values, as in the bf16 kernel.
+template <int NT, int KTW>
+__global__ __launch_bounds__(256, 2) void conv_wgrad_tile16x3_kernel(WgradTileArgs p) {
+    constexpr int WT_NP = WT_NP_OF(NT);
+    extern __shared__ __attribute__((aligned(16))) __bf16 wt_lds[];     // hi: halo rows [WT_TH][RS] + WT_SLACK, dOut tile [256][WT_NP]; then the same for lo
+    __shared__ float bred[16][64];
+    const ConvGeom& g = p.g;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int kh, grp, sub;
+    {
+        const int inner = p.KH * p.subs_n * p.subs_c;
+        int rest;
+        if ((p.G & 7) == 0) {
+            const int w = blockIdx.x, xcd = w & 7, slot = w >> 3;
+            rest = slot % inner;
+            grp = (slot / inner) * 8 + xcd;
+        } else {
+            rest = blockIdx.x % inner;
+            grp = blockIdx.x / inner;
+        }
+        kh = rest % p.KH;
+        sub = rest / p.KH;
+    }
+    const int sn = sub / p.subs_c, sc = sub - sn * p.subs_c;
+    const int n0 = sn * p.N, ic0 = sc * g.C, Nfull = p.N * p.subs_n;
+    const int wcols = WT_TW + p.KW - 1, RS = wcols * g.C;
+    const int IMG = WT_TH * RS + WT_SLACK + 256 * WT_NP;  // elements of one (halo, dOut tile) image
+    __bf16* halo = wt_lds;
+    __bf16* dt = wt_lds + WT_TH * RS + WT_SLACK;
+    __bf16* halo_lo = wt_lds + IMG;
+    __bf16* dt_lo = dt + IMG;
+    const int nkt = (g.seglen + 15) >> 4;
+    f32x4 acc[NT][KTW];
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+#pragma unroll
+        for (int jj = 0; jj < KTW; ++jj) acc[i][jj] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int e = tid; e < WT_SLACK; e += 256) { halo[WT_TH * RS + e] = (__bf16)0.f; halo_lo[WT_TH * RS + e] = (__bf16)0.f; }
+    const int dnq = tid & 15, dp0 = tid >> 4;
+    float bq[4] = {0.f, 0.f, 0.f, 0.f};
+    const bool want_bias = (p.bpart != nullptr) && (kh == 0) && (sc == 0);
+
+    for (int t = grp; t < p.ntiles; t += p.G) {
+        const int tw_i = t % p.ntw, rem = t / p.ntw, th_i = rem % p.nth, b = rem / p.nth;
+        const int ho0 = th_i * WT_TH, wo0 = tw_i * WT_TW;
+        const int wi0 = wo0 + g.iw0;
+        const int vcols = max(0, min(wcols, g.W - wi0));
+        __syncthreads();                                 // previous tile fully consumed
+        {   // ---- input rows ho0 + r + kh, split; zero outside the input (pieces of 8 elements as in the bf16 kernel)
+            int tl = tid;
+            asm volatile("" : "+v"(tl));
+            constexpr int HNF = 9, HB = 3;
+            const int pmax = max(vcols - 1, 0), himax = g.H - 1;
+            const float* src0 = p.A + (((size_t)b * g.H) * g.W + wi0) * p.ics + ic0;
+#pragma unroll
+            for (int it0 = 0; it0 < HNF; it0 += HB) {
+                float4 fa[HB], fc[HB];
+#pragma unroll
+                for (int q = 0; q < HB; ++q) {
+                    const int ef = min(tl * 8 + 2048 * (it0 + q), WT_TH * RS - 8);
+                    const int r = (ef >= RS) + (ef >= 2 * RS) + (ef >= 3 * RS), e = ef - r * RS;
+                    const int pos = e / g.C, within = e - pos * g.C;
+                    const float* sp = src0 + ((size_t)min(ho0 + r + kh + g.ih0, himax) * g.W + min(pos, pmax)) * p.ics + within;
+                    fa[q] = *reinterpret_cast<const float4*>(sp); fc[q] = *reinterpret_cast<const float4*>(sp + 4);
+                }
+#pragma unroll
+                for (int q = 0; q < HB; ++q) {
+                    const int ef = tl * 8 + 2048 * (it0 + q);
+                    if (ef < WT_TH * RS) {
+                        const int r = (ef >= RS) + (ef >= 2 * RS) + (ef >= 3 * RS), e = ef - r * RS;
+                        const bool in = (ho0 + r + kh + g.ih0 < g.H) && (e < vcols * g.C);
+                        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+                        bf16x8 vh, vl;
+                        split_bf16x8(in ? fa[q] : z, in ? fc[q] : z, vh, vl);
+                        *reinterpret_cast<bf16x8*>(halo + ef) = vh;
+                        *reinterpret_cast<bf16x8*>(halo_lo + ef) = vl;
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        {   // ---- dOut tile [256 positions][N] (zero for positions outside the output and n >= N)
+            int tq = tid;
+            asm volatile("" : "+v"(tq));
+            const int dnq = tq & 15, dp0 = tq >> 4;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                float4 rd[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    const int pos = dp0 + 16 * (8 * h + q), r = pos >> 6, c = pos & 63;
+                    const int ho = min(ho0 + r, g.Hout - 1), wo = min(wo0 + c, g.Wout - 1);
+                    const size_t off = (((size_t)b * g.OH + ho + g.oh0) * g.OW + wo + g.ow0) * g.OC + n0 + min(4 * dnq, p.N - 4);
+                    rd[q] = *reinterpret_cast<const float4*>(p.dOut + off);
+                }
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    const int pos = dp0 + 16 * (8 * h + q), r = pos >> 6, c = pos & 63;
+                    const bool ok = (ho0 + r < g.Hout) && (wo0 + c < g.Wout) && (4 * dnq < p.N);
+                    const float4 v4 = ok ? rd[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+                    bf16x4 vh, vl;
+                    split_bf16x4(v4, vh, vl);
+                    if (4 * dnq < WT_NP) {
+                        *reinterpret_cast<bf16x4*>(dt + pos * WT_NP + 4 * dnq) = vh;
+                        *reinterpret_cast<bf16x4*>(dt_lo + pos * WT_NP + 4 * dnq) = vl;
+                    }
+                    if (want_bias) { bq[0] += v4.x; bq[1] += v4.y; bq[2] += v4.z; bq[3] += v4.w; }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        __syncthreads();
+        // ---- 8 reduction steps of 32 positions; the fragments of step ks + 1 are read during step ks
+        auto lda = [&](int ks, bf16x8 (&af)[NT], bf16x8 (&afl)[NT]) {
+#pragma unroll
+            for (int i = 0; i < NT; ++i) {
+                af[i] = tr_frag(dt + (ks * 32) * WT_NP, WT_NP, 16 * i, lane);
+                afl[i] = tr_frag(dt_lo + (ks * 32) * WT_NP, WT_NP, 16 * i, lane);
+            }
+        };
+        auto ldb = [&](int ks, int jj, bf16x8& bh, bf16x8& bl) {
+            const int o = (ks >> 1) * RS + (ks & 1) * 32 * g.C, col = 16 * min(wave + 4 * jj, nkt - 1);
+            bh = tr_frag(halo + o, g.C, col, lane);
+            bl = tr_frag(halo_lo + o, g.C, col, lane);
+        };
+        {
+            bf16x8 ac[NT], acl[NT], an[NT], anl[NT];
+            lda(0, ac, acl);
+#pragma unroll 1
+            for (int ks = 0; ks < WT_TH * 2; ++ks) {
+                if (ks + 1 < WT_TH * 2) lda(ks + 1, an, anl);
+#pragma unroll
+                for (int jj = 0; jj < KTW; ++jj) {
+                    bf16x8 bh, bl;
+                    ldb(ks, jj, bh, bl);
+#pragma unroll
+                    for (int i = 0; i < NT; ++i) {       // the small terms first, then hi*hi
+                        acc[i][jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(acl[i], bh, acc[i][jj], 0, 0, 0);
+                        acc[i][jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ac[i], bl, acc[i][jj], 0, 0, 0);
+                        acc[i][jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ac[i], bh, acc[i][jj], 0, 0, 0);
+                    }
+                }
+                if (ks + 1 < WT_TH * 2) {
+#pragma unroll
+                    for (int i = 0; i < NT; ++i) { ac[i] = an[i]; acl[i] = anl[i]; }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    }
+    // ---- partials, as conv_wgrad_tile16_kernel
+    const int li = lane & 15, lg = lane >> 4;
+    float* part = p.part + (size_t)grp * Nfull * p.Kfull + (size_t)n0 * p.Kfull + (size_t)kh * p.KW * p.ics + ic0;
+    int kcol[KTW];
+#pragma unroll
+    for (int jj = 0; jj < KTW; ++jj) {
+        const int kk = 16 * (wave + 4 * jj) + li, kw = kk / g.C;
+        kcol[jj] = (wave + 4 * jj < nkt && kk < g.seglen) ? kw * p.ics + (kk - kw * g.C) : -1;
+    }
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const int n = 16 * i + 4 * lg + reg;
+            if (n >= p.N) continue;
+#pragma unroll
+            for (int jj = 0; jj < KTW; ++jj)
+                if (kcol[jj] >= 0) part[(size_t)n * p.Kfull + kcol[jj]] = acc[i][jj][reg];
+        }
+    if (want_bias) {
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < 4; ++q) bred[dp0][4 * dnq + q] = bq[q];
@@ -2744,5 +3380,262 @@ extern "C" int nele_weight_prep(const float* Wt, const float* sigma, int N, int 
     hipLaunchKernelGGL(weight_prep_kernel, dim3(min(1024, (total + 255) / 256)), dim3(256), 0, as_stream(stream), Wt, sigma, N, Cvalid, C,
                        KH, KW, Wf, Wb);
     NELE_CHECK_LAUNCH("nele_weight_prep");
+    return NELE_OK;
+}
+
+// ================================================================================ bf16x3: split-operand products on the bf16 matrix cores
+// x = hi + lo with hi = bf16(x), lo = bf16(x - hi); a product a*b is taken as lo_a*hi_b + hi_a*lo_b + hi_a*hi_b (three
+// v_mfma_f32_16x16x32_bf16 per k-step, float32 accumulation): float32-grade results at 3/16 of the f32 MFMA's cycles.  Activations stay
+// float32 in memory and are split while they are staged; the weights arrive as a hi and a lo fragment stream of the bf16 layout.
+// Geometries the split kernels decline are an error here (nele_conv_span_bf16x3_supported); the plans run them on the float32 kernels.
+struct Frag16x3Jobs { const float* Wg[WB_MAXJ]; __bf16* Whi[WB_MAXJ]; __bf16* Wlo[WB_MAXJ]; int N[WB_MAXJ], Ktot[WB_MAXJ], seglen[WB_MAXJ], KH[WB_MAXJ]; };
+__global__ void weight_frag16x3_batch_kernel(Frag16x3Jobs J) {
+    const int q = blockIdx.y;
+    const float* __restrict__ Wg = J.Wg[q];
+    const int N = J.N[q], Ktot = J.Ktot[q], seglen = J.seglen[q], KH = J.KH[q];
+    const int NT = (N + 15) / 16, sps = (seglen + 31) / 32;
+    const int total = KH * sps * NT * 64 * 8;
+    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
+        const int e = idx & 7, lane = (idx >> 3) & 63, t = idx >> 9, j = t % NT, ks = t / NT;
+        const int kh = ks / sps, s_ = ks - kh * sps;
+        const int n = j * 16 + (lane & 15), kin = s_ * 32 + 8 * (lane >> 4) + e;
+        float v = 0.f;
+        if (n < N && kin < seglen) v = Wg[(size_t)n * Ktot + (size_t)kh * seglen + kin];
+        const __bf16 h = (__bf16)v;
+        J.Whi[q][idx] = h;
+        J.Wlo[q][idx] = (__bf16)(v - (float)h);
+    }
+}
+
+// ptrs_host [3 * jobs] = (Wg [N][Ktot] f32, Whi, Wlo), dims_host [4 * jobs] = (N, Ktot, seglen, KH): nele_weight_prep_frag16x3 per job
+extern "C" int nele_weight_prep_frag16x3_batch(const void* const* ptrs_host, const int* dims_host, int jobs, void* stream) {
+    NELE_CHECK_ARG(ptrs_host && dims_host && jobs >= 1 && jobs <= WB_MAXJ, "nele_weight_prep_frag16x3_batch: bad arguments (jobs <= 16)");
+    Frag16x3Jobs J;
+    long long maxtotal = 1;
+    for (int q = 0; q < jobs; ++q) {
+        J.Wg[q] = (const float*)ptrs_host[3 * q]; J.Whi[q] = (__bf16*)ptrs_host[3 * q + 1]; J.Wlo[q] = (__bf16*)ptrs_host[3 * q + 2];
+        J.N[q] = dims_host[4 * q]; J.Ktot[q] = dims_host[4 * q + 1]; J.seglen[q] = dims_host[4 * q + 2]; J.KH[q] = dims_host[4 * q + 3];
+        NELE_CHECK_ARG(J.Wg[q] && J.Whi[q] && J.Wlo[q] && J.N[q] > 0 && J.KH[q] > 0 && J.seglen[q] > 0 && J.KH[q] * J.seglen[q] == J.Ktot[q],
+                       "nele_weight_prep_frag16x3_batch: job %d invalid", q);
+        const long long total = nele_weight_frag16_elems(J.N[q], J.seglen[q], J.KH[q]) - 2048;
+        if (total > maxtotal) maxtotal = total;
+    }
+    hipLaunchKernelGGL(weight_frag16x3_batch_kernel, dim3((unsigned)min(512LL, (maxtotal + 255) / 256), jobs), dim3(256), 0, as_stream(stream), J);
+    NELE_CHECK_LAUNCH("nele_weight_prep_frag16x3_batch");
+    return NELE_OK;
+}
+
+// hi and lo fragment streams of Wg, each nele_weight_frag16_elems(N, seglen, KH) bf16 elements in the layout of nele_weight_prep_frag16
+extern "C" int nele_weight_prep_frag16x3(const float* Wg, int N, int Ktot, int seglen, int KH, void* Whi, void* Wlo, void* stream) {
+    NELE_CHECK_ARG(Wg && Whi && Wlo && N > 0 && KH > 0 && seglen > 0 && KH * seglen == Ktot, "nele_weight_prep_frag16x3: bad arguments");
+    const void* ptrs[3] = {Wg, Whi, Wlo};
+    const int dims[4] = {N, Ktot, seglen, KH};
+    return nele_weight_prep_frag16x3_batch(ptrs, dims, 1, stream);
+}
+
+// LDS budgets of the split kernels (160 KB per CU, 158 KB usable as in the bf16 selectors).  Both stage twice the bf16 kernels' bytes, so
+// they get their own, smaller choices: 2-D tiles of 4 or 2 rows with weight chunks of at most TILE16_SBMAX_X3 steps; Conv1d strips with
+// chunks of at most C1D_SBMAX_X3 steps and one workgroup per (strip, 64-channel chunk).
+static int tile16x3_sb(const ConvGeom& g) {
+    const int sps = (g.seglen + 31) / 32;
+    int SB = 1;
+    for (int d = 1; d <= TILE16_SBMAX_X3; ++d)
+        if (sps % d == 0) SB = d;
+    return SB;
+}
+static size_t tile16x3_lds(const ConvGeom& g, int N, int KH, int KW, int TH) {
+    if (N > 64 || N % 4 || g.OC % 4 || g.C % 8 || KH * g.seglen != g.Ktot || KW * g.C != g.seglen) return 0;
+    const long long RS = (long long)(TILE16_TW + KW - 1) * g.C;
+    if (RS > 4096) return 0;
+    const int NT = (N + 15) / 16;
+    const long long bytes = 2 * ((long long)(TH + KH - 1) * RS + 64) * 2 + 2 * (((long long)tile16x3_sb(g) * NT * 1024 + 4095) & ~4095LL);
+    if (bytes > 158 * 1024) return 0;
+    return (size_t)(bytes < 4 * 16 * 68 * 4 ? 4 * 16 * 68 * 4 : bytes);
+}
+static int tile16x3_th(const ConvGeom& g, int N, int KH, int KW) {
+    if (tile16x3_lds(g, N, KH, KW, 4)) return 4;
+    if (tile16x3_lds(g, N, KH, KW, 2)) return 2;
+    return 0;
+}
+static int conv1d16x3_sb(const ConvGeom& g, int N, int KH, int KW, size_t* lds_out) {
+    if (KH != 1 || N % 4 || g.OC % 4 || g.C % 8 || KW * g.C != g.seglen || g.seglen != g.Ktot || g.seglen % 32) return 0;
+    if (N > 64 && N % 64) return 0;
+    const long long RS = (long long)(C1D_TW + KW - 1) * (g.C + (((g.C & (g.C - 1)) == 0) ? C1D_PAD(g.C) : 0));
+    const int sps = g.seglen / 32, TNsel = (N >= 64) ? 4 : (N + 15) / 16;
+    for (int d = C1D_SBMAX_X3; d >= 1; --d) {
+        if (sps % d) continue;
+        const long long bytes = 2 * (RS + 64) * 2 + 4 * (((long long)d * TNsel * 1024 + 4095) & ~4095LL);    // hi + lo strip, two (hi, lo) weight slots
+        if (bytes <= 158 * 1024) {
+            if (lds_out) *lds_out = (size_t)(bytes < 4 * 16 * 68 * 4 ? 4 * 16 * 68 * 4 : bytes);
+            return d;
+        }
+    }
+    return 0;
+}
+extern "C" int nele_conv_span_bf16x3_supported(int M, int N, const int* geom, int KH, int KW) {
+    ConvGeom g;
+    memcpy(&g, geom, sizeof(ConvGeom));
+    if (g.Wout < 32) return 0;
+    if (KH == 1 && conv1d16x3_sb(g, N, KH, KW, nullptr)) return 1;
+    return tile16x3_th(g, N, KH, KW) ? 1 : 0;
+}
+
+// nele_conv_span_bf16 with split operands: Whi / Wlo from nele_weight_prep_frag16x3 (same fragment layout as Wfrag there)
+extern "C" int nele_conv_span_bf16x3(const float* A, const void* Whi, const void* Wlo, const float* bias, const float* aux, float* out, int M, int N,
+                                     int epi, float slope, const int* geom, int KH, int KW, long long a_elems, void* stream) {
+    NELE_CHECK_ARG(A && Whi && Wlo && out && geom, "nele_conv_span_bf16x3: null pointer");
+    if (!nele_conv_span_bf16x3_supported(M, N, geom, KH, KW)) return nele_set_error(NELE_ERR_UNSUPPORTED, "nele_conv_span_bf16x3: geometry not supported");
+    NELE_CHECK_ARG(a_elems < 2147483647LL, "nele_conv_span_bf16x3: input buffer too large for 32-bit offsets");
+    NELE_CHECK_ARG(!(epi == EPI_BIAS || epi == EPI_BIAS_LRELU || epi == EPI_BIAS_EXPTANH) || bias, "nele_conv_span_bf16x3: epilogue needs bias");
+    NELE_CHECK_ARG(epi != EPI_MASK_LRELU_GRAD || aux, "nele_conv_span_bf16x3: epilogue needs aux");
+    Tile16Args t;
+    memcpy(&t.g, geom, sizeof(ConvGeom));
+    t.A = A; t.Wfrag = (const __bf16*)Whi; t.bias = bias; t.aux = aux; t.out = out; t.N = N; t.NT = (N + 15) / 16; t.epi = epi; t.slope = slope;
+    t.KH = KH; t.KW = KW; t.steps_per_seg = (t.g.seglen + 31) / 32; t.dbg = nullptr;
+    const __bf16* wlo = (const __bf16*)Wlo;
+    hipStream_t s = as_stream(stream);
+    size_t clds = 0;
+    const int csb = KH == 1 ? conv1d16x3_sb(t.g, N, KH, KW, &clds) : 0;
+    if (csb) {
+        static unsigned long long cattr = 0;
+        if (nele_first_use_on_device(&cattr)) {
+#define C1DX3_ATTR(TN_) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_tile16x3_kernel<TN_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
+            C1DX3_ATTR(1); C1DX3_ATTR(2); C1DX3_ATTR(3); C1DX3_ATTR(4);
+#undef C1DX3_ATTR
+        }
+        const int BH = M / t.g.Wout;
+        const int nchunksN = (N > 64) ? N / 64 : 1, TNsel = (N >= 64) ? 4 : t.NT;
+        const int nstrips = ((t.g.Wout + C1D_TW - 1) / C1D_TW) * BH;
+        t.SB = csb; t.steps_per_seg = t.g.seglen / 32; t.ntiles = nchunksN; t.ncl = 1; t.SBH = BH;
+        const dim3 grid((unsigned)(t.ntiles * 8 * ((nstrips + 7) / 8)));
+        switch (TNsel) {
+            case 1: hipLaunchKernelGGL((conv1d_tile16x3_kernel<1>), grid, dim3(256), clds, s, t, wlo); break;
+            case 2: hipLaunchKernelGGL((conv1d_tile16x3_kernel<2>), grid, dim3(256), clds, s, t, wlo); break;
+            case 3: hipLaunchKernelGGL((conv1d_tile16x3_kernel<3>), grid, dim3(256), clds, s, t, wlo); break;
+            default: hipLaunchKernelGGL((conv1d_tile16x3_kernel<4>), grid, dim3(256), clds, s, t, wlo); break;
+        }
+        NELE_CHECK_LAUNCH("nele_conv_span_bf16x3(conv1d)");
+        return NELE_OK;
+    }
+    const int th = tile16x3_th(t.g, N, KH, KW);
+    t.SB = tile16x3_sb(t.g);
+    const int B_ = M / (t.g.Hout * t.g.Wout);
+    const size_t lds = tile16x3_lds(t.g, N, KH, KW, th);
+    static unsigned long long tattr = 0;
+    if (nele_first_use_on_device(&tattr)) {
+#define T16X3_ATTR(TN_, TH_) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_tile16x3_kernel<TN_, TH_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
+        T16X3_ATTR(1, 4); T16X3_ATTR(2, 4); T16X3_ATTR(3, 4); T16X3_ATTR(4, 4);
+        T16X3_ATTR(1, 2); T16X3_ATTR(2, 2); T16X3_ATTR(3, 2); T16X3_ATTR(4, 2);
+#undef T16X3_ATTR
+    }
+    t.ntiles = ((t.g.Wout + TILE16_TW - 1) / TILE16_TW) * ((t.g.Hout + th - 1) / th) * B_;
+    const dim3 grid((unsigned)((t.ntiles + 7) / 8 * 8));
+#define T16X3_LAUNCH(TN_, TH_) hipLaunchKernelGGL((conv_tile16x3_kernel<TN_, TH_>), grid, dim3(256), lds, s, t, wlo)
+#define T16X3_PICK(TH_) switch (t.NT) { case 1: T16X3_LAUNCH(1, TH_); break; case 2: T16X3_LAUNCH(2, TH_); break; case 3: T16X3_LAUNCH(3, TH_); break; default: T16X3_LAUNCH(4, TH_); break; }
+    // measurement hook: "tile16x3_N<N>_K<Ktot>" times one layer's launch (D.conv5 forward: tile16x3_N64_K3888)
+    char ptag[48] = "";
+    if (nele_prof_armed()) snprintf(ptag, sizeof(ptag), "tile16x3_N%d_K%d", N, t.g.Ktot);
+    const bool prof_t = ptag[0] && nele_prof_match(ptag);
+    if (prof_t) nele_prof_mark(s);
+    if (th == 4) { T16X3_PICK(4) } else { T16X3_PICK(2) }
+    if (prof_t) nele_prof_mark(s);
+#undef T16X3_PICK
+#undef T16X3_LAUNCH
+    NELE_CHECK_LAUNCH("nele_conv_span_bf16x3(tile)");
+    return NELE_OK;
+}
+
+// Weight gradient with split operands.  Layers the split tile kernel declines (too wide for its LDS budget, short rows) run on the float32
+// kernels: the result is float32-grade either way, and never a single bf16 product.
+// dynamic LDS of the split weight-gradient kernel: 160 KB less its 4 KB of static bias-reduction scratch; the input rows are staged as
+// 9 pieces of 8 elements per thread (at most 4 x RS = 18432 elements)
+#define WTX3_LDS_MAX (156 * 1024)
+static long long wgrad_tile16x3_lds(int NT, int KW, int C) {
+    return 2 * ((long long)WT_TH * (WT_TW + KW - 1) * C + WT_SLACK + 256 * WT_NP_OF(NT)) * 2;
+}
+static bool wgrad_x3_sliced(int M, int N, const ConvGeom& g, int KH, int KW) {
+    return N % 64 == 0 && g.C % 64 == 0 && KW * g.C == g.seglen && KW * 4 <= 28 && g.Wout >= 32 && M % (g.Hout * g.Wout) == 0 &&
+           WT_TH * (WT_TW + KW - 1) * 64 <= 9 * 2048 && wgrad_tile16x3_lds(4, KW, 64) <= WTX3_LDS_MAX;
+}
+static bool wgrad_x3_tile(int M, int N, const ConvGeom& g, int KH, int KW) {
+    return N <= 64 && g.C % 8 == 0 && KW * g.C == g.seglen && (g.seglen + 15) / 16 <= 28 && g.Wout >= 32 &&
+           (long long)WT_TH * (WT_TW + KW - 1) * g.C <= 9 * 2048 && wgrad_tile16x3_lds((N + 15) / 16, KW, g.C) <= WTX3_LDS_MAX && M % (g.Hout * g.Wout) == 0;
+}
+extern "C" int nele_conv_wgrad_bf16x3_supported(int M, int N, const int* geom, int KH, int KW) {
+    ConvGeom g;
+    memcpy(&g, geom, sizeof(ConvGeom));
+    if (N % 4 || g.OC % 4 || KH * KW * g.C != g.Ktot) return 0;
+    return (wgrad_x3_tile(M, N, g, KH, KW) || wgrad_x3_sliced(M, N, g, KH, KW)) ? 1 : 0;
+}
+extern "C" int nele_conv_wgrad_bf16x3(const float* A, const float* dOut, float* workspace, long long workspace_floats, int M, int N,
+                                      const int* geom, int KH, int KW, int Cvalid, float* dW, float* db, int accumulate, void* stream) {
+    if (!nele_conv_wgrad_bf16x3_supported(M, N, geom, KH, KW))
+        return conv_wgrad_impl(A, dOut, workspace, workspace_floats, M, N, geom, KH, KW, Cvalid, dW, db, accumulate, 0, stream);
+    NELE_CHECK_ARG(A && dOut && workspace && geom && dW, "nele_conv_wgrad_bf16x3: null pointer");
+    ConvGeom g;
+    memcpy(&g, geom, sizeof(ConvGeom));
+    int st = check_geom("nele_conv_wgrad_bf16x3", g, M, N);
+    if (st) return st;
+    int splits = 1;
+    const long long need = nele_conv_wgrad_workspace_floats(M, N, g.Ktot, &splits);
+    if (workspace_floats < need) return nele_set_error(NELE_ERR_WORKSPACE, "nele_conv_wgrad_bf16x3: workspace %lld < %lld floats", workspace_floats, need);
+    hipStream_t s = as_stream(stream);
+    // measurement hook: "wgrad_N<N>_K<Ktot>" as in conv_wgrad_impl (the launch and its partial reduction)
+    char ptag[48] = "";
+    if (nele_prof_armed()) snprintf(ptag, sizeof(ptag), "wgrad_N%d_K%d", N, g.Ktot);
+    const bool prof_w = ptag[0] && nele_prof_match(ptag);
+    if (prof_w) nele_prof_mark(s);
+    ConvGeom gt = g;                                       // sub-problems of 64 x 64 channels for the wide layers, as in conv_wgrad_impl
+    int Nt = N, subs_n = 1, subs_c = 1, Bt = M / (g.Hout * g.Wout);
+    if (!wgrad_x3_tile(M, N, g, KH, KW)) {
+        gt.C = 64; gt.seglen = KW * 64; gt.Ktot = KH * KW * 64;
+        Nt = 64; subs_n = N / 64; subs_c = g.C / 64;
+        if (KH == 1 && g.H == 1 && g.Hout == 1 && g.OH == 1 && g.ih0 == 0 && g.oh0 == 0) { gt.H = Bt; gt.Hout = Bt; gt.OH = Bt; Bt = 1; }
+    }
+    const int nkt = (gt.seglen + 15) / 16, NT = (Nt + 15) / 16, ktw = (nkt + 3) / 4;
+    const size_t lds = (size_t)wgrad_tile16x3_lds(NT, KW, gt.C);
+    WgradTileArgs t;
+    t.A = A; t.dOut = dOut; t.part = workspace; t.N = Nt; t.B = Bt; t.KH = KH; t.KW = KW; t.d16 = 0;
+    t.ics = g.C; t.subs_n = subs_n; t.subs_c = subs_c; t.Kfull = g.Ktot;
+    t.nth = (gt.Hout + WT_TH - 1) / WT_TH; t.ntw = (gt.Wout + WT_TW - 1) / WT_TW; t.ntiles = t.B * t.nth * t.ntw;
+    const int max_splits = (M + 511) / 512;
+    int G = (max_splits < 64) ? (max_splits > splits ? max_splits : splits) : 64;
+    if (G < splits) G = splits;
+    if (G > t.ntiles) G = t.ntiles;
+    const int wg_per_group = KH * subs_n * subs_c;
+    {   // one workgroup per CU (LDS): the group count (a multiple of 8) that minimises rounds x tiles per workgroup
+        static int ncu = 0;
+        if (!ncu) { int dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev); if (ncu <= 0) ncu = 256; }
+        if (G >= 16) {
+            long long best = -1;
+            int bestG = G;
+            for (int cand = G & ~7; cand >= 8; cand -= 8) {
+                const long long rounds = ((long long)wg_per_group * cand + ncu - 1) / ncu, per = (t.ntiles + cand - 1) / cand;
+                if (best < 0 || rounds * per < best) { best = rounds * per; bestG = cand; }
+            }
+            G = bestG;
+        }
+    }
+    t.G = G; t.g = gt;
+    t.bpart = db ? workspace + (size_t)G * N * g.Ktot : nullptr;
+    static unsigned long long wattr = 0;
+    if (nele_first_use_on_device(&wattr)) {
+#define WTX3_ATTR(NT_, K_) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_tile16x3_kernel<NT_, K_>), hipFuncAttributeMaxDynamicSharedMemorySize, WTX3_LDS_MAX)
+        WTX3_ATTR(1, 2); WTX3_ATTR(2, 2); WTX3_ATTR(3, 2); WTX3_ATTR(4, 2); WTX3_ATTR(1, 4); WTX3_ATTR(2, 4); WTX3_ATTR(3, 4); WTX3_ATTR(4, 4);
+        WTX3_ATTR(1, 7); WTX3_ATTR(2, 7); WTX3_ATTR(3, 7); WTX3_ATTR(4, 7);
+#undef WTX3_ATTR
+    }
+    const dim3 grid(wg_per_group * G);
+#define WTX3_LAUNCH(NT_, K_) hipLaunchKernelGGL((conv_wgrad_tile16x3_kernel<NT_, K_>), grid, dim3(256), lds, s, t)
+#define WTX3_PICK(K_) switch (NT) { case 1: WTX3_LAUNCH(1, K_); break; case 2: WTX3_LAUNCH(2, K_); break; case 3: WTX3_LAUNCH(3, K_); break; default: WTX3_LAUNCH(4, K_); break; }
+    if (ktw <= 2) { WTX3_PICK(2) } else if (ktw <= 4) { WTX3_PICK(4) } else { WTX3_PICK(7) }
+#undef WTX3_PICK
+#undef WTX3_LAUNCH
+    NELE_CHECK_LAUNCH("nele_conv_wgrad_bf16x3(tile)");
+    const int total = N * g.Ktot;
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(min(1024, (total + 255) / 256)), dim3(256), 0, s, workspace, t.bpart, G, N, KH, KW, g.C, Cvalid, dW, db,
+                       accumulate);
+    NELE_CHECK_LAUNCH("nele_conv_wgrad_bf16x3(reduce)");
+    if (prof_w) nele_prof_mark(s);
     return NELE_OK;
 }

@@ -142,15 +142,16 @@ GParams g_params() {
 }
 
 struct GWs {
-    Buf wf[8], wb[8], wf16f[8], wf16b[8], wgl0[6], wgl1[6];
+    Buf wf[8], wb[8], wf16f[8], wf16b[8], wgl0[6], wgl1[6], wx3f[6][2], wx3b[6][2];   // wx3*: hi / lo fragment streams of the conv layers (bf16x3)
     Buf a5, h1, inp16[6], carry, Y[6], mean[6], rstd[6], cln_scratch, inp[6], dY[6], dY16[6], dA[6], da5, do2, dpre1, gpart, bpart, ws;
     Geom gf[6], gb[6], gw[6], gfc, gwfc;
     int nchunks = 0;
-    bool fused_ok = false, fused = false;
+    bool fused_ok = false, fused = false, x3 = false;
     size_t bytes = 0;
 };
 
-void g_layout(int B, int T, bool bf16, bool need_bwd, void* base, GWs& w) {
+// bf16x3 (x3): float32 buffers as in float32 mode; the conv layers' passes on the split kernels, the Linear layers on the float32 kernels
+void g_layout(int B, int T, bool bf16, bool need_bwd, void* base, GWs& w, bool x3 = false) {
     Ws a(base);
     const int dims[8][4] = {{256, 5 * 128, 128, 5 * 256}, {256, 7 * 256, 256, 7 * 256}, {256, 7 * 256, 256, 7 * 256}, {256, 7 * 256, 256, 7 * 256},
                             {256, 7 * 256, 256, 7 * 256}, {64, 5 * 256, 256, 5 * 64}, {64, 64, 64, 64}, {64, 64, 64, 64}};
@@ -158,6 +159,13 @@ void g_layout(int B, int T, bool bf16, bool need_bwd, void* base, GWs& w) {
     w.fused_ok = NELE_SWITCH_INT("NELE_G_FUSED", 1) != 0;           // =0: the per-layer kernels in bf16 mode too (A/B)
     for (int l = 0; l < 6; ++l) w.fused_ok = w.fused_ok && nele_glayer16_supported(G_LAYERS[l].cin, G_LAYERS[l].cout, G_LAYERS[l].k);
     w.fused = bf16 && w.fused_ok && (!need_bwd || T >= 32);
+    w.x3 = x3;
+    if (x3)
+        for (int l = 0; l < 6; ++l)
+            for (int h = 0; h < 2; ++h) {
+                w.wx3f[l][h] = a.bf16(nele_weight_frag16_elems(dims[l][0], dims[l][1], 1));
+                w.wx3b[l][h] = a.bf16(nele_weight_frag16_elems(dims[l][2], dims[l][3], 1));
+            }
     if (bf16) {
         for (int q = 0; q < 8; ++q) {
             w.wf16f[q] = a.bf16(nele_weight_frag16_elems(dims[q][0], dims[q][1], 1));
@@ -214,6 +222,11 @@ void g_layout(int B, int T, bool bf16, bool need_bwd, void* base, GWs& w) {
 // Generator_Conv1D_cLN._gemm
 void g_gemm(Builder& b, const GWs& w, bool bf16, const Buf& A, int q, bool back, const void* bias, const void* aux, Arg out, int B, int N, int epi, const Geom& g) {
     const long long M = M_of(B, g);
+    if (w.x3 && q < 6 && nele_conv_span_bf16x3_supported((int)M, N, g.a, g.KH, g.KW)) {
+        const Buf* f = back ? w.wx3b[q] : w.wx3f[q];
+        b.add("nele_conv_span_bf16x3", 0, {P(A), P(f[0]), P(f[1]), P(bias), P(aux), out, I(M), I(N), I(epi), F(SLOPE), P(b.geom(g)), I(g.KH), I(g.KW), I(A.elems)});
+        return;
+    }
     if (bf16 && nele_conv_span_bf16_supported((int)M, N, g.a, g.KH, g.KW)) {
         b.add("nele_conv_span_bf16", 0, {P(A), P(back ? w.wf16b[q] : w.wf16f[q]), P(bias), P(aux), out, I(M), I(N), I(epi), F(SLOPE), P(b.geom(g)), I(g.KH), I(g.KW), I(A.elems)});
         return;
@@ -234,6 +247,17 @@ void g_prep_weights(Builder& b, const GWs& w, const float* par, const GParams& p
         memcpy(dj + 5 * q, d, sizeof(d));
     }
     b.add("nele_weight_prep_batch", 0, {P(b.host(pj, 32)), P(b.host(dj, 40)), I(8)});
+    if (w.x3) {
+        const void* xj[36]; int yj[48];
+        for (int l = 0; l < 6; ++l) {
+            const GL& L = G_LAYERS[l];
+            xj[6 * l] = w.wf[l].p; xj[6 * l + 1] = w.wx3f[l][0].p; xj[6 * l + 2] = w.wx3f[l][1].p;
+            xj[6 * l + 3] = w.wb[l].p; xj[6 * l + 4] = w.wx3b[l][0].p; xj[6 * l + 5] = w.wx3b[l][1].p;
+            const int d[8] = {L.cout, L.k * L.cin, L.k * L.cin, 1, L.cin, L.k * L.cout, L.k * L.cout, 1};
+            memcpy(yj + 8 * l, d, sizeof(d));
+        }
+        b.add("nele_weight_prep_frag16x3_batch", 0, {P(b.host(xj, 36)), P(b.host(yj, 48)), I(12)});
+    }
     if (!bf16) return;
     const int dims[8][4] = {{256, 5 * 128, 128, 5 * 256}, {256, 7 * 256, 256, 7 * 256}, {256, 7 * 256, 256, 7 * 256}, {256, 7 * 256, 256, 7 * 256},
                             {256, 7 * 256, 256, 7 * 256}, {64, 5 * 256, 256, 5 * 64}, {64, 64, 64, 64}, {64, 64, 64, 64}};
@@ -305,7 +329,11 @@ void g_backward(Builder& b, const GWs& w, const float* par, float* grad, const G
                                  P(w.fused ? w.dY16[l].p : nullptr), P(w.gpart), P(w.bpart), P(w.cln_scratch), I(B), I(T), I(L.cout), I(L.k - 1), F(SLOPE)});
         b.add("nele_colsum2", 0, {P(w.gpart), P(grad + pp.gain[l]), P(w.bpart), P(grad + pp.beta[l]), I((long long)B * w.nchunks), I(L.cout), I(1)});
         if (w.fused) wgrad(w.inp16[l], w.dY16[l], L.cout, w.gw[l], L.cin, grad + pp.w[l], grad + pp.b[l], true);
-        else wgrad(w.inp[l], w.dY[l], L.cout, w.gw[l], L.cin, grad + pp.w[l], grad + pp.b[l], bf16);
+        else if (w.x3) {
+            if (overlap) b.hand_over(0, 1);
+            b.add("nele_conv_wgrad_bf16x3", wst, {P(w.inp[l]), P(w.dY[l]), P(w.ws), I(w.ws.elems), I(M_of(B, w.gw[l])), I(L.cout), P(b.geom(w.gw[l])), I(w.gw[l].KH),
+                                                  I(w.gw[l].KW), I(L.cin), P(grad + pp.w[l]), P(grad + pp.b[l]), I(1)});
+        } else wgrad(w.inp[l], w.dY[l], L.cout, w.gw[l], L.cin, grad + pp.w[l], grad + pp.b[l], bf16);
         if (l > 0) {
             if (w.fused) b.add("nele_glayer16_conv", 0, {P(w.dY16[l]), P(w.wgl1[l]), P(w.dA[l]), I(B), I(T), I(L.cout), I(L.cin), I(L.k)});
             else g_gemm(b, w, bf16, w.dY[l], l, true, nullptr, nullptr, P(w.dA[l]), B, L.cin, EPI_NONE, w.gb[l]);
@@ -340,17 +368,19 @@ DParams d_params(int cin, int nout) {
 }
 
 struct DWs {
-    Buf sigma, wf[5], wb[5], wff[5], wbf[5], wff16[5], wbf16[5], wf16c[5], wb16c[5];
+    Buf sigma, wf[5], wb[5], wff[5], wbf[5], wff16[5], wbf16[5], wf16c[5], wb16c[5], wfx3[5][2], wbx3[5][2];   // wfx3 / wbx3: hi, lo (bf16x3)
     Buf act[5], gbuf[5], gbuf16, ddin, gap_part, pooled, h1, h2, dz1, dz2, dz3, dpooled, ws, tmpw, scratch64, ws2, tmpw2, scratch64b;
     Geom gf[5], gb[5], gw[5];
     int dims[6][3], pad[5], cins[5];
-    bool c16 = false, grad16_ok = false, span_f[5], span_b[5], span16_f[5], span16_b[5];
+    bool c16 = false, grad16_ok = false, span_f[5], span_b[5], span16_f[5], span16_b[5], x3 = false, x3_f[5] = {}, x3_b[5] = {};
     int P = 0, gap_parts = 0;
     size_t bytes = 0;
 };
 
-int d_layout(int B, int T, int cin0, bool bf16, void* base, DWs& w) {
+// bf16x3 (x3): float32 buffers as in float32 mode; layers 1-4 on the split kernels where they take the geometry, layer 0 (1 x 1) float32
+int d_layout(int B, int T, int cin0, bool bf16, void* base, DWs& w, bool x3 = false) {
     Ws a(base);
+    w.x3 = x3;
     w.sigma = a.f32(8);
     {
         int cpad = 4;
@@ -363,6 +393,8 @@ int d_layout(int B, int T, int cin0, bool bf16, void* base, DWs& w) {
             w.wff16[l] = a.bf16(nele_weight_frag16_elems(co, k * cpad, k));
             w.wbf16[l] = a.bf16(nele_weight_frag16_elems(cpad, k * co, k));
             if (k > 1) { w.wf16c[l] = a.bf16(nele_conv16_wfrag_elems(co, k * cpad, k)); w.wb16c[l] = a.bf16(nele_conv16_wfrag_elems(cpad, k * co, k)); }
+            if (x3 && k > 1)
+                for (int h = 0; h < 2; ++h) { w.wfx3[l][h] = a.bf16(nele_weight_frag16_elems(co, k * cpad, k)); w.wbx3[l][h] = a.bf16(nele_weight_frag16_elems(cpad, k * co, k)); }
             cpad = co;
         }
     }
@@ -404,6 +436,10 @@ int d_layout(int B, int T, int cin0, bool bf16, void* base, DWs& w) {
         w.span_b[l] = nele_conv_span_supported((int)M_of(B, w.gb[l]), w.cins[l], w.gb[l].a, w.gb[l].KH, w.gb[l].KW) != 0;
         w.span16_f[l] = nele_conv_span_bf16_supported((int)M_of(B, w.gf[l]), co, w.gf[l].a, w.gf[l].KH, w.gf[l].KW) != 0;
         w.span16_b[l] = nele_conv_span_bf16_supported((int)M_of(B, w.gb[l]), w.cins[l], w.gb[l].a, w.gb[l].KH, w.gb[l].KW) != 0;
+        if (x3 && l > 0) {
+            w.x3_f[l] = nele_conv_span_bf16x3_supported((int)M_of(B, w.gf[l]), co, w.gf[l].a, w.gf[l].KH, w.gf[l].KW) != 0;
+            w.x3_b[l] = nele_conv_span_bf16x3_supported((int)M_of(B, w.gb[l]), w.cins[l], w.gb[l].a, w.gb[l].KH, w.gb[l].KW) != 0;
+        }
     }
     w.grad16_ok = NELE_SWITCH_INT("NELE_D_GRAD16", 1) && !w.c16 && nele_conv_span_bf16_a16_supported((int)M_of(B, w.gb[4]), w.cins[4], w.gb[4].a, w.gb[4].KH, w.gb[4].KW) &&
                   nele_conv_wgrad_bf16_d16_supported((int)M_of(B, w.gw[4]), D_CONVS[4][0], w.gw[4].a, w.gw[4].KH, w.gw[4].KW);
@@ -479,9 +515,20 @@ void d_prepare(Builder& b, const DWs& w, const float* par, const DParams& pp, co
         for (int l = 0; l < 5; ++l) {
             const int co = D_CONVS[l][0], k = D_CONVS[l][1];
             b.add("nele_weight_prep", 0, {P(par + pp.w[l]), P(sig + l), I(co), I(ci), I(cpad), I(k), I(k), P(w.wf[l]), P(w.wb[l])});
-            if (w.span_f[l]) b.add("nele_weight_prep_frag", 0, {P(w.wf[l]), I(co), I(k * k * cpad), P(w.wff[l])});
-            if (w.span_b[l]) b.add("nele_weight_prep_frag", 0, {P(w.wb[l]), I(cpad), I(k * k * co), P(w.wbf[l])});
+            if (w.span_f[l] && !w.x3_f[l]) b.add("nele_weight_prep_frag", 0, {P(w.wf[l]), I(co), I(k * k * cpad), P(w.wff[l])});
+            if (w.span_b[l] && !w.x3_b[l]) b.add("nele_weight_prep_frag", 0, {P(w.wb[l]), I(cpad), I(k * k * co), P(w.wbf[l])});
             ci = cpad = co;
+        }
+        if (w.x3) {
+            const void* xj[24]; int yj[32]; int nx = 0;
+            cpad = 4;
+            for (int l = 0; l < 5; ++l) {
+                const int co = D_CONVS[l][0], k = D_CONVS[l][1];
+                if (w.x3_f[l]) { xj[3 * nx] = w.wf[l].p; xj[3 * nx + 1] = w.wfx3[l][0].p; xj[3 * nx + 2] = w.wfx3[l][1].p; const int e0[4] = {co, k * k * cpad, k * cpad, k}; memcpy(yj + 4 * nx, e0, sizeof(e0)); ++nx; }
+                if (w.x3_b[l]) { xj[3 * nx] = w.wb[l].p; xj[3 * nx + 1] = w.wbx3[l][0].p; xj[3 * nx + 2] = w.wbx3[l][1].p; const int e1[4] = {cpad, k * k * co, k * co, k}; memcpy(yj + 4 * nx, e1, sizeof(e1)); ++nx; }
+                cpad = co;
+            }
+            if (nx) b.add("nele_weight_prep_frag16x3_batch", 0, {P(b.host(xj, 3 * nx)), P(b.host(yj, 4 * nx)), I(nx)});
         }
     }
 }
@@ -503,6 +550,9 @@ void d_forward(Builder& b, const DWs& w, const float* par, const DParams& pp, in
                 b.add("nele_conv16_gap", 0, {A, P(w.wf16c[l]), P(bias), P(w.act[l]), I(M), I(co), F(SLOPE), P(b.geom(g)), I(g.KH), I(g.KW), S(1), P(w.gap_part)});
             else
                 b.add("nele_conv16", 0, {A, P(w.wf16c[l]), P(bias), P((void*)nullptr), P(w.act[l]), I(1), I(M), I(co), I(EPI_BIAS_LRELU), F(SLOPE), P(b.geom(g)), I(g.KH), I(g.KW)});
+        } else if (w.x3_f[l]) {
+            b.add("nele_conv_span_bf16x3", 0, {A, P(w.wfx3[l][0]), P(w.wfx3[l][1]), P(bias), P((void*)nullptr), P(w.act[l]), I(M), I(co), I(EPI_BIAS_LRELU), F(SLOPE), P(b.geom(g)), I(g.KH),
+                                                I(g.KW), I(a_elems)});
         } else if (bf16 && w.span16_f[l]) {
             b.add("nele_conv_span_bf16", 0, {A, P(w.wff16[l]), P(bias), P((void*)nullptr), P(w.act[l]), I(M), I(co), I(EPI_BIAS_LRELU), F(SLOPE), P(b.geom(g)), I(g.KH), I(g.KW), I(a_elems)});
         } else if (w.span_f[l]) {
@@ -559,7 +609,7 @@ void d_backward(Builder& b, const DWs& w, const float* par, float* grad, const D
             if (overlap) b.hand_over(0, st);
             const Buf& dOut = l == 4 ? glast : w.gbuf[l];
             const bool b16 = bf16 && l > 0;
-            const char* fn = b16 ? "nele_conv_wgrad_bf16" : "nele_conv_wgrad";
+            const char* fn = b16 ? "nele_conv_wgrad_bf16" : (w.x3 && l > 0) ? "nele_conv_wgrad_bf16x3" : "nele_conv_wgrad";
             const bool a16 = l > 0 && w.act[l - 1].b16;
             if (dOut.b16) fn = a16 ? "nele_conv_wgrad_bf16_a16d16" : "nele_conv_wgrad_bf16_d16";
             const Geom& g = w.gw[l];
@@ -573,7 +623,10 @@ void d_backward(Builder& b, const DWs& w, const float* par, float* grad, const D
             b.add("nele_conv16", 0, {P(w.gbuf[l]), P(w.wb16c[l]), P((void*)nullptr), P(w.act[l - 1]), P(w.gbuf[l - 1]), I(w.gbuf[l - 1].b16 ? 1 : 0), I(M), I(Ci), I(EPI_MASK_LRELU_GRAD),
                                     F(SLOPE), P(b.geom(g)), I(g.KH), I(g.KW)});
         } else if (l > 0) {
-            if (bf16 && w.span16_b[l]) {
+            if (w.x3_b[l]) {
+                b.add("nele_conv_span_bf16x3", 0, {P(w.gbuf[l]), P(w.wbx3[l][0]), P(w.wbx3[l][1]), P((void*)nullptr), P(w.act[l - 1]), P(w.gbuf[l - 1]), I(M), I(Ci),
+                                                    I(EPI_MASK_LRELU_GRAD), F(SLOPE), P(b.geom(g)), I(g.KH), I(g.KW), I(w.gbuf[l].elems)});
+            } else if (bf16 && w.span16_b[l]) {
                 const Buf& src = l == 4 ? glast : w.gbuf[l];
                 b.add(src.b16 ? "nele_conv_span_bf16_a16" : "nele_conv_span_bf16", 0, {P(src), P(w.wbf16[l]), P((void*)nullptr), P(w.act[l - 1]), P(w.gbuf[l - 1]), I(M), I(Ci),
                                                                                     I(EPI_MASK_LRELU_GRAD), F(SLOPE), P(b.geom(g)), I(g.KH), I(g.KW), I(src.elems)});
@@ -593,6 +646,10 @@ void d_backward(Builder& b, const DWs& w, const float* par, float* grad, const D
 }  // namespace
 
 // ------------------------------------------------------------------------------------------ C ABI
+// precision codes (include/nele_hip.h): NELE_PREC_BF16X3 = split operands; every other nonzero value = bf16 operands, as before the code
+static bool prec_bf16(int prec) { return prec != NELE_PREC_F32 && prec != NELE_PREC_BF16X3; }
+static bool prec_x3(int prec) { return prec == NELE_PREC_BF16X3; }
+
 extern "C" long long nele_gen_param_count(void) { return g_params().total; }
 extern "C" long long nele_disc_param_count(int cin, int nout) { return (cin >= 1 && cin <= 4 && nout >= 1 && nout <= 4) ? d_params(cin, nout).total : -1; }
 
@@ -616,7 +673,7 @@ extern "C" int nele_disc_param_layout(int cin, int nout, long long* offsets, int
 extern "C" long long nele_gen_workspace_bytes(int B, int T, int bf16, int need_bwd) {
     if (B <= 0 || T <= 0) return -1;
     GWs w;
-    g_layout(B, T, bf16 != 0, need_bwd != 0, nullptr, w);
+    g_layout(B, T, prec_bf16(bf16), need_bwd != 0, nullptr, w, prec_x3(bf16));
     return (long long)w.bytes;
 }
 
@@ -649,7 +706,7 @@ struct Built {                                       // the tables of one build 
 int gen_build(const char* fn, int B, int T, int bf16, int need_bwd, int overlap_wgrad, const float* params_flat, float* grads_flat, void* workspace,
               long long workspace_bytes, int zero_fill, void* stream, bool fold_prep, void** prep_out, void** fwd_out, void** bwd_out) {
     GWs w;
-    g_layout(B, T, bf16 != 0, need_bwd != 0, workspace, w);
+    g_layout(B, T, prec_bf16(bf16), need_bwd != 0, workspace, w, prec_x3(bf16));
     if (workspace_bytes < (long long)w.bytes) return nele_set_error(NELE_ERR_WORKSPACE, "%s: workspace too small (%lld < %lld)", fn, workspace_bytes, (long long)w.bytes);
     // zero rows in front of / behind the time axis, zero carry slots: written once, kept by the kernels
     if (zero_fill && hipMemsetAsync(workspace, 0, w.bytes, as_stream(stream)) != hipSuccess) return nele_set_error(NELE_ERR_HIP, "%s: hipMemsetAsync failed", fn);
@@ -659,19 +716,19 @@ int gen_build(const char* fn, int B, int T, int bf16, int need_bwd, int overlap_
     if (prep_out) {
         out.outs[0] = prep_out;
         Builder b;
-        g_prep_weights(b, w, params_flat, pp, bf16 != 0);
+        g_prep_weights(b, w, params_flat, pp, prec_bf16(bf16));
         if (const int st = finish_plan(b, 0, {}, {}, prep_out)) return st;
     }
     if (fwd_out) {
         out.outs[1] = fwd_out;
         Builder b;
-        g_forward(b, w, params_flat, pp, B, T, bf16 != 0, need_bwd != 0, fold_prep);
+        g_forward(b, w, params_flat, pp, B, T, prec_bf16(bf16), need_bwd != 0, fold_prep);
         if (const int st = finish_plan(b, 4, {io, io, io}, {0, 0, 0}, fwd_out)) return st;
     }
     if (bwd_out) {
         out.outs[2] = bwd_out;
         Builder b;
-        g_backward(b, w, params_flat, grads_flat, pp, B, T, bf16 != 0, overlap_wgrad != 0);
+        g_backward(b, w, params_flat, grads_flat, pp, B, T, prec_bf16(bf16), overlap_wgrad != 0);
         if (const int st = finish_plan(b, 2, {io, io}, {0, 0}, bwd_out)) return st;
     }
     out.ok = true;
@@ -684,7 +741,7 @@ int disc_build(const char* fn, int B, int T, int cin, int nout, int bf16, int tr
                float* grads_flat, const void* const* sn_uv_host, void* workspace, long long workspace_bytes, int zero_fill, void* stream, bool fold_prep,
                void** prep_out, void** fwd_out, void** bwd_out) {
     DWs w;
-    if (const int st = d_layout(B, T, cin, bf16 != 0, workspace, w)) return st;
+    if (const int st = d_layout(B, T, cin, prec_bf16(bf16), workspace, w, prec_x3(bf16))) return st;
     if (workspace_bytes < (long long)w.bytes) return nele_set_error(NELE_ERR_WORKSPACE, "%s: workspace too small (%lld < %lld)", fn, workspace_bytes, (long long)w.bytes);
     if (zero_fill && hipMemsetAsync(workspace, 0, w.bytes, as_stream(stream)) != hipSuccess) return nele_set_error(NELE_ERR_HIP, "%s: hipMemsetAsync failed", fn);
     const DParams pp = d_params(cin, nout);
@@ -693,20 +750,20 @@ int disc_build(const char* fn, int B, int T, int cin, int nout, int bf16, int tr
     if (prep_out) {
         out.outs[0] = prep_out;
         Builder b;
-        d_prepare(b, w, params_flat, pp, sn_uv_host, cin, bf16 != 0, S(0));
+        d_prepare(b, w, params_flat, pp, sn_uv_host, cin, prec_bf16(bf16), S(0));
         if (const int st = finish_plan(b, 1, {0}, {0}, prep_out)) return st;
     }
     if (fwd_out) {
         out.outs[1] = fwd_out;
         Builder b;
-        if (fold_prep) d_prepare(b, w, params_flat, pp, sn_uv_host, cin, bf16 != 0, I(train ? 1 : 0));
-        d_forward(b, w, params_flat, pp, B, T, nout, bf16 != 0);
+        if (fold_prep) d_prepare(b, w, params_flat, pp, sn_uv_host, cin, prec_bf16(bf16), I(train ? 1 : 0));
+        d_forward(b, w, params_flat, pp, B, T, nout, prec_bf16(bf16));
         if (const int st = finish_plan(b, 3, {din_bytes, (long long)B * 4, sc_bytes}, {0, 1, 0}, fwd_out)) return st;
     }
     if (bwd_out) {
         out.outs[2] = bwd_out;
         Builder b;
-        d_backward(b, w, params_flat, grads_flat, pp, sn_uv_host, B, T, cin, nout, bf16 != 0, need_din != 0, weight_grads != 0, overlap_wgrad != 0);
+        d_backward(b, w, params_flat, grads_flat, pp, sn_uv_host, B, T, cin, nout, prec_bf16(bf16), need_din != 0, weight_grads != 0, overlap_wgrad != 0);
         if (const int st = finish_plan(b, 4, {sc_bytes, sc_bytes, (long long)B * 4, din_bytes}, {0, 0, 1, 0}, bwd_out)) return st;
     }
     out.ok = true;
@@ -733,14 +790,14 @@ extern "C" int nele_gen_plans_build(int B, int T, int bf16, int need_bwd, int ov
 extern "C" long long nele_disc_workspace_bytes(int B, int T, int cin, int bf16) {
     if (B <= 0 || T < 21 || cin < 1 || cin > 4) return -1;
     DWs w;
-    if (d_layout(B, T, cin, bf16 != 0, nullptr, w)) return -1;
+    if (d_layout(B, T, cin, prec_bf16(bf16), nullptr, w, prec_x3(bf16))) return -1;
     return (long long)w.bytes;
 }
 
 // device pointer of the input gradient [B][64][T][4] the backward plan writes (need_din), inside `workspace`
 extern "C" float* nele_disc_workspace_ddin(void* workspace, int B, int T, int cin, int bf16) {
     DWs w;
-    if (!workspace || B <= 0 || T < 21 || d_layout(B, T, cin, bf16 != 0, workspace, w)) return nullptr;
+    if (!workspace || B <= 0 || T < 21 || d_layout(B, T, cin, prec_bf16(bf16), workspace, w, prec_x3(bf16))) return nullptr;
     return reinterpret_cast<float*>(w.ddin.p);
 }
 
@@ -748,7 +805,7 @@ extern "C" float* nele_disc_workspace_ddin(void* workspace, int B, int T, int ci
 // "pooled" [B][64], "gbuf16" (the bf16 pooling gradient, bf16 mode), "ddin".  -> its device pointer and *elsize (2: bfloat16, 4: float32), or NULL where this layout has no such buffer.
 extern "C" void* nele_disc_workspace_buffer(void* workspace, int B, int T, int cin, int bf16, const char* name, int* elsize) {
     DWs w;
-    if (!workspace || !name || B <= 0 || T < 21 || d_layout(B, T, cin, bf16 != 0, workspace, w)) return nullptr;
+    if (!workspace || !name || B <= 0 || T < 21 || d_layout(B, T, cin, prec_bf16(bf16), workspace, w, prec_x3(bf16))) return nullptr;
     const Buf* b = nullptr;
     if (!strncmp(name, "act", 3) && name[3] >= '0' && name[3] <= '4' && !name[4]) b = &w.act[name[3] - '0'];
     else if (!strncmp(name, "gbuf", 4) && name[4] >= '0' && name[4] <= '4' && !name[5]) b = &w.gbuf[name[4] - '0'];

@@ -268,7 +268,7 @@ def main(argv=None):
     ap.add_argument('--noise', required=True)
     ap.add_argument('--output', default='./output_inference')
     ap.add_argument('--batch', type=int, default=32)
-    ap.add_argument('--precision', choices=('bf16', 'f32'), default='bf16')
+    ap.add_argument('--precision', choices=('bf16', 'bf16x3', 'f32'), default='bf16')
     ap.add_argument('--score', action='store_true', help='SIIB / HASPI / ESTOI (PESQ / ViSQOL when registered) of the written files')
     ap.add_argument('--groups', default='Cafeteria,AirportAnnouncement', help='noise types (substrings of the file names) reported separately; empty = all files together')
     from . import quality as _q

@@ -58,6 +58,15 @@ class cLN(nn.Module):
         self.bias0 = nn.Parameter(torch.zeros(1, dimension, 1), requires_grad=trainable)
 
 
+# precision string -> the library's precision code (NELE_PREC_*): 'bf16' 1, 'bf16x3' 2 (split-operand bf16 products, float32-grade), anything
+# else 0 (float32 operands)
+_PREC_CODES = {'bf16': 1, 'bf16x3': 2}
+
+
+def _prec_code(precision):
+    return _PREC_CODES.get(precision, 0)
+
+
 def _norm_dev(dev):
     """torch.device('cuda') != torch.device('cuda:0'): an index-less device would make every cache below look stale (and re-home the
     flat parameter buffer on every call).  Normalise to the indexed device."""
@@ -266,7 +275,8 @@ class Generator_Conv1D_cLN(nn.Module):
         self._wstream = None
         self.overlap_wgrad = True          # weight gradients on a second stream beside the data-gradient chain
         self._last_mask = None
-        self.precision = 'f32'            # 'bf16': bf16 MFMA operands (f32 accumulate) in the Conv1d / Linear GEMMs (fwd, dgrad, wgrad)
+        self.precision = 'f32'            # 'bf16': bf16 MFMA operands (f32 accumulate) in the Conv1d / Linear GEMMs (fwd, dgrad, wgrad);
+                                          # 'bf16x3': split-operand bf16 products in the Conv1d passes (float32-grade), Linear layers float32
         # Several forward passes in flight on different streams (inference.Enhancer.enhance_stream): each stream names its own workspace
         # through `buffer_slot`.  While the weights are frozen (freeze_weights) a workspace writes its weight layouts once, at its first
         # forward pass, instead of at the head of every forward pass.
@@ -309,7 +319,7 @@ class Generator_Conv1D_cLN(nn.Module):
         fl = self._flat
 
         def make():
-            b16 = int(self.precision == 'bf16')
+            b16 = _prec_code(self.precision)
             n = _lib.lib.nele_gen_workspace_bytes(B, T, b16, int(need_bwd))
             ws = _Workspace(n, dev, (fl.flat.data_ptr(), fl.grad.data_ptr()))
             prep, fwd = c_void_p(), c_void_p()
@@ -358,7 +368,7 @@ class Generator_Conv1D_cLN(nn.Module):
         plan = ws.plans.get(('bwd', overlap))
         if plan is None:
             fl, h = self._flat, c_void_p()
-            call('nele_gen_plans_build', B, T, int(self.precision == 'bf16'), 1, int(overlap), ptr(fl.flat), ptr(fl.grad), ptr(ws.buf), ws.buf.numel(), 0,
+            call('nele_gen_plans_build', B, T, _prec_code(self.precision), 1, int(overlap), ptr(fl.flat), ptr(fl.grad), ptr(ws.buf), ws.buf.numel(), 0,
                  stream(), None, None, ctypes.byref(h))
             plan = ws.add(('bwd', overlap), h)
         side = ()
@@ -444,7 +454,8 @@ class _DiscriminatorBase(nn.Module):
         self.overlap_wgrad = True          # weight gradients on two more streams beside the data-gradient chain
         self.profile_prefix = ''           # prepended to the ops.PROFILE name of this module's conv5 forward launches (bench.py)
         self.weight_grad_enabled = True   # reference computes (unused) D weight grads in the G-step too
-        self.precision = 'f32'            # 'bf16': bf16 MFMA operands (f32 accumulate) in the conv forward / data-gradient passes
+        self.precision = 'f32'            # 'bf16': bf16 MFMA operands (f32 accumulate) in the conv forward / data-gradient passes;
+                                          # 'bf16x3': split-operand bf16 products in the k > 1 conv passes (float32-grade)
 
     def flat_parameters(self, device=None):
         device = device or next(self.parameters()).device
@@ -470,7 +481,7 @@ class _DiscriminatorBase(nn.Module):
         owner = (fl.flat.data_ptr(), fl.grad.data_ptr()) + tuple(uv)
 
         def make():
-            b16 = int(self.precision == 'bf16')
+            b16 = _prec_code(self.precision)
             n = _lib.lib.nele_disc_workspace_bytes(B, T, self._cin, b16)
             if n < 0:
                 raise ValueError("Discriminator: T=%d is too short (needs T >= 21, model.py:105-109)" % T)
@@ -542,7 +553,8 @@ class _DiscriminatorBase(nn.Module):
         score = _empty((B, self._nout), dev)
         # padded batch of utterances of different lengths: the pooling runs over each utterance's own valid output columns (frames - 20)
         ws.wvalid = None if frames is None else (frames.to(device=dev, dtype=torch.int32) - 20).contiguous()
-        libtag = ('span_N%d_K%d' if self.precision == 'f32' else 'conv16_N%d_K%d_e2') % _D5_OUT
+        # the kernel that runs D.conv5's forward: the span kernel (float32), the split tile kernel (bf16x3), conv16 (bf16)
+        libtag = {'bf16': 'conv16_N%d_K%d_e2', 'bf16x3': 'tile16x3_N%d_K%d'}.get(self.precision, 'span_N%d_K%d') % _D5_OUT
         prof = _profiled(self.profile_prefix + 'D.conv5.fwd', libtag)
         call('nele_disc_fwd', c_void_p(ws.plans['fwd']), ptr(a), ptr(ws.wvalid), ptr(score), _streams(), 1)
         _collect(prof, libtag, 2.0 * B * 44 * (T - 20) * _D5_OUT[0] * _D5_OUT[1])
@@ -576,7 +588,7 @@ class _DiscriminatorBase(nn.Module):
         plan = ws.plans.get(form)
         if plan is None:                      # another backward form over the same workspace: built without zeroing it again
             fl, h = self._flat, c_void_p()
-            call('nele_disc_plans_build', B, T, self._cin, self._nout, int(self.precision == 'bf16'), int(need_din), int(wgrad), int(overlap), ptr(fl.flat),
+            call('nele_disc_plans_build', B, T, self._cin, self._nout, _prec_code(self.precision), int(need_din), int(wgrad), int(overlap), ptr(fl.flat),
                  ptr(fl.grad), self.sn_uv_host(), ptr(ws.buf), ws.buf.numel(), 0, stream(), None, None, ctypes.byref(h))
             plan = ws.add(form, h)
         side = ()

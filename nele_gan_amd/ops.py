@@ -24,6 +24,12 @@ _SIGS = {
     'nele_conv_wgrad_bf16_d16_supported': [c_int, c_int, ctypes.POINTER(c_int), c_int, c_int],
     'nele_conv_wgrad_bf16_d16': [_P, _P, _P, c_longlong, c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_int, _P, _P, c_int, _P],
     'nele_weight_prep_frag16': [_P, c_int, c_int, c_int, c_int, _P, _P],
+    'nele_weight_prep_frag16x3': [_P, c_int, c_int, c_int, c_int, _P, _P, _P],
+    'nele_weight_prep_frag16x3_batch': [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, _P],
+    'nele_conv_span_bf16x3_supported': [c_int, c_int, ctypes.POINTER(c_int), c_int, c_int],
+    'nele_conv_span_bf16x3': [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, ctypes.POINTER(c_int), c_int, c_int, c_longlong, _P],
+    'nele_conv_wgrad_bf16x3_supported': [c_int, c_int, ctypes.POINTER(c_int), c_int, c_int],
+    'nele_conv_wgrad_bf16x3': [_P, _P, _P, c_longlong, c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_int, _P, _P, c_int, _P],
     'nele_conv16_supported': [c_int, c_int, ctypes.POINTER(c_int), c_int, c_int],
     'nele_conv16_weight_prep_batch': [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, _P],
     'nele_conv16': [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, ctypes.POINTER(c_int), c_int, c_int, _P],

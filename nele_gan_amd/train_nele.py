@@ -1529,7 +1529,7 @@ def main(argv=None):
     ap.add_argument('--output', default='./output')
     ap.add_argument('--chkpt', default='./chkpt')
     ap.add_argument('--log', default='./log.txt')
-    ap.add_argument('--precision', choices=('bf16', 'f32'), default='bf16', help='MFMA operand precision of G and D (f32 = the reference\'s arithmetic)')
+    ap.add_argument('--precision', choices=('bf16', 'bf16x3', 'f32'), default='bf16', help='MFMA operand precision of G and D (f32 = the reference\'s arithmetic)')
     ap.add_argument('--valid-filter', default=None, help='keep validation files whose name contains this (train_nele.py:65: \'AIR_stairway\')')
     ap.add_argument('--resume', default=None, help='checkpoint to start from (train_nele.py:82-84)')
     ap.add_argument('--first-epoch', type=int, default=1)
