@@ -1,18 +1,23 @@
 #!/usr/bin/env python
 """Headline benchmark: utterances/s per GAN_epoch step (G + D + metric loss) on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
 
 One "step" = one canonical GAN_epoch step over one batch of synthetic utterances already
 resident in HBM: features(clean, noise) -> G-step (G fwd+bwd through D, Adam-G) -> generate (G eval,
 gain, iSTFT, PCM_16) -> true metrics (SIIB + HASPI + ESTOI, logistic maps) -> D-step (D fwd+bwd, Adam-D).
 Workload at N = 1 = BASELINE.json configs[2] (the largest single-GPU configuration): batch 256 synthetic
-4 s @ 16 kHz utterances, SIIB+HASPI+ESTOI multi-metric targets, bf16 MFMA operands.  The same JSON line
-carries two companions measured after the timed region: "configs1" (BASELINE configs[1]: batch 32,
-SIIB+ESTOI), "nonperiodic" (the headline workload at L = 63 871, no multiple of SIIB's 200-sample hop, so
-neither SIIB's frame-periodic shortcut nor its rank-deficient-component cut applies), "headline_f32" (float32 MFMA
-operands), "shard128" / "global1024" (the two ends of configs[3]'s strong-scaling ratio measured on one GPU).
+4 s @ 16 kHz utterances, SIIB+HASPI+ESTOI multi-metric targets, bf16 MFMA operands.
+A plain run does what the headline figure needs: set up, warm up, time the steps, check them, write --dump-outputs,
+print the line (with the per-kernel figures the library's event hook took inside the timed steps).  `--full` also
+runs everything measured beside it, after the timed region: the isolated D.conv5 launches, the inference path,
+the epoch mixes, the CPU baseline, the two-gradient all-reduce (N > 1) and the companions - "configs1" (BASELINE
+configs[1]: batch 32, SIIB+ESTOI), "nonperiodic" (the headline workload at L = 63 871, no multiple of SIIB's
+200-sample hop, so neither SIIB's frame-periodic shortcut nor its rank-deficient-component cut applies),
+"headline_f32" (float32 MFMA operands), "shard128" / "global1024" (the two ends of configs[3]'s strong-scaling
+ratio measured on one GPU).  Without --full, --companions, --cpu-utts, --inference and --epoch-equivalent
+default to off; given explicitly they hold in either mode.  --no-isolated drops the isolated launches from --full.
 Multi-GPU: utterances shard across ranks, one flat RCCL all-reduce of the G and of the D gradients
 per step.  `python bench.py --gpus N` with N > 1 and no RANK in the environment starts
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same arguments>` as a CHILD process
@@ -528,12 +533,16 @@ def main():
     ap.add_argument('--global-batch', type=int, default=0, metavar='G',
                     help='total utterances, split over the ranks (strong scaling; N > 1 default: 1024 = BASELINE configs[3]; overrides --batch)')
     ap.add_argument('--dry-run', action='store_true', help='CPU / gloo: launcher, sharding and collectives only, no kernels')
-    ap.add_argument('--no-isolated', action='store_true', help='skip the isolated D.conv5 forward launches after the timed region (profiling runs: '
+    ap.add_argument('--full', action='store_true', help='after the timed region, also run every measurement beside the headline figure: the isolated '
+                                                         'D.conv5 launches, the companions, the inference path, the epoch mixes, the CPU baseline and (N > 1) '
+                                                         'the all-reduce alone; a plain run times the headline steps only')
+    ap.add_argument('--no-isolated', action='store_true', help='with --full: skip the isolated D.conv5 forward launches after the timed region (profiling runs: '
                                                                  'the kernel statistics then hold the step\'s own launches only)')
     ap.add_argument('--length', type=int, default=64000)
     ap.add_argument('--metrics', default='siib&haspi&estoi')
-    ap.add_argument('--companions', type=int, default=1, help='also run the configs[1] and non-periodic-length companions (N = 1 only; 0 = skip)')
-    ap.add_argument('--cpu-utts', type=int, default=32, help='utterances in the CPU-baseline sample (0 = skip)')
+    ap.add_argument('--companions', type=int, default=None, help='also run the configs[1] and non-periodic-length companions (N = 1 only; 0 = skip; '
+                                                                  'default 1 with --full, else 0)')
+    ap.add_argument('--cpu-utts', type=int, default=None, help='utterances in the CPU-baseline sample (0 = skip; default 32 with --full, else 0)')
     ap.add_argument('--breakdown', action='store_true', help='per-stage timing to stderr')
     ap.add_argument('--inference', type=int, default=-1, metavar='K',
                     help='also time K batches of the inference path (BASELINE configs[4]: 8 s utterances, features -> G -> resynthesis -> RMS 0.03 -> PCM_16); reported as "inference"')
@@ -564,6 +573,11 @@ def main():
             a.batch = 256
     if a.global_batch > 0:
         a.scaling = 'strong'
+    if a.companions is None:
+        a.companions = int(a.full)
+    if a.cpu_utts is None:
+        a.cpu_utts = 32 if a.full else 0
+    a.isolated = a.full and not a.no_isolated
     companions_default = world == 1 and a.batch == 256 and a.length == 64000 and a.metrics == 'siib&haspi&estoi'
     if a.inference < 0:
         a.inference = 10 if (companions_default and a.companions) else 0
@@ -719,7 +733,7 @@ def main():
     ops.PROFILE = None if lib_tags else {iso_tag: []}
     torch.cuda.synchronize()
     iso = []
-    if not a.no_isolated:            # profiling runs switch this off: the per-step kernel sums must hold the step's own launches only
+    if a.isolated:                   # --full only; profiling runs switch it off: the per-step kernel sums must hold the step's own launches only
         tr.D.eval()
         tr.D.profile_prefix = 'iso.'
         if lib_tags:
@@ -735,7 +749,7 @@ def main():
     ops.PROFILE = None
     # the step's two gradient all-reduces (G 8.37 MB, D 1.37 MB) alone, after the timed region: what a step pays for them at most
     allreduce_ms = None
-    if world > 1:
+    if world > 1 and a.full:
         gg, gd = tr.G.flat_parameters().grad, tr.D.flat_parameters().grad
         for _ in range(3):
             ndist.allreduce_mean_(gg); ndist.allreduce_mean_(gd)
@@ -767,7 +781,7 @@ def main():
         traffic = pmc.get(ckey, {}).get('hbm_bytes_corrected')
         kernel_ms = sum(e0.elapsed_time(e1) for e0, e1, _ in prof) / max(1, len(prof))
         flops = prof[0][2] if prof else 0.0
-        iso_ms = sum(e0.elapsed_time(e1) for e0, e1, _ in iso) / max(1, len(iso))
+        iso_ms = sum(e0.elapsed_time(e1) for e0, e1, _ in iso) / len(iso) if iso else None      # None: not measured (plain run, --no-isolated)
         peak = BF16_MFMA_PEAK_TFLOPS if a.precision == 'bf16' else F32_MFMA_PEAK_TFLOPS
         achieved = flops / (kernel_ms * 1e-3) / 1e12 if kernel_ms > 0 else 0.0
         out = {
@@ -788,8 +802,8 @@ def main():
                          'traffic': traffic, 'mfma_busy_frac': pmc.get(ckey, {}).get('mfma_busy_frac'), 'launch_ms': kernel_ms,
                          'launch_ms_gstep': sum(e0.elapsed_time(e1) for e0, e1, _ in prof_g) / max(1, len(prof_g)),   # beside the half-GPU tridiagonalisation
                          'launch_ms_dstep': sum(e0.elapsed_time(e1) for e0, e1, _ in prof_d) / max(1, len(prof_d)),
-                         'isolated_launch_ms': iso_ms, 'achieved_isolated': (flops / (iso_ms * 1e-3) / 1e12 if iso_ms > 0 else 0.0),
-                         'frac_isolated': (flops / (iso_ms * 1e-3) / 1e12 / peak if iso_ms > 0 else 0.0), 'launches_timed': len(prof), 'flops_per_launch': flops,
+                         'isolated_launch_ms': iso_ms, 'achieved_isolated': (flops / (iso_ms * 1e-3) / 1e12 if iso_ms else None),
+                         'frac_isolated': (flops / (iso_ms * 1e-3) / 1e12 / peak if iso_ms else None), 'launches_timed': len(prof), 'flops_per_launch': flops,
                          'pmc_source': pmc_note},
             'ranks_seen': ranks_seen,
             'host_cpus_bound': (len(numa_cpus) if numa_cpus else None),     # CPUs of the GPU's NUMA node this process was restricted to (None: unbound)

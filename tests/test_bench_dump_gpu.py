@@ -1,6 +1,6 @@
 """GPU: `bench.py --dump-outputs DIR` writes what the last timed step computed (losses, targets, a seeded sample of the enhanced
 signals, the updated weights) as float32 .npy files, `--steps` sets the number of timed steps, and two runs with the same arguments
-(seeded inputs, same initial weights) write the same arrays."""
+(seeded inputs, same initial weights) write the same arrays; a run without `--full` measures nothing beside the timed steps."""
 import json
 import os
 import subprocess
@@ -15,14 +15,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 B, L = 4, 24000
 
 
-def _bench(out_dir, steps):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', '1',
-                        '--batch', str(B), '--length', str(L), '--companions', '0', '--cpu-utts', '0', '--no-isolated',
-                        '--dump-outputs', str(out_dir)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+def _run(args):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--batch', str(B), '--length', str(L)] + args,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
     assert len(lines) == 1
     return json.loads(lines[0])
+
+
+def _bench(out_dir, steps):
+    return _run(['--steps', str(steps), '--warmup', '1', '--companions', '0', '--cpu-utts', '0', '--no-isolated', '--dump-outputs', str(out_dir)])
 
 
 def test_dump_outputs_of_the_last_timed_step_are_reproducible(tmp_path):
@@ -40,3 +43,13 @@ def test_dump_outputs_of_the_last_timed_step_are_reproducible(tmp_path):
     assert b['dumped_outputs']['enhanced_rows'] == a['dumped_outputs']['enhanced_rows']
     for n in names:
         assert np.array_equal(np.load(tmp_path / 'b' / (n + '.npy')), arr[n]), n
+
+
+def test_a_plain_run_measures_the_timed_steps_only():
+    """Without --full nothing is measured after the timed steps: no CPU baseline, no companions, no isolated D.conv5 launches - the line
+    holds the headline figure and what the library's event hook took inside the timed steps."""
+    out = _run(['--steps', '2', '--warmup', '1'])
+    assert out['steps'] == 2 and out['warmup'] == 1 and out['ms_per_step'] > 0 and out['value'] > 0
+    assert out['unit'] == 'utterances/s' and out['higher_is_better'] is True and out['dtype'] == 'bf16'
+    assert not {'cpu_baseline', 'configs1', 'nonperiodic', 'headline_f32', 'inference', 'epoch_equivalent', 'allreduce_ms_per_step'} & set(out)
+    assert out['roofline_mfma']['isolated_launch_ms'] is None
