@@ -132,7 +132,7 @@ int nele_gen_plans_build(int B, int T, int bf16, int need_bwd, int overlap_wgrad
 int nele_disc_plans_build(int B, int T, int cin, int nout, int bf16, int need_din, int weight_grads, int overlap_wgrad, const float* params_flat,
                           float* grads_flat, const void* const* sn_uv_host, void* workspace, long long workspace_bytes, int zero_fill, void* stream,
                           void** prep_out, void** fwd_out, void** bwd_out);
-/* One buffer of a discriminator workspace (tests): "act0".."act4", "gbuf0".."gbuf4", "pooled", "gbuf16", "ddin" -> device pointer and *elsize (2: bfloat16,
+/* One buffer of a discriminator workspace (tests): "act0".."act4", "gbuf0".."gbuf4", "pooled", "gbuf16", "ddin", "sigma" (float32 [8]) -> device pointer and *elsize (2: bfloat16,
  * 4: float32), or NULL where the layout of this shape / precision has no such buffer. */
 void* nele_disc_workspace_buffer(void* workspace, int B, int T, int cin, int bf16, const char* name, int* elsize);
 /* Hand-over events between the streams of a pass (hipEvent, timing disabled), recordable as plan operations */

@@ -802,7 +802,7 @@ extern "C" float* nele_disc_workspace_ddin(void* workspace, int B, int T, int ci
 }
 
 // One buffer of a discriminator workspace (tests): "act0".."act4" (layer outputs), "gbuf0".."gbuf4" (their zero-bordered gradients),
-// "pooled" [B][64], "gbuf16" (the bf16 pooling gradient, bf16 mode), "ddin".  -> its device pointer and *elsize (2: bfloat16, 4: float32), or NULL where this layout has no such buffer.
+// "pooled" [B][64], "gbuf16" (the bf16 pooling gradient, bf16 mode), "ddin", "sigma" (float32 [8]: the spectral norms of the eight layers).  -> its device pointer and *elsize (2: bfloat16, 4: float32), or NULL where this layout has no such buffer.
 extern "C" void* nele_disc_workspace_buffer(void* workspace, int B, int T, int cin, int bf16, const char* name, int* elsize) {
     DWs w;
     if (!workspace || !name || B <= 0 || T < 21 || d_layout(B, T, cin, prec_bf16(bf16), workspace, w, prec_x3(bf16))) return nullptr;
@@ -812,6 +812,7 @@ extern "C" void* nele_disc_workspace_buffer(void* workspace, int B, int T, int c
     else if (!strcmp(name, "pooled")) b = &w.pooled;
     else if (!strcmp(name, "gbuf16")) b = &w.gbuf16;
     else if (!strcmp(name, "ddin")) b = &w.ddin;
+    else if (!strcmp(name, "sigma")) b = &w.sigma;
     if (!b || !b->p) return nullptr;
     if (elsize) *elsize = b->b16 ? 2 : 4;
     return b->p;
