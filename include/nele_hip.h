@@ -497,7 +497,18 @@ int nele_metric_siib_var(const float* x, const float* y, const int* lengths, int
 
 /* Batched symmetric eigen-decomposition, float64, n <= 512 (np.linalg.eigh in pysiib's KLT): A [B][n][n] symmetric
  * (destroyed) -> lam [B][n] ascending, U [B][n][n] with ROW j = eigenvector j.  Householder tridiagonalisation,
- * Sturm bisection, inverse iteration, back-transformation (csrc/eigh.hip). */
+ * Sturm bisection, inverse iteration, back-transformation (csrc/eigh.hip).
+ * Contract (tests/eigh_contract.py; tests/test_eigh_gpu.py).  eps = 2^-52, ||A|| = max |lambda|, N = max(n, 16); finite symmetric inputs
+ * with n in 2 .. 512 and max |a_ij| in [1e-100, 1e100] (or A = 0).  A GROUP is a maximal run of eigenvalues whose consecutive gaps are
+ * <= tau ||A||, tau = 1e-10 (no component SIIB keeps falls into one; a periodic utterance's null space is one).  For every j:
+ *   lam ascending, |lam_j - lam_j^LAPACK| <= N eps ||A||, ||A u_j - lam_j u_j||_2 <= N eps ||A||, | ||u_j||_2 - 1 | <= N eps
+ *   (one named allowance: 1.125 N eps ||A|| for both when lam_j is in a group - bisection leaves a 420-fold eigenvalue 1.0625 N eps off);
+ *   outside groups |u_i . u_j| <= C_o eps ||A|| / |lam_i - lam_j| + 4 N eps with C_o = 0.375 (4x the largest ratio measured);
+ *   inside a group |u_i . u_j| <= 4 N eps;  every output finite (A = 0: lam = 0, U orthogonal).
+ * NOT MET YET for the members of a group (tests/test_eigh_gpu.py: strict xfails per class): their vectors are an arbitrary, non-orthogonal
+ * basis of the group's eigenspace (|u_i . u_j| up to O(1)), and equal eigenvalues may be an ulp out of order.  A caller that uses such
+ * vectors must orthogonalise them itself.
+ * Refused (status returned, nothing written): n < 2, n > 512, a workspace below nele_eigh_workspace_bytes, U == A, NULL pointers. */
 long long nele_eigh_workspace_bytes(int B, int n);
 int nele_eigh_sym_batched(double* A, int n, int B, double* lam, double* U, void* workspace, long long workspace_bytes,
                           void* stream);

@@ -10,10 +10,14 @@
 //       threads of a wave touch one coalesced row per step)
 //   e4  back-transformation with the Householder reflectors, a slab of 30 eigenvectors per workgroup held in LDS
 //
-// Close eigenvalues are separated by dstein's perturbation (10 eps |lambda|); vectors are NOT re-orthogonalised
-// against each other: for spectra without (numerically) repeated eigenvalues inverse iteration already delivers
-// eigenvectors orthogonal to ~eps ||T|| / gap, and for repeated eigenvalues the individual vectors are arbitrary in any
-// solver (SIIB drops the only systematic such cluster, the rank-deficient null space, by its eigenvalue tolerance).
+// Contract (include/nele_hip.h at nele_eigh_sym_batched; checked by tests/eigh_contract.py and tests/test_eigh_gpu.py): with
+// N = max(n, 16) and ||A|| = max |lambda|, eigenvalues within N eps ||A|| of LAPACK's, residuals <= N eps ||A||, norms 1 to N eps, vectors
+// outside groups (runs of eigenvalues with gaps <= 1e-10 ||A||) orthogonal to 0.375 eps ||A|| / gap + 4 N eps.  Close eigenvalues are
+// separated by dstein's perturbation (10 eps |lambda|) and vectors are NOT re-orthogonalised against each other, so INSIDE a group the
+// vectors are an arbitrary, non-orthogonal basis of the eigenspace (measured |u_i . u_j| up to O(1)) and equal eigenvalues may be an ulp
+// out of order: the contract's in-group clauses are not met yet.  SIIB drops the only systematic group, the null space of a periodic
+// utterance's covariance, by its eigenvalue tolerance.  A tridiagonal matrix whose largest entry lies outside [2^-20, 2^20] is scaled by a
+// power of two before the bisection (eigh_prescale_kernel).
 #include "common.h"
 #include <cstdlib>
 
@@ -30,6 +34,7 @@ struct EighWs {
     double* lu;     // [B][6][(n+2)/2][EG_MAXN][2]
     int* pin;       // [B][n][EG_MAXN]
     uint4* xch;     // [B][2][2][EG_MAXN] cluster tridiagonalisation: tagged exchange slots (zeroed per call)
+    double* scl;    // [B] eigenvalue scale of matrix b: 2^k when eigh_prescale_kernel scaled T by 2^-k, 0 for T = 0
     int* flag;      // [B + 1] cluster tridiagonalisation gave up on matrix b (its workgroups were not co-resident within the spin limit):
                     //         the single-workgroup kernels skip it and eigh_tridiag_repair_kernel redoes it; [B] = matrices repaired (zeroed per call)
 };
@@ -2101,6 +2106,10 @@ __global__ __launch_bounds__(64) void eigh_invit_kernel(int n, EighWs ws, const 
     double onenrm = fabs(d[0]) + (n > 1 ? fabs(e[0]) : 0.0);
     if (n > 1) onenrm = fmax(onenrm, fabs(d[n - 1]) + fabs(e[n - 2]));
     for (int i = 1; i < n - 1; ++i) onenrm = fmax(onenrm, fabs(d[i]) + fabs(e[i - 1]) + fabs(e[i]));
+    if (onenrm == 0.0) {
+        for (int i = 0; i < n; ++i) z[(size_t)i * EG_MAXN] = (i == j) ? 1.0 : 0.0;
+        return;
+    }
     const double dtpcrt = sqrt(0.1 / (double)n);
     // ---- start vector: deterministic pseudo-random in (-1, 1), never stored.  The first forward elimination rides inside the
     // factorisation below (its multiplier and interchange of step k are at hand the moment they are computed) on the UNSCALED vector -
@@ -2360,6 +2369,10 @@ __global__ __launch_bounds__(64, IV2_OCC) void eigh_invit2_kernel(int n, EighWs 
     double onenrm = fabs(d[0]) + (n > 1 ? fabs(e[0]) : 0.0);
     if (n > 1) onenrm = fmax(onenrm, fabs(d[n - 1]) + fabs(e[n - 2]));
     for (int i = 1; i < n - 1; ++i) onenrm = fmax(onenrm, fabs(d[i]) + fabs(e[i - 1]) + fabs(e[i]));
+    if (onenrm == 0.0) {                       // T = 0 (A = 0): the start vector would be scaled to zero and normalised by 1 / sqrt(0)
+        for (int i = 0; i < n; ++i) z[(size_t)i * EG_MAXN] = (i == j) ? 1.0 : 0.0;
+        return;
+    }
     const double dtpcrt = sqrt(0.1 / (double)n);
     const unsigned int rs0 = 0x9E3779B9u * (unsigned)(j + 1) + 12345u;
     auto lcg = [](unsigned int& rs) {
@@ -2851,6 +2864,45 @@ __global__ __launch_bounds__(256, 1) void eigh_backtransform_wy_kernel(const dou
         }
 }
 
+// ------------------------------------------------------------------------------------------ scaling of T
+// The Sturm recurrence rescales its running pair once per eight steps and assumes a step grows it by < 1e8: entries far from 1 (A 1e+-100)
+// break that and the counts.  Like dsyev's scaling step this multiplies by a power of two (exact), but it acts on T, not on A, and with its
+// own window: a tridiagonal matrix whose largest entry lies outside [2^-20, 2^20] is scaled to [1, 2) before the bisection, and its
+// eigenvalues are scaled back once the inverse iteration has used them as shifts (the eigenvectors do not change).  Every other matrix is
+// left alone (scale 1: bit-identical results).  T = 0 (A = 0) gets scale 0: eigenvalues exactly 0.  Scaling down can flush entries of T more
+// than 2^1000 below its largest to zero, which moves eigenvalues by far less than eps ||T||.  The Householder reduction itself is safe over
+// the contract's range (squares of 1e+-100 entries stay normal), and T is 2n values where A is n^2: scaling T costs microseconds.
+#define EG_SCALE_LO 0x1p-20
+#define EG_SCALE_HI 0x1p+20
+__global__ __launch_bounds__(256) void eigh_prescale_kernel(int n, EighWs ws) {
+    __shared__ double red[8];
+    const int b = blockIdx.x;
+    double* d = ws.d + (size_t)b * n;
+    double* e = ws.e + (size_t)b * n;
+    double m = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) m = fmax(m, fmax(fabs(d[i]), (i < n - 1) ? fabs(e[i]) : 0.0));
+    m = block_max(m, red);
+    double back = 1.0;
+    if (m == 0.0) back = 0.0;
+    else if (m < EG_SCALE_LO || m > EG_SCALE_HI) {
+        const int k = ilogb(m);                            // m in [2^k, 2^(k+1))
+        const double f = ldexp(1.0, -k);
+        for (int i = threadIdx.x; i < n; i += 256) {
+            d[i] *= f;
+            if (i < n - 1) e[i] *= f;
+        }
+        back = ldexp(1.0, k);
+    }
+    if (threadIdx.x == 0) ws.scl[b] = back;
+}
+
+__global__ __launch_bounds__(256) void eigh_postscale_kernel(int n, EighWs ws, double* __restrict__ lam) {
+    const int b = blockIdx.x;
+    const double back = ws.scl[b];
+    if (back == 1.0) return;
+    for (int j = threadIdx.x; j < n; j += 256) lam[(size_t)b * n + j] *= back;
+}
+
 // ------------------------------------------------------------------------------------------ C ABI
 static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
@@ -2865,6 +2917,7 @@ static size_t eigh_layout(int B, int n, EighWs* w, char* base) {
     TAKE(lu, double, (size_t)B * 6 * (n + 2) * EG_MAXN);
     TAKE(pin, int, (size_t)B * n * EG_MAXN);
     TAKE(xch, uint4, (size_t)B * EG_XCH * EG_MAXN);
+    TAKE(scl, double, (size_t)B);
     TAKE(flag, int, (size_t)B + 64);
 #undef TAKE
     return o;
@@ -3028,6 +3081,7 @@ int nele_eigh_sym_batched_ex(double* A, int n, int B, double* lam, double* U, vo
     } else {
         hipLaunchKernelGGL(eigh_tridiag_kernel, dim3(B), dim3(1024), 0, s, A, n, ws);
     }
+    hipLaunchKernelGGL(eigh_prescale_kernel, dim3(B), dim3(256), 0, s, n, ws);
     hipLaunchKernelGGL(eigh_sde_kernel, dim3(B), dim3(256), 0, s, n, ws);
     hipLaunchKernelGGL(eigh_bisect_kernel, dim3((n + 256 / EG_NL - 1) / (256 / EG_NL), B), dim3(256), 0, s, n, ws, lam);
     // sweeps after the growth criterion is met: LAPACK's dstein uses EXTRA = 2 and documents "should be at least 1"; with the eigenvalues
@@ -3037,6 +3091,7 @@ int nele_eigh_sym_batched_ex(double* A, int n, int B, double* lam, double* U, vo
     // NELE_EIGH_INVIT_STORE=1 (test library): the kernel that stores the LU factors instead of recomputing them (bit-identical; 6.2 GB per 256 matrices)
     if (NELE_SWITCH_INT("NELE_EIGH_INVIT_STORE", 0)) { NELE_AB_ONLY(hipLaunchKernelGGL(eigh_invit_kernel, dim3((n + 63) / 64, B), dim3(64), 0, s, n, ws, lam, iv_extra);) }
     else hipLaunchKernelGGL(eigh_invit2_kernel, dim3((n + 63) / 64, B), dim3(64), 0, s, n, ws, lam, iv_extra);
+    hipLaunchKernelGGL(eigh_postscale_kernel, dim3(B), dim3(256), 0, s, n, ws, lam);
     const size_t lds = sizeof(double) * (2 * (size_t)BT_CH * 16 * (n <= 448 ? 28 : 32) + 2 * BT_CH);
     const int wy_on = NELE_SWITCH_INT("NELE_EIGH_WY", 1);   // =0: the reflector-by-reflector back-transformation (A/B diagnostic)
     NELE_ONCE_PER_DEVICE({

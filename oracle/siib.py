@@ -71,10 +71,8 @@ def stack(X, K):
     return np.concatenate([X[:, k:k + cols] for k in range(K)], axis=0)   # row index = k*J + j
 
 
-def siib_gauss(x, y, fs=FS, return_parts=False):
-    x = np.asarray(x, dtype=np.float64)
-    y = np.asarray(y, dtype=np.float64)
-    assert fs == FS and x.shape == y.shape and x.ndim == 1
+def _stacked(x, y):
+    """Stacked, mean-free log-band frames (420 x frames) of the clean and the degraded signal."""
     xh = intel.stft(x).T
     yh = intel.stft(y).T
     xh = xh.real ** 2 + xh.imag ** 2
@@ -95,6 +93,24 @@ def siib_gauss(x, y, fs=FS, return_parts=False):
     Ys = stack(Y, K_STACK)
     Xs = Xs - Xs.mean(axis=1, keepdims=True)
     Ys = Ys - Ys.mean(axis=1, keepdims=True)
+    return Xs, Ys, vad
+
+
+def klt_covariance(x, fs=FS):
+    """The clean covariance whose eigenvectors are SIIB's KLT basis (420 x 420 float64), after the wrapper's replication."""
+    x = np.asarray(x, dtype=np.float64)
+    M, _ = intel.siib_replication(x, fs)
+    if M > 1:
+        x = np.hstack([x] * M)
+    Xs, _, _ = _stacked(x, x)
+    return Xs @ Xs.T / (Xs.shape[1] - 1)
+
+
+def siib_gauss(x, y, fs=FS, return_parts=False):
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    assert fs == FS and x.shape == y.shape and x.ndim == 1
+    Xs, Ys, vad = _stacked(x, y)
     n = Xs.shape[1]
     Cxx = Xs @ Xs.T / (n - 1)
     lam, U = np.linalg.eigh(Cxx)
