@@ -587,6 +587,35 @@ int nele_fir_filter(const float* x, int B, int L, const double* h, int Lh, doubl
 int nele_norm_clip(const double* a64, const float* a32, const float* add, int B, int N, double target_rms, float* out, double* out64,
                    int* nclip, void* stream);
 
+/* ---- real-time enhancement (csrc/realtime.hip) ------------------------------------------------------------------------------------
+ * The offline chain (STFT, band features, IMCRA, Generator_Conv1D_cLN, resynthesis) run causally, one 256-sample hop of up to
+ * max_streams independent streams at a time (DESIGN.md "Real-time enhancement").  `state` (nele_rt_state_bytes(max_streams) bytes,
+ * 256-byte aligned) holds the weight layouts and one record per stream slot; nele_rt_init writes the layouts of params_flat (the
+ * generator's flat parameters in nele_gen_param_layout order) and clears every slot; nele_rt_set_weights rewrites only the layouts.
+ * precision: NELE_PREC_F32 or NELE_PREC_BF16 (the same value in every call on one state).
+ * nele_rt_hop: clean / noise [max_streams][nh * 256] float32, hop h of the call in columns [256 h, 256 h + 256); active [max_streams]
+ * (bytes, NULL = all): inactive slots are neither read nor changed.  out [max_streams][nh * 256]: a slot's hop m (counted from its
+ * start) yields output hop m - 1 in the same columns; a slot's first hop yields zeros; inactive slots' columns are left as they were.
+ * beta2 [max_streams]: fixed energy gain beta^2 per slot (alpha^2 = beta^2 mask), or NULL: prefix normalisation
+ * (alpha^2[t] = mask[t] sum_{t' <= t} P / sum_{t' <= t} mask P, P = clean band ** 6).  dbg_* [max_streams][dbg_frames][64] (each may be
+ * NULL): clean band ** 1/6, noise band ** 1/6, mask, alpha^2 of every frame computed, at the frame's index (frames >= dbg_frames are
+ * not written).
+ * nele_rt_finish: for the slots with tail_lengths[b] in 0 .. 255 (and at least 2 hops received; others: tail_lengths[b] < 0), the last
+ * tail_lengths[b] samples (clean_tail / noise_tail [max_streams][256]) end the stream: out [max_streams][256] receives its last output
+ * hop (from the end-reflected last frame), after which the slot ignores hops until nele_rt_reset.
+ * nele_rt_reset: clears the slots with slots[b] != 0 (NULL = all): a fresh stream starts there. */
+long long nele_rt_state_bytes(int max_streams);
+long long nele_rt_stream_record_bytes(void);
+int nele_rt_init(void* state, long long state_bytes, int max_streams, const float* params_flat, int precision, void* stream);
+int nele_rt_set_weights(void* state, long long state_bytes, int max_streams, const float* params_flat, int precision, void* stream);
+int nele_rt_reset(void* state, long long state_bytes, int max_streams, const unsigned char* slots, void* stream);
+int nele_rt_hop(void* state, long long state_bytes, int max_streams, int precision, const float* clean, const float* noise,
+                const unsigned char* active, int nh, const float* beta2, float* out, float* dbg_band, float* dbg_noise, float* dbg_mask,
+                float* dbg_alpha2, int dbg_frames, void* stream);
+int nele_rt_finish(void* state, long long state_bytes, int max_streams, int precision, const float* clean_tail, const float* noise_tail,
+                   const int* tail_lengths, const float* beta2, float* out, float* dbg_band, float* dbg_noise, float* dbg_mask,
+                   float* dbg_alpha2, int dbg_frames, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -124,6 +124,21 @@ lib.nele_disc_workspace_ddin.argtypes = _SIGS['nele_disc_workspace_ddin']
 lib.nele_disc_workspace_ddin.restype = c_void_p
 lib.nele_disc_workspace_buffer.argtypes = _SIGS['nele_disc_workspace_buffer']
 lib.nele_disc_workspace_buffer.restype = c_void_p
+# real-time enhancement (csrc/realtime.hip, nele_gan_amd/realtime.py)
+_RT_DBG = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]
+_SIGS.update({
+    'nele_rt_init': [c_void_p, c_longlong, c_int, c_void_p, c_int, c_void_p],
+    'nele_rt_set_weights': [c_void_p, c_longlong, c_int, c_void_p, c_int, c_void_p],
+    'nele_rt_reset': [c_void_p, c_longlong, c_int, c_void_p, c_void_p],
+    'nele_rt_hop': [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p] + _RT_DBG,
+    'nele_rt_finish': [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + _RT_DBG,
+})
+for _n in ('nele_rt_init', 'nele_rt_set_weights', 'nele_rt_reset', 'nele_rt_hop', 'nele_rt_finish'):
+    declare(_n, _SIGS[_n])
+for _n, _a in (('nele_rt_state_bytes', [c_int]), ('nele_rt_stream_record_bytes', [])):
+    getattr(lib, _n).argtypes = _a
+    getattr(lib, _n).restype = c_longlong
+    _SIGS[_n] = _a
 lib.nele_imcra_workspace_bytes.restype = c_longlong
 lib.nele_wav_post_workspace_doubles.argtypes = [c_int, c_int]
 lib.nele_wav_post_workspace_doubles.restype = c_longlong
