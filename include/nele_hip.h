@@ -389,6 +389,17 @@ int nele_energy_norm_fwd(const float* clean, const float* mask, const float* noi
 /* Gradient w.r.t. the mask given d(din).  din = the forward pass's output (may be NULL: the enhanced band is then recomputed). */
 int nele_energy_norm_bwd(const float* clean, const float* mask, const float* beta2, const float* s2, const float* ddin, const float* din,
                          float p, float inv_p, float* dmask, int B, int T, void* stream);
+/* The causal (prefix) form of train_nele.py:133-140 / inference.py:99-104, what the real-time path emits:
+ * S1[t] / S2[t] = sums of clean^inv_p / mask*clean^inv_p over the bands of frames <= t (float64, frames added in order);
+ * ratio [B][T] = S2[t] > 0 ? S1[t] / S2[t] : 1 (float32), s2 [B][T] = S2[t] (float64: the backward pass reads both);
+ * din = (clean*mask^p*ratio[t]^p, noise, clean, 0) (may be NULL; needs noise), alpha2 = mask*ratio[t] (may be NULL): bit-identical to
+ * the alpha^2 of nele_rt_hop on bit-equal band features and mask.  Layouts as nele_energy_norm_fwd; no allocation, one launch. */
+int nele_energy_norm_prefix_fwd(const float* clean, const float* mask, const float* noise, float p, float inv_p, float* ratio,
+                                double* s2, float* din, float* alpha2, int B, int T, void* stream);
+/* Gradient w.r.t. the mask given d(din): dmask[t,c] = dE clean p mask^(p-1) ratio[t]^p - K[t] clean^inv_p with the suffix sum
+ * K[t] = sum_{t'' >= t} (sum_c dE clean mask^p)[t''] p ratio[t'']^p / S2[t''] (terms with S2 <= 0 are zero).  din as above. */
+int nele_energy_norm_prefix_bwd(const float* clean, const float* mask, const float* ratio, const double* s2, const float* ddin,
+                                const float* din, float p, float inv_p, float* dmask, int B, int T, void* stream);
 
 /* dataloader.py:76-84: band features (enhanced, noise, clean) [B][T][64] -> D input [B][64][T][4]
  * (c2 NULL for Discriminator_Quality's (enhanced, clean)). */

@@ -28,11 +28,21 @@ fs = 16000
 
 
 class Enhancer:
-    def __init__(self, chkpt_path=None, device='cuda', G=None):
+    def __init__(self, chkpt_path=None, device='cuda', G=None, norm=None):
+        """norm: the energy normalisation of mask -> alpha^2 - 'utterance' (inference.py:99-104: sums over the whole utterance) or
+        'prefix' (sums over the frames up to each frame: what realtime.RealtimeEnhancer emits; train with
+        GanTrainer(norm='prefix')).  None: what the checkpoint records ('enhance-norm'), else 'utterance'.  The final
+        enh / rms(enh) * 0.03 and PCM_16 are the same in both modes."""
+        if norm is not None:
+            M.check_norm(norm, 'Enhancer')
         self.device = M._norm_dev(device)
         self.G = G if G is not None else M.Generator_Conv1D_cLN()
+        recorded = 'utterance'
         if chkpt_path is not None:
-            self.G.load_state_dict(torch.load(chkpt_path, map_location='cpu')['enhance-model'])   # inference.py:71-72
+            ck = torch.load(chkpt_path, map_location='cpu')
+            self.G.load_state_dict(ck['enhance-model'])                                           # inference.py:71-72
+            recorded = M.check_norm(ck.get('enhance-norm', 'utterance'), 'Enhancer (checkpoint)')
+        self.norm = recorded if norm is None else norm
         self.G = self.G.to(self.device)
         self.G.eval()
         # An Enhancer that owns its generator (loaded from a checkpoint, never trained through this object) writes the weight layouts once and
@@ -42,7 +52,7 @@ class Enhancer:
         self._frozen_precision = None
         self._slots = []                # streams of enhance_stream, created on first use and kept (the runtime maps streams to hardware queues once)
 
-    def _enhance_impl(self, clean_wav, noise_wav, pcm16, lengths):
+    def _enhance_impl(self, clean_wav, noise_wav, pcm16, lengths, rms_target=0.030):
         if self._own_G and not torch.cuda.is_current_stream_capturing() and (not self.G._weights_frozen or self._frozen_precision != self.G.precision):
             torch.cuda.current_stream(self.device).wait_event(self.G.freeze_weights(self.device))
             self._frozen_precision = self.G.precision
@@ -51,15 +61,16 @@ class Enhancer:
         clean_spec, clean_band = au.stft_band(clean_wav, p_power, lengths=lengths)
         noise_band = au.noise_band(noise_wav, p_power, lengths=lengths, frames=frames)
         mask = self.G(clean_band, noise_band)
-        alpha2 = M.normed_alpha2(mask, clean_band, inv_p, frames=frames)
-        return au.gain_istft(alpha2, clean_spec, rms_target=0.030, pcm16=pcm16, frames=frames)
+        alpha2 = M.normed_alpha2(mask, clean_band, inv_p, frames=frames, norm=self.norm)
+        return au.gain_istft(alpha2, clean_spec, rms_target=rms_target, pcm16=pcm16, frames=frames)
 
     @torch.no_grad()
-    def enhance(self, clean_wav, noise_wav, pcm16=True, lengths=None):
+    def enhance(self, clean_wav, noise_wav, pcm16=True, lengths=None, rms_target=0.030):
         """clean_wav, noise_wav [B,L] -> enhanced wav [B, 256*(T-1)] at RMS 0.03 (inference.py:99-115).
         lengths [B] (optional): samples of each utterance inside the padded batch; row b of the result then holds
-        256 * (lengths[b] // 256) samples followed by zeros, and its RMS is taken over those samples."""
-        return self._enhance_impl(clean_wav, noise_wav, pcm16, lengths)
+        256 * (lengths[b] // 256) samples followed by zeros, and its RMS is taken over those samples.
+        rms_target = 0: no final gain (with norm='prefix' and pcm16=False: the signal the real-time path emits)."""
+        return self._enhance_impl(clean_wav, noise_wav, pcm16, lengths, rms_target)
 
     @torch.no_grad()
     def enhance_stream(self, batches, inflight=4, pcm16=True):
@@ -269,13 +280,14 @@ def main(argv=None):
     ap.add_argument('--output', default='./output_inference')
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--precision', choices=('bf16', 'bf16x3', 'f32'), default='bf16')
+    ap.add_argument('--norm', choices=M.NORMS, default=None, help="energy normalisation (default: what the checkpoint records, else 'utterance'); 'prefix' = the causal form the real-time path emits")
     ap.add_argument('--score', action='store_true', help='SIIB / HASPI / ESTOI (PESQ / ViSQOL when registered) of the written files')
     ap.add_argument('--groups', default='Cafeteria,AirportAnnouncement', help='noise types (substrings of the file names) reported separately; empty = all files together')
     from . import quality as _q
     _q.add_cli_arguments(ap)
     a = ap.parse_args(argv)
     _q.backends_from_cli(a)
-    e = Enhancer(a.chkpt)
+    e = Enhancer(a.chkpt, norm=a.norm)
     e.G.precision = a.precision
     files = sorted(dataio.get_filepaths(a.clean))
     noise = a.noise.rstrip('/') + '/'

@@ -636,15 +636,50 @@ class _EnergyNormPack(torch.autograd.Function):
         return dmask, None, None, None, None
 
 
-def energy_norm_pack(mask, clean_band, noise_band, p_power=1.0 / 6, inv_p=6.0):
+class _EnergyNormPackPrefix(torch.autograd.Function):
+    """The causal (prefix) form: every frame normalised by the energy sums of the frames up to it (nele_energy_norm_prefix_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, mask, clean, noise, p, inv_p):
+        ratio, s2, din, _ = ops.energy_norm_prefix_fwd(clean, mask, noise, p, inv_p, want_din=True)
+        ctx.save_for_backward(mask, clean, ratio, s2, din)
+        ctx.p, ctx.inv_p = p, inv_p
+        ctx.mark_non_differentiable(ratio)
+        return din, ratio
+
+    @staticmethod
+    def backward(ctx, ddin, dratio):
+        mask, clean, ratio, s2, din = ctx.saved_tensors
+        dmask = ops.energy_norm_prefix_bwd(clean, mask, ratio, s2, ddin.contiguous(), ctx.p, ctx.inv_p, din=din)
+        return dmask, None, None, None, None
+
+
+NORMS = ('utterance', 'prefix')
+
+
+def check_norm(norm, who):
+    """'utterance': the reference's sums over the whole utterance (train_nele.py:133-140); 'prefix': sums over the frames up to each
+    frame - causal, what realtime.RealtimeEnhancer emits."""
+    if norm not in NORMS:
+        raise ValueError("%s: norm must be 'utterance' or 'prefix' (got %r)" % (who, norm))
+    return norm
+
+
+def energy_norm_pack(mask, clean_band, noise_band, p_power=1.0 / 6, inv_p=6.0, norm='utterance'):
     """mask, clean_band, noise_band [B,T,64] -> (D input [B,64,T,4] = (enh, noise, clean, 0), beta2 [B]).
-    Utterance-level (per sample) normalisation, as the batch-1 reference (train_nele.py:133-146)."""
-    return _EnergyNormPack.apply(mask.contiguous(), clean_band.contiguous(), noise_band.contiguous(), float(p_power), float(inv_p))
+    Utterance-level (per sample) normalisation, as the batch-1 reference (train_nele.py:133-146).
+    norm='prefix': the causal form of the real-time path; the second value is then ratio [B,T] (beta2 of every prefix)."""
+    fn = _EnergyNormPackPrefix if check_norm(norm, 'energy_norm_pack') == 'prefix' else _EnergyNormPack
+    return fn.apply(mask.contiguous(), clean_band.contiguous(), noise_band.contiguous(), float(p_power), float(inv_p))
 
 
-def normed_alpha2(mask, clean_band, inv_p=6.0, frames=None):
+def normed_alpha2(mask, clean_band, inv_p=6.0, frames=None, norm='utterance'):
     """mask * beta_2 (train_nele.py:303-307; inference.py:99-104), no autograd.  frames [B]: STFT frames of each utterance inside a
-    padded batch (the energy sums of beta_2 run over those frames only)."""
+    padded batch (the energy sums of beta_2 run over those frames only).
+    norm='prefix': mask[t] * ratio[t], bit-identical to the real-time path's alpha^2 on bit-equal band features and mask."""
+    if check_norm(norm, 'normed_alpha2') == 'prefix':
+        return ops.energy_norm_prefix_fwd(clean_band.contiguous(), mask.contiguous(), None, 1.0 / inv_p, float(inv_p), want_din=False,
+                                          want_alpha2=True)[3]
     _, _, _, alpha2 = ops.energy_norm_fwd(clean_band.contiguous(), mask.contiguous(), None, 1.0 / inv_p, float(inv_p), want_din=False,
                                           want_alpha2=True, frames=frames)
     return alpha2

@@ -53,6 +53,8 @@ _SIGS = {
     'nele_exptanh_bwd': [_P, _P, _P, c_longlong, _P],
     'nele_energy_norm_fwd': [_P, _P, _P, c_float, c_float, _P, _P, _P, _P, c_int, c_int, _P],
     'nele_energy_norm_bwd': [_P, _P, _P, _P, _P, _P, c_float, c_float, _P, c_int, c_int, _P],
+    'nele_energy_norm_prefix_fwd': [_P, _P, _P, c_float, c_float, _P, _P, _P, _P, c_int, c_int, _P],
+    'nele_energy_norm_prefix_bwd': [_P, _P, _P, _P, _P, _P, c_float, c_float, _P, c_int, c_int, _P],
     'nele_d_pack': [_P, _P, _P, _P, c_int, c_int, _P],
     'nele_d_layout': [_P, _P, c_int, c_int, c_int, c_int, _P],
     'nele_d_gather_items': [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), ctypes.POINTER(c_longlong), c_int, c_int, c_int, _P, _P, _P],
@@ -195,6 +197,26 @@ def energy_norm_bwd(clean, mask, beta2, s2, ddin, p, inv_p, din=None):
     B, T, _ = clean.shape
     dmask = torch.empty_like(mask)
     call('nele_energy_norm_bwd', ptr(clean), ptr(mask), ptr(beta2), ptr(s2), ptr(ddin), ptr(din), p, inv_p, ptr(dmask), B, T, stream())
+    return dmask
+
+
+def energy_norm_prefix_fwd(clean, mask, noise, p, inv_p, want_din=True, want_alpha2=False):
+    """The causal (prefix) form of energy_norm_fwd (csrc/prefixnorm.hip): -> (ratio [B,T] float32, s2 [B,T] float64, din, alpha2).
+    Padded batches need no frame counts, for the reason given in energy_norm_fwd."""
+    B, T, _ = clean.shape
+    dev = clean.device
+    ratio = torch.empty((B, T), device=dev)
+    s2 = torch.empty((B, T), dtype=torch.float64, device=dev)
+    din = torch.empty((B, 64, T, 4), device=dev) if want_din else None
+    alpha2 = torch.empty((B, T, 64), device=dev) if want_alpha2 else None
+    call('nele_energy_norm_prefix_fwd', ptr(clean), ptr(mask), ptr(noise), p, inv_p, ptr(ratio), ptr(s2), ptr(din), ptr(alpha2), B, T, stream())
+    return ratio, s2, din, alpha2
+
+
+def energy_norm_prefix_bwd(clean, mask, ratio, s2, ddin, p, inv_p, din=None):
+    B, T, _ = clean.shape
+    dmask = torch.empty_like(mask)
+    call('nele_energy_norm_prefix_bwd', ptr(clean), ptr(mask), ptr(ratio), ptr(s2), ptr(ddin), ptr(din), p, inv_p, ptr(dmask), B, T, stream())
     return dmask
 
 

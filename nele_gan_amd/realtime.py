@@ -52,7 +52,9 @@ class RealtimeEnhancer:
 
     chkpt_path / G: the generator (a checkpoint with an 'enhance-model' entry, or a ``model.Generator_Conv1D_cLN``); random weights when
     neither is given.  precision: 'f32' or 'bf16' (bf16 operands, float32 accumulation, as ``Generator_Conv1D_cLN`` in that mode).
-    norm: 'prefix' (alpha^2[t] = mask[t] * sum_{t'<=t} P / sum_{t'<=t} mask P) or a tensor [streams] of fixed beta^2 per slot.
+    norm: 'prefix' (alpha^2[t] = mask[t] * sum_{t'<=t} P / sum_{t'<=t} mask P) or a tensor [streams] of fixed beta^2 per slot; the default
+    is 'prefix' whatever the checkpoint records.  The matching training and offline modes - the same arithmetic bit for bit - are
+    ``train_nele.GanTrainer(norm='prefix')`` and ``inference.Enhancer(norm='prefix')``.
 
     Host bookkeeping: ``hops[s]`` (hops received), ``emitted[s]`` (output samples produced), ``finished[s]``."""
 

@@ -144,8 +144,12 @@ class _MetricForkCtx:
 
 class GanTrainer:
     def __init__(self, target_metric=TargetMetric, device='cuda', lr_g=5e-4, lr_d=2.5e-4, use_quality=False, pcm16=True, seed=666,
-                 haspi_dither=None, dither_seed=0, quality_scorer=None):
-        """quality_scorer: a ``quality.Scorer`` (PESQ / ViSQOL are external host programs, registered with quality.set_backends): with
+                 haspi_dither=None, dither_seed=0, quality_scorer=None, norm='utterance'):
+        """norm: the energy normalisation of the G-step's D input and of generate() - 'utterance' (the reference, train_nele.py:133-140:
+        sums over the whole utterance) or 'prefix' (sums over the frames up to each frame: the causal form realtime.RealtimeEnhancer
+        emits) - and with it of canonical_step, run_epoch (training samples, validation pass, D items) and fit.  The
+        pre-enhanced MultiEnh examples are files and are not renormalised.
+        quality_scorer: a ``quality.Scorer`` (PESQ / ViSQOL are external host programs, registered with quality.set_backends): with
         ``use_quality`` run_epoch then scores the generated and the pre-enhanced examples for D_Qua's targets where the batches bring none
         ('qua' / 'drc_qua'), and the validation utterances for the learning curve (train_nele.py:216-222, 323-324, 336-337).
         haspi_dither: None = HASPI targets without the IHC firing jitter (deterministic); 'utterance' = the reference's semantics
@@ -154,6 +158,7 @@ class GanTrainer:
         as a single-GPU run does.  The ids come with the batch (``utt_ids``; default: position in the batch)."""
         if haspi_dither not in (None, 'utterance'):
             raise ValueError("haspi_dither must be None or 'utterance'")
+        self.norm = M.check_norm(norm, 'GanTrainer')
         self.haspi_dither = haspi_dither
         self.dither_seed = int(dither_seed)
         self.metrics = parse_metrics(target_metric)
@@ -303,7 +308,7 @@ class GanTrainer:
             self.D_Qua.weight_grad_enabled = False
         self.optimizer_g.zero_grad()
         mask = self.G(clean_band, noise_band)
-        din, _ = M.energy_norm_pack(mask, clean_band, noise_band, p_power, inv_p)
+        din, _ = M.energy_norm_pack(mask, clean_band, noise_band, p_power, inv_p, norm=self.norm)
         self._last_din = din                         # bench.py re-launches D's forward on it for the isolated roofline figure
         self.D.profile_prefix = 'gstep.'             # bench.py times these launches
         score = self.D.forward_packed(din, frames)
@@ -326,7 +331,7 @@ class GanTrainer:
     def generate(self, clean_band, noise_band, clean_spec, rms_target=0.0, frames=None):
         self.G.eval()
         mask = self.G(clean_band, noise_band)
-        alpha2 = M.normed_alpha2(mask, clean_band, inv_p, frames=frames)
+        alpha2 = M.normed_alpha2(mask, clean_band, inv_p, frames=frames, norm=self.norm)
         enh_wav = au.gain_istft(alpha2, clean_spec, rms_target=rms_target, pcm16=self.pcm16, frames=frames)
         self.G.train()
         return enh_wav
@@ -1495,6 +1500,8 @@ class GanTrainer:
         sd = {'enhance-model': self.G.state_dict(), 'intel-model': self.D.state_dict()}
         if self.D_Qua is not None:
             sd['quality-model'] = self.D_Qua.state_dict()
+        if self.norm != 'utterance':                 # (utterance-mode checkpoints stay what they were: the reference's two entries)
+            sd['enhance-norm'] = self.norm
         torch.save(sd, path)
 
     def flush(self):
@@ -1502,9 +1509,15 @@ class GanTrainer:
         something touches D).  Call before reading ``self.D``'s weights or ``step_d`` directly after canonical_step."""
         self._flush_d()
 
-    def load_checkpoint(self, path):
+    def load_checkpoint(self, path, allow_norm_mismatch=False):
+        """A checkpoint records the energy normalisation its generator was trained for ('enhance-norm'; absent = 'utterance', reference
+        checkpoints included).  One recorded for another mode than this trainer's is refused unless ``allow_norm_mismatch``."""
         self._flush_d()                 # a pending pre-load gradient must not be applied to the loaded weights
         ck = torch.load(path, map_location=self.device)
+        recorded = ck.get('enhance-norm', 'utterance')
+        if recorded != self.norm and not allow_norm_mismatch:
+            raise ValueError("load_checkpoint: %s was trained with norm=%r, this trainer runs norm=%r (allow_norm_mismatch=True loads it anyway)"
+                             % (path, recorded, self.norm))
         self.G.load_state_dict(ck['enhance-model'])
         if 'intel-model' in ck:
             self.D.load_state_dict(ck['intel-model'])
@@ -1530,6 +1543,7 @@ def main(argv=None):
     ap.add_argument('--chkpt', default='./chkpt')
     ap.add_argument('--log', default='./log.txt')
     ap.add_argument('--precision', choices=('bf16', 'bf16x3', 'f32'), default='bf16', help='MFMA operand precision of G and D (f32 = the reference\'s arithmetic)')
+    ap.add_argument('--norm', choices=M.NORMS, default='utterance', help="energy normalisation: the reference's utterance-level sums, or 'prefix' - the causal form the real-time path emits")
     ap.add_argument('--valid-filter', default=None, help='keep validation files whose name contains this (train_nele.py:65: \'AIR_stairway\')')
     ap.add_argument('--resume', default=None, help='checkpoint to start from (train_nele.py:82-84)')
     ap.add_argument('--first-epoch', type=int, default=1)
@@ -1551,7 +1565,7 @@ def main(argv=None):
     if a.quality:
         from . import quality
         scorer = quality.Scorer()
-    tr = GanTrainer(a.metrics, device='cuda:%d' % local, use_quality=a.quality, quality_scorer=scorer)
+    tr = GanTrainer(a.metrics, device='cuda:%d' % local, use_quality=a.quality, quality_scorer=scorer, norm=a.norm)
     for m_ in (tr.G, tr.D, tr.D_Qua):
         if m_ is not None:
             m_.precision = a.precision
