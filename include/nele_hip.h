@@ -627,6 +627,31 @@ int nele_rt_finish(void* state, long long state_bytes, int max_streams, int prec
                    const int* tail_lengths, const float* beta2, float* out, float* dbg_band, float* dbg_noise, float* dbg_mask,
                    float* dbg_alpha2, int dbg_frames, void* stream);
 
+/* ---- active speech level and noise mixing (csrc/level.hip) -------------------------------------------------------------------------
+ * asl_P56.py:23-148 asl_P56(x, 16000, 16) (ITU-T P.56 method B) for B utterances side by side: x [B][Lmax] float32, lengths [B] (device,
+ * NULL = every row has Lmax samples).  Per utterance: asl_msq, actfact, c0 (the reference's return triple), sq = sum x^2 (float64 sum of
+ * the float32 samples' squares in a fixed order), counts [B][15] = the reference's activity counters `a` after its `a += 2`, status = 0
+ * or one of NELE_P56_* - the three inputs on which the reference fails with its c0 unset (no active sample; long-term level less than
+ * the margin above the lowest threshold; no threshold reaches the margin): asl_msq = actfact = c0 = 0 there, never NaN.
+ * The envelope is the reference's two lfilter passes in float64 in sample order: counts equal the reference's integers.  Results of a
+ * row do not depend on B or on the other rows.  workspace: nele_asl_p56_workspace_bytes(B, Lmax) bytes (may be 0 / NULL). */
+#define NELE_P56_SILENT 1
+#define NELE_P56_BELOW_MARGIN 2
+#define NELE_P56_NO_CROSSING 4
+long long nele_asl_p56_workspace_bytes(int B, int Lmax);
+int nele_asl_p56_var(const float* x, const int* lengths, int B, int Lmax, void* workspace, long long workspace_bytes, double* asl_msq,
+                     double* actfact, double* c0, double* sq, long long* counts, int* status, void* stream);
+/* Noise rows at a target SNR: pool [N][Ln] float32 with pool_lengths [N] (NULL = Ln each); per utterance b the segment
+ * v[k] = pool[rows[b]][(offsets[b] + k) mod pool_lengths[rows[b]]], k < lengths[b]; Nms = its mean square (float64, fixed order);
+ * gain[b] = sqrt(level[b] / (10^(snr_db[b] / 10) Nms)); noise[b][k] = (float)(gain[b] v[k]), zeros behind the row's end.  level [B]:
+ * the speech level as a mean square (asl_msq, or sq / length).  status [B]: 0 or NELE_MIX_* bits, with a zero row and gain 0. */
+#define NELE_MIX_ZERO_NOISE 1
+#define NELE_MIX_ZERO_LEVEL 2
+#define NELE_MIX_BAD_ROW 4
+int nele_mix_noise_var(const float* pool, const int* pool_lengths, int N, int Ln, const int* rows, const int* offsets,
+                       const double* snr_db, const double* level, const int* lengths, int B, int Lmax, float* noise, double* gain,
+                       int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -416,15 +416,22 @@ class FileBatches:
     (numpy's frombuffer / astype release the GIL), ``ahead`` batches are decoded beyond the one being asked for, and each batch is staged
     through pinned host memory with an asynchronous copy on its own stream (the consumer's stream waits for that copy only).
     ``seq[i]`` may be asked for repeatedly and in any order (run_epoch walks the list once for the G-steps and once for the sample
-    generation): a batch is decoded again when it is no longer cached, like the reference."""
+    generation): a batch is decoded again when it is no longer cached, like the reference.
+    With ``mixer`` (mixing.NoiseMixer) no noise file is read: the 'noise' entry is ``mixer.mix(clean, lengths, names, epoch)`` - what
+    an utterance receives follows its file name and ``epoch`` alone, so every batch size, order and shard sees the same rows - and the
+    batch carries 'noise_key' (mixer, epoch): what the trainer's noise-dependent caches must be keyed by beside the utterance."""
 
-    def __init__(self, file_list, noise_path, batch=32, drc_path=None, workers=8, ahead=2, device='cuda', pad_to=4096, keep=4, int16=True):
+    def __init__(self, file_list, noise_path=None, batch=32, drc_path=None, workers=8, ahead=2, device='cuda', pad_to=4096, keep=4, int16=True,
+                 mixer=None, epoch=0):
         """``int16`` (default): a batch is read by ONE library call (nele_wav_read_pcm16_batch, ``workers`` library threads) into pinned int16
         rows, uploaded as int16 and converted on the device (nele_pcm16_to_float: s / 32768, the padding and the samples behind the shorter
         of clean / noise zeroed there).  A batch that holds any other wav flavour - and every batch with ``int16=False`` - takes the
         per-file float32 path (read_wav_into / load on ``workers`` Python threads)."""
         import concurrent.futures as cf
         self.int16 = bool(int16)
+        if (mixer is None) == (noise_path is None):
+            raise ValueError("FileBatches: either a folder of noise files or a mixer")
+        self.mixer, self.epoch = mixer, int(epoch)
         self.files, self.noise_path, self.drc_path = list(file_list), noise_path, drc_path
         self.names = [f.split('/')[-1] for f in self.files]
         self.groups = [list(range(k, min(k + batch, len(self.files)))) for k in range(0, len(self.files), batch)]
@@ -443,7 +450,15 @@ class FileBatches:
         """One hashable per utterance of group g for the trainer's caches (GanTrainer.enable_clean_cache): the clean FILE (not its base name:
         Train/Clean/x.wav and Test/Clean/x.wav are different utterances) with the noise and pre-enhanced folders it is paired with - the
         cached features and D items of an utterance depend on those files too."""
-        return [(self.files[i], self.noise_path, self.drc_path) for i in self.groups[g]]
+        return [(self.files[i], self.noise_path if self.mixer is None else self.mixer.tag(), self.drc_path) for i in self.groups[g]]
+
+    def _mixed(self, b, g, names):
+        """the batch's noise rows from the mixer (on the current stream: the copy stream, behind the clean rows' upload).  What is drawn
+        follows the file NAME; the speech level the mixer remembers follows the clean file's PATH (Train/Clean/x.wav and Test/Clean/x.wav
+        are different signals).  'mix': what was drawn and measured for the rows (NoiseMixer.last of this very call)."""
+        b['noise'] = self.mixer.mix(b['clean'], b['lengths'], names, self.epoch, level_keys=[self.files[i] for i in self.groups[g]])
+        b['noise_key'] = (self.mixer.tag(), self.epoch)
+        b['mix'] = dict(self.mixer.last)
 
     def _bound(self, path):
         """upper bound of a file's samples from its size (exact for the 44-byte-header PCM_16 files the reference writes)"""
@@ -455,9 +470,12 @@ class FileBatches:
     def _decode_into(self, idx, rows):
         """decode file idx into its rows of the group's pinned buffers -> (samples clean/noise, samples drc, name)"""
         name = self.files[idx].split('/')[-1]
-        srcs = [self.files[idx], self.noise_path + name] + ([self.drc_path + name] if self.drc_path is not None else [])
+        srcs = [self.files[idx], None if self.mixer is not None else self.noise_path + name] + ([self.drc_path + name] if self.drc_path is not None else [])
         got = []
         for path, row in zip(srcs, rows):
+            if path is None:                                               # mixed noise: as long as the clean file
+                got.append(got[0])
+                continue
             r = read_wav_into(path, row)
             if r is None:                                                  # not plain mono PCM_16: the general reader
                 x, sr = load(path)
@@ -469,7 +487,8 @@ class FileBatches:
             got.append(r[0])
         m = min(got[0], got[1])                                            # the noise file is cut to the clean file's length and vice versa
         rows[0][m:] = 0.0
-        rows[1][m:] = 0.0
+        if rows[1] is not None:
+            rows[1][m:] = 0.0
         return m, (got[2] if len(got) > 2 else None), name
 
     def _pinned(self, shape):
@@ -486,13 +505,13 @@ class FileBatches:
             # the files' sample counts in one library call (round 6: 2 x B stat() calls per batch were 0.8 of the ~3.1 ms of interpreter time
             # that bound the streamed file path - tools/files_sweep.py: the same 41 k utterances/s with 4, 8 or 16 reader threads, with or
             # without writing)
-            need = [p_ for p_ in [self.files[i] for i in idxs] + [self.noise_path + nm for nm in names] +
+            need = [p_ for p_ in [self.files[i] for i in idxs] + ([self.noise_path + nm for nm in names] if self.mixer is None else []) +
                     ([self.drc_path + nm for nm in names] if self.drc_path is not None else []) if p_ not in self._bounds]
             if need:
                 for p_, n_ in zip(need, probe_wav_batch_pcm16(need, self.workers)):
                     if n_ > 0:
                         self._bounds[p_] = int(n_)
-        Lmax = max(max(self._bound(self.files[i]), self._bound(self.noise_path + nm)) for i, nm in zip(idxs, names))
+        Lmax = max(max(self._bound(self.files[i]), self._bound(self.noise_path + nm) if self.mixer is None else 0) for i, nm in zip(idxs, names))
         if self.pad_to:
             Lmax = (Lmax + self.pad_to - 1) // self.pad_to * self.pad_to
         n = len(idxs)
@@ -504,15 +523,18 @@ class FileBatches:
             Ld = max(Ld, Lmax)
         if self.int16 and not force_f32:
             import torch
-            hc, hn = pinned_get((n, Lmax), torch.int16), pinned_get((n, Lmax), torch.int16)
+            hc, hn = pinned_get((n, Lmax), torch.int16), (pinned_get((n, Lmax), torch.int16) if self.mixer is None else None)
             hd = pinned_get((n, Ld), torch.int16) if self.drc_path is not None else None
-            sets = [([self.files[i] for i in idxs], hc), ([self.noise_path + nm for nm in names], hn)]
+            sets = [([self.files[i] for i in idxs], hc), ([self.noise_path + nm for nm in names] if hn is not None else None, hn)]
             if hd is not None:
                 sets.append(([self.drc_path + nm for nm in names], hd))
 
             def run_batch():                                               # one task per batch: the library's threads do the rest
                 out = []
                 for paths, h in sets:
+                    if h is None:                                          # mixed noise: the clean files' sample counts
+                        out.append(out[0])
+                        continue
                     got, sr = read_wav_batch_pcm16(paths, h.numpy(), self.workers)
                     if (got == -2).any():
                         raise IOError('cannot read ' + paths[int(np.argmax(got == -2))])
@@ -523,9 +545,9 @@ class FileBatches:
                 return out
             self._pending[g] = ('i16', self.pool.submit(run_batch), hc, hn, hd, names)
             return
-        hc, hn = self._pinned((n, Lmax)), self._pinned((n, Lmax))
+        hc, hn = self._pinned((n, Lmax)), (self._pinned((n, Lmax)) if self.mixer is None else None)
         hd = self._pinned((n, Ld)) if self.drc_path is not None else None
-        ac, an, ad = hc.numpy(), hn.numpy(), (hd.numpy() if hd is not None else None)
+        ac, an, ad = hc.numpy(), (hn.numpy() if hn is not None else [None] * n), (hd.numpy() if hd is not None else None)
         # a task = a run of rows (submitting one task per file costs the submitting thread ~20 us each: more than the decode itself)
         nt = max(1, min(self.workers, n))
         per = (n + nt - 1) // nt
@@ -562,8 +584,11 @@ class FileBatches:
                            'nele_pcm16_to_float')       # (not _lib.call: never part of a recorded pass)
                 return out, dl
             clean, dl = up(hc, lens)
-            noise, _ = up(hn, lens)
-            b = {'clean': clean, 'noise': noise, 'lengths': dl, 'names': list(names), 'lengths_host': lens, 'keys': self._keys(g)}
+            b = {'clean': clean, 'lengths': dl, 'names': list(names), 'lengths_host': lens, 'keys': self._keys(g)}
+            if hn is not None:
+                b['noise'], _ = up(hn, lens)
+            else:
+                self._mixed(b, g, names)
             if hd is not None:
                 dlens = got[2].astype(np.int32)
                 b['drc'], b['drc_lengths'] = up(hd, dlens)
@@ -591,9 +616,13 @@ class FileBatches:
         if self._copy is None:
             self._copy = torch.cuda.Stream(device=self.device)
         with torch.cuda.stream(self._copy):
-            b = {'clean': hc.to(self.device, non_blocking=True), 'noise': hn.to(self.device, non_blocking=True),
+            b = {'clean': hc.to(self.device, non_blocking=True),
                  'lengths': torch.from_numpy(lens).pin_memory().to(self.device, non_blocking=True), 'names': [r[2] for r in res],
                  'lengths_host': lens, 'keys': self._keys(g)}
+            if hn is not None:
+                b['noise'] = hn.to(self.device, non_blocking=True)
+            else:
+                self._mixed(b, g, b['names'])
             if hd is not None:
                 dlens = np.asarray([r[1] for r in res], dtype=np.int32)
                 b['drc'] = hd.to(self.device, non_blocking=True)

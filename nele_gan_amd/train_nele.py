@@ -1127,7 +1127,7 @@ class GanTrainer:
             fc = getattr(self, '_feat_cache', None)
             k_ = None
             if kw_ and kw_['keys'] is not None and fc is not None:
-                k_ = (tuple(kw_['keys']), tuple(b['clean'].shape))
+                k_ = (tuple(kw_['keys']), tuple(b['clean'].shape), b.get('noise_key'))     # (mixed noise: another batch of features every epoch)
                 hit = fc.get(k_)
                 if hit is not None:
                     fc.move_to_end(k_)
@@ -1284,6 +1284,8 @@ class GanTrainer:
             # all known skips the DRC file's STFT and its three metric calls altogether.
             dkeys = ckw(b).get('keys') if b.get('drc') is not None else None
             dcache = getattr(self, '_drc_cache', None)
+            if b.get('noise_key') is not None:                          # mixed noise: an utterance's noise changes with the epoch, and its pre-enhanced
+                dcache = None                                           # example's D input (noise band) and targets with it - nothing of them is kept
             drc_items, miss = None, None
             if dkeys is not None and dcache is not None:
                 drc_items = [dcache.get(k_) for k_ in dkeys]
@@ -1359,7 +1361,7 @@ class GanTrainer:
     # ---------------------------------------------------------------- the script's outer loop (train_nele.py:28-120, 272-277, 426-428)
     def fit(self, train_clean_files, train_noise_path, valid_clean_files=(), valid_noise_path=None, train_enh_path=None, epochs=GAN_epoch,
             sampling=num_of_sampling, valid_samples=num_of_valid_sample, batch=32, output_path='./output', pt_dir='./chkpt', log_path='./log.txt',
-            workers=8, first_epoch=1, clean_cache=False, on_epoch=None):
+            workers=8, first_epoch=1, clean_cache=False, on_epoch=None, mixer=None):
         """``for gan_epoch in np.arange(1, GAN_epoch+1)`` of the reference script over folders of wav files, in its order:
         every epoch the training list is shuffled and its first ``sampling`` files are drawn (train_nele.py:118-119), `run_epoch` runs on them
         (G-steps from epoch 2, validation on the first ``valid_samples`` validation files with the learning-curve line appended to
@@ -1368,6 +1370,9 @@ class GanTrainer:
         pre-enhanced examples, three D passes with 1/30 replay).  Files are read in batches of ``batch`` through dataio.FileBatches (the
         reference: batch 1); ``clean_cache``: keep the clean-signal halves of the metrics across epochs (enable_clean_cache).
         ``on_epoch(result_dict)``: called after every epoch (return True to stop).  -> list of the epochs' result dicts.
+        ``mixer`` (mixing.NoiseMixer; ``train_noise_path`` is then None): every epoch's training batches receive fresh noise - pool
+        segment and SNR drawn per (utterance, epoch) - instead of noise files; validation stays on ``valid_noise_path`` when given, else
+        it is mixed once with epoch 0, so that the learning-curve line compares like with like across epochs.
         The shuffles use Python's global generator, seeded by the constructor like train_nele.py:28."""
         from . import dataio
         dataio.creatdir(pt_dir)                                         # :45-46
@@ -1384,7 +1389,8 @@ class GanTrainer:
             valid_files = valid_files[lo_:hi_]
         vb = None
         if valid_files:
-            vb = dataio.FileBatches(valid_files, valid_noise_path, batch=batch, workers=workers, ahead=2, keep=2, device=self.device)
+            vb = dataio.FileBatches(valid_files, valid_noise_path, batch=batch, workers=workers, ahead=2, keep=2, device=self.device,
+                                    mixer=mixer if valid_noise_path is None else None, epoch=0)
         results = []
         try:
             for gan_epoch in range(int(first_epoch), int(epochs) + 1):
@@ -1393,7 +1399,8 @@ class GanTrainer:
                 if self.world > 1:                                      # ... and trains on its shard of the epoch's draw (the same shuffle on every
                     lo_, hi_ = ndist.shard_range(len(sel))              # rank: the constructor seeds the generator; gradients are item-weighted means)
                     sel = sel[lo_:hi_]
-                fb = dataio.FileBatches(sel, train_noise_path, batch=batch, drc_path=train_enh_path, workers=workers, ahead=2, keep=2, device=self.device)
+                fb = dataio.FileBatches(sel, train_noise_path if mixer is None else None, batch=batch, drc_path=train_enh_path, workers=workers, ahead=2,
+                                        keep=2, device=self.device, mixer=mixer, epoch=gan_epoch)
                 try:
                     res = self.run_epoch(gan_epoch, fb, vb if vb is not None else (), chkpt_path=os.path.join(pt_dir, 'chkpt_%d.pt' % gan_epoch),
                                          sample_dir=output_path, log_path=log_path, d_batch=batch)
@@ -1549,6 +1556,10 @@ def main(argv=None):
     ap.add_argument('--first-epoch', type=int, default=1)
     ap.add_argument('--no-cache', action='store_true', help='recompute the clean-signal halves of the metrics every epoch')
     ap.add_argument('--quality', action='store_true', help='train Discriminator_Quality too (train_nele.py:150-152, 362-365): needs --pesq and --visqol - external programs')
+    ap.add_argument('--noise-pool', default=None, help='folder of noise recordings: training noise is mixed from it afresh every epoch (Train/Noise is not read)')
+    ap.add_argument('--snr', default=None, help='comma-separated SNRs in dB drawn from with --noise-pool (default: -11,-9,-7,-5,-3,-1)')
+    ap.add_argument('--snr-level', choices=('asl', 'rms'), default='asl', help='speech level of the SNR: ITU-T P.56 active speech level, or long-term mean square')
+    ap.add_argument('--mix-seed', type=int, default=0)
     from . import quality as _q
     _q.add_cli_arguments(ap)
     a = ap.parse_args(argv)
@@ -1584,10 +1595,21 @@ def main(argv=None):
             v = res.get('valid') or {}
             print('epoch %d: g_loss %s, %d samples, %d D steps, valid %s' % (res['gan_epoch'], res['g_loss'] if res['g_loss'] is None else '%.4f' % float(res['g_loss']),
                                                                              res['samples'], res['d_steps'], ', '.join('%s %.3f' % kv for kv in v.items())), flush=True)
+    mixer = None
+    if a.noise_pool:
+        from . import mixing, synth
+        pool = sorted(dataio.get_filepaths(a.noise_pool))
+        if not pool:
+            ap.error('--noise-pool: no wav file under ' + a.noise_pool)
+        mixer = mixing.NoiseMixer(pool, snrs_db=[float(v) for v in a.snr.split(',')] if a.snr else synth.SNRS_DB, level=a.snr_level, seed=a.mix_seed,
+                                  device='cuda:%d' % local)
+    valid_noise = root + '/Test/Noise/'
+    if mixer is not None and not os.path.isdir(valid_noise):
+        valid_noise = None                                               # mixed once (epoch 0)
     try:
-        tr.fit(train, root + '/Train/Noise/', valid, root + '/Test/Noise/', train_enh_path=enh if os.path.isdir(enh) else None, epochs=a.epochs,
-               sampling=a.sampling, valid_samples=a.valid_samples, batch=a.batch, output_path=a.output, pt_dir=a.chkpt, log_path=a.log,
-               first_epoch=a.first_epoch, clean_cache=not a.no_cache, on_epoch=report)
+        tr.fit(train, None if mixer is not None else root + '/Train/Noise/', valid, valid_noise, train_enh_path=enh if os.path.isdir(enh) else None,
+               epochs=a.epochs, sampling=a.sampling, valid_samples=a.valid_samples, batch=a.batch, output_path=a.output, pt_dir=a.chkpt, log_path=a.log,
+               first_epoch=a.first_epoch, clean_cache=not a.no_cache, on_epoch=report, mixer=mixer)
     finally:
         if world > 1:
             import torch.distributed as tdist
