@@ -598,6 +598,31 @@ int nele_fir_filter(const float* x, int B, int L, const double* h, int Lh, doubl
 int nele_norm_clip(const double* a64, const float* a32, const float* add, int B, int N, double target_rms, float* out, double* out64,
                    int* nclip, void* stream);
 
+/* ---- rooms: one impulse response per row (csrc/fftconv.hip) -------------------------------------------------------------------------
+ * eval_metrics.py:124-167 for a batch whose rows have their own RIR and length.  nele_fir_fft_var is scipy.signal.lfilter(h, [1], x)
+ * like nele_fir_filter, computed by uniformly partitioned overlap-save: 256-sample blocks, 512-point float64 transforms; per output
+ * block Y_j = sum_p X_{j - p} H_p in ascending p over the RIR's ceil(taps / 256) partition spectra (agrees with nele_fir_filter to
+ * 1e-12 max|y|; not bit for bit).
+ * nele_rir_bank_prepare: rirs [R][Lhmax] float64 (device; row r holds taps[r] samples, what lies behind them is ignored), taps [R]
+ * (device, clamped to 1 .. Lhmax) -> bank (nele_rir_bank_bytes(R, Lhmax) bytes, 256-byte aligned, opaque).  The direct-path filter
+ * rir[:argmax + tau] of :127-131 is one more row with fewer taps.
+ * nele_fir_fft_var: x [B][Lmax] float32, lengths [B] (device, NULL = Lmax each), rir_index [B] (device, NULL = entry 0) -> y [B][Lmax]
+ * float64: row b = lfilter(bank entry rir_index[b], [1], x[b][:lengths[b]]); y[b][lengths[b]:] = 0 exactly and x is not read there; a
+ * row whose index is outside the bank is all zeros.  The work of a row follows its own entry's taps, not Lhmax.  A row's output is
+ * the same bits whatever B, the other rows and the bank's other entries are.  workspace: nele_fir_fft_workspace_bytes(B, Lmax) bytes,
+ * 16-byte aligned (the blocks' spectra, 4096 bytes per 256 samples).  The *_bytes functions return -1 on bad arguments. */
+long long nele_rir_bank_bytes(int R, int Lhmax);
+int nele_rir_bank_prepare(const double* rirs, const int* taps, int R, int Lhmax, void* bank, void* stream);
+long long nele_fir_fft_workspace_bytes(int B, int Lmax);
+int nele_fir_fft_var(const float* x, int B, int Lmax, const int* lengths, const void* bank, const int* rir_index, double* y,
+                     void* workspace, void* stream);
+
+/* nele_norm_clip per row: n = lengths[b] (device, NULL = N) samples, v[i] = a[b][i] (+ add[b][i + add_shift[b]]) for i < n; the rms
+ * and clip() are taken over those n; out[b][i] = v'[i + out_shift[b]] while i + out_shift[b] < n and exact zeros behind, up to N
+ * (the `[b:]` of eval_metrics.py:136,142 with b = argmax of the row's RIR).  add_shift / out_shift [B] (device, NULL = 0). */
+int nele_norm_clip_var(const double* a64, const float* a32, const float* add, int B, int N, const int* lengths, const int* add_shift,
+                       const int* out_shift, double target_rms, float* out, double* out64, int* nclip, void* stream);
+
 /* ---- real-time enhancement (csrc/realtime.hip) ------------------------------------------------------------------------------------
  * The offline chain (STFT, band features, IMCRA, Generator_Conv1D_cLN, resynthesis) run causally, one 256-sample hop of up to
  * max_streams independent streams at a time (DESIGN.md "Real-time enhancement").  `state` (nele_rt_state_bytes(max_streams) bytes,

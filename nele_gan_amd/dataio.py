@@ -422,8 +422,9 @@ class FileBatches:
     batch carries 'noise_key' (mixer, epoch): what the trainer's noise-dependent caches must be keyed by beside the utterance."""
 
     def __init__(self, file_list, noise_path=None, batch=32, drc_path=None, workers=8, ahead=2, device='cuda', pad_to=4096, keep=4, int16=True,
-                 mixer=None, epoch=0):
-        """``int16`` (default): a batch is read by ONE library call (nele_wav_read_pcm16_batch, ``workers`` library threads) into pinned int16
+                 mixer=None, epoch=0, rir_bank=None):
+        """``rir_bank`` (room.RirBank): every batch carries 'rir' - the bank row of each file by its name (RirBank.ids; -1: anechoic), host int32.
+        ``int16`` (default): a batch is read by ONE library call (nele_wav_read_pcm16_batch, ``workers`` library threads) into pinned int16
         rows, uploaded as int16 and converted on the device (nele_pcm16_to_float: s / 32768, the padding and the samples behind the shorter
         of clean / noise zeroed there).  A batch that holds any other wav flavour - and every batch with ``int16=False`` - takes the
         per-file float32 path (read_wav_into / load on ``workers`` Python threads)."""
@@ -432,6 +433,7 @@ class FileBatches:
         if (mixer is None) == (noise_path is None):
             raise ValueError("FileBatches: either a folder of noise files or a mixer")
         self.mixer, self.epoch = mixer, int(epoch)
+        self.rir_bank = rir_bank
         self.files, self.noise_path, self.drc_path = list(file_list), noise_path, drc_path
         self.names = [f.split('/')[-1] for f in self.files]
         self.groups = [list(range(k, min(k + batch, len(self.files)))) for k in range(0, len(self.files), batch)]
@@ -595,6 +597,8 @@ class FileBatches:
                 b['drc_lengths_host'] = dlens
             ev = torch.cuda.Event()
             ev.record(self._copy)
+        if self.rir_bank is not None:
+            b['rir'] = self.rir_bank.ids(b['names'])
         self._ready[g] = (b, ev, (hc, hn, hd) + tuple(small))
 
     def _stage(self, g):
@@ -629,6 +633,8 @@ class FileBatches:
                 b['drc_lengths'] = torch.from_numpy(dlens).pin_memory().to(self.device, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(self._copy)
+        if self.rir_bank is not None:
+            b['rir'] = self.rir_bank.ids(b['names'])
         self._ready[g] = (b, ev, (hc, hn, hd))
         self._trim()
 

@@ -82,3 +82,19 @@ def evaluate(clean, enh, noise, rir=None, metrics=('siib', 'haspi', 'estoi'), en
     out = {m: fn[m](clean_a, mixed)[0].double().cpu().numpy() for m in metrics}
     out['summary'] = ', '.join('%s is %.3f' % (m.upper(), float(np.mean(out[m]))) for m in metrics)
     return out
+
+
+def evaluate_rooms(clean, enh, noise, bank, rir_ids, lengths=None, metrics=('siib', 'haspi', 'estoi'), enh_rms=0.03):
+    """``evaluate`` with a room per utterance: bank = room.RirBank, rir_ids [B] = its rows (bank.ids(names); -1 = anechoic), lengths [B]
+    samples per row (None: full rows).  Raw scores per utterance, the summary over all, and ``by_rir``: name (None = anechoic) -> means."""
+    from . import room
+    clean, enh, noise = _dev32(clean), _dev32(enh), _dev32(noise)
+    ids = np.asarray(rir_ids.cpu() if isinstance(rir_ids, torch.Tensor) else rir_ids, dtype=np.int32)
+    clean_a, mixed, la = room.Room(bank).apply(clean, enh, noise, ids, lengths, enh_rms=enh_rms)
+    fn = {'siib': mt.batch_siib, 'haspi': mt.batch_haspi, 'estoi': mt.batch_estoi}
+    out = {m: fn[m](clean_a, mixed, lengths=la)[0].double().cpu().numpy() for m in metrics}
+    line = lambda rows: ', '.join('%s is %.3f' % (m.upper(), float(np.mean(out[m][rows]))) for m in metrics)
+    out['summary'] = line(slice(None))
+    out['by_rir'] = {bank.name_of(i): line(ids == i) for i in sorted(set(ids.tolist()))}
+    out['lengths'] = la.cpu().numpy()
+    return out

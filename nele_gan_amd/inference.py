@@ -267,6 +267,37 @@ def score_enhanced(clean_path, noise_path, enhanced_names, groups=('Cafeteria', 
     return res
 
 
+def score_rooms(clean_path, noise_path, enhanced_names, bank, batch=32, metrics=('siib', 'haspi', 'estoi'), out=None):
+    """The scores of the enhanced files in the room each file's name gives (room.RirBank.ids: '<utt>#<rir>#...wav'; no such RIR:
+    anechoic), eval_metrics.py:100-186 per utterance: eval_metrics.evaluate_rooms over batches of ``batch`` files.
+    -> {rir name (None = anechoic): {metric: mean, 'files': n}}; one report line per RIR is printed to ``out``."""
+    import sys
+    import numpy as np
+    from . import dataio, eval_metrics
+    out = sys.stdout if out is None else out
+    ids = bank.ids([dataio.wave_name_of(f) + '.wav' for f in enhanced_names])
+    rows = {m: [] for m in metrics}
+    for k in range(0, len(enhanced_names), batch):
+        trip = []
+        for f in enhanced_names[k:k + batch]:
+            name = dataio.wave_name_of(f) + '.wav'
+            c, e, v = dataio.load(clean_path + name, sr=16000)[0], dataio.load(f, sr=16000)[0], dataio.load(noise_path + name, sr=16000)[0]
+            n = min(len(c), len(e), len(v))                                          # eval_metrics.py:111-114
+            trip.append((c[:n], e[:n], v[:n]))
+        (c, lens), (e, _), (v, _) = (dataio.pad_batch([t[i] for t in trip]) for i in range(3))
+        r = eval_metrics.evaluate_rooms(c, e, v, bank, ids[k:k + batch], lengths=lens, metrics=metrics)
+        for m in metrics:
+            rows[m].append(r[m])
+    rows = {m: np.concatenate(v) for m, v in rows.items()}
+    res = {}
+    for i in sorted(set(ids.tolist())):
+        name = bank.name_of(i)
+        res[name] = {m: float(np.mean(rows[m][ids == i])) for m in metrics}
+        res[name]['files'] = int((ids == i).sum())
+        out.write('%s:\n%s\n\n======\n' % ('NO_rev' if name is None else name, ', '.join('%s is %.3f' % (m.upper(), res[name][m]) for m in metrics)))
+    return res
+
+
 def main(argv=None):
     """``python -m nele_gan_amd.inference --chkpt ./trained_model/chkpt_GD.pt --clean <dir> --noise <dir> --output <dir>`` = the
     reference's usage step 4 (`python inference.py`, README; inference.py:28-146): every wav under --clean is enhanced against the noise file
@@ -283,6 +314,8 @@ def main(argv=None):
     ap.add_argument('--norm', choices=M.NORMS, default=None, help="energy normalisation (default: what the checkpoint records, else 'utterance'); 'prefix' = the causal form the real-time path emits")
     ap.add_argument('--score', action='store_true', help='SIIB / HASPI / ESTOI (PESQ / ViSQOL when registered) of the written files')
     ap.add_argument('--groups', default='Cafeteria,AirportAnnouncement', help='noise types (substrings of the file names) reported separately; empty = all files together')
+    ap.add_argument('--rir', default=None, help="with --score: folder of 16 kHz room impulse responses; the files are also scored in the room their name gives "
+                                                "('<utt>#<rir>#...wav'), reported per RIR")
     from . import quality as _q
     _q.add_cli_arguments(ap)
     a = ap.parse_args(argv)
@@ -295,6 +328,9 @@ def main(argv=None):
     print('%d files -> %s' % (len(out), a.output))
     if a.score:
         score_enhanced(a.clean.rstrip('/') + '/', noise, out, groups=tuple(g for g in a.groups.split(',') if g))
+        if a.rir:
+            from . import room
+            score_rooms(a.clean.rstrip('/') + '/', noise, out, room.RirBank(a.rir), batch=a.batch)
     return 0
 
 

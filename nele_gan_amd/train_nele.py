@@ -144,8 +144,12 @@ class _MetricForkCtx:
 
 class GanTrainer:
     def __init__(self, target_metric=TargetMetric, device='cuda', lr_g=5e-4, lr_d=2.5e-4, use_quality=False, pcm16=True, seed=666,
-                 haspi_dither=None, dither_seed=0, quality_scorer=None, norm='utterance'):
-        """norm: the energy normalisation of the G-step's D input and of generate() - 'utterance' (the reference, train_nele.py:133-140:
+                 haspi_dither=None, dither_seed=0, quality_scorer=None, norm='utterance', room=None):
+        """room: a ``room.Room`` (or a ``room.RirBank``): the listener's room.  The metric targets of every batch that brings ``rir_ids``
+        (bank rows, -1 = anechoic row) are then taken on Room.apply's (direct-path clean, reverberated enhanced + noise) instead of
+        (clean, enhanced + noise) - true_metrics, true_metrics_pair, canonical_step, run_epoch, fit.  G's and D's inputs and every network
+        pass are unchanged; without ``rir_ids`` (or without a room) every path computes what it computes without this argument.
+        norm: the energy normalisation of the G-step's D input and of generate() - 'utterance' (the reference, train_nele.py:133-140:
         sums over the whole utterance) or 'prefix' (sums over the frames up to each frame: the causal form realtime.RealtimeEnhancer
         emits) - and with it of canonical_step, run_epoch (training samples, validation pass, D items) and fit.  The
         pre-enhanced MultiEnh examples are files and are not renormalised.
@@ -159,6 +163,10 @@ class GanTrainer:
         if haspi_dither not in (None, 'utterance'):
             raise ValueError("haspi_dither must be None or 'utterance'")
         self.norm = M.check_norm(norm, 'GanTrainer')
+        if room is not None and not hasattr(room, 'apply'):
+            from . import room as _room
+            room = _room.Room(room)
+        self.room = room
         self.haspi_dither = haspi_dither
         self.dither_seed = int(dither_seed)
         self.metrics = parse_metrics(target_metric)
@@ -453,22 +461,46 @@ class GanTrainer:
         return _MetricFork(self, inputs)
 
     @torch.no_grad()
-    def true_metrics(self, clean_wav, enh_wav, noise_wav, norm=True, lengths=None, resynth=True, utt_ids=None, defer=False, keys=None):
+    def _room_keys(self, keys, rir_ids):
+        """cache keys of a batch scored in a room: the direct-path clean signal belongs to (utterance, RIR), so the RIR's NAME joins the
+        key - the same utterance under two RIRs (or with and without one) never shares a clean-signal state"""
+        if keys is None:
+            return None
+        ids = np.asarray(rir_ids.cpu() if isinstance(rir_ids, torch.Tensor) else rir_ids).reshape(-1)
+        return [('room', self.room.bank.name_of(int(i)), self.room.bank.tau, k_) for k_, i in zip(keys, ids)]
+
+    def _room_pair(self, clean_wav, enh_wav, noise_wav, lengths, resynth, rir_ids):
+        """(x, y, lengths) the metrics see of a batch in the trainer's room (Room.apply on the columns and lengths they would see without)"""
+        L = min(clean_wav.shape[1], enh_wav.shape[1])
+        lengths = au._i32(lengths, self.device)
+        if resynth:
+            lengths = self.enhanced_lengths(lengths)
+        elif lengths is not None:
+            lengths = torch.clamp(lengths, max=L)
+        return self.room.apply(clean_wav[:, :L], enh_wav[:, :L], noise_wav[:, :L], rir_ids, lengths)
+
+    def true_metrics(self, clean_wav, enh_wav, noise_wav, norm=True, lengths=None, resynth=True, utt_ids=None, defer=False, keys=None,
+                     rir_ids=None):
         """[B, n_metrics] targets of (clean, enhanced + noise) (audio_util.py:120-203).  lengths [B]: samples of each utterance inside the
         padded batch; resynth=True: ``enh_wav`` came out of ``generate`` (each row holds 256 * (L // 256) samples); False: ``lengths``
         already are min(clean, enhanced) per utterance (the pre-enhanced 'DRC' examples, audio_util.py:267-321).
         utt_ids [B] int64: utterance ids for the per-utterance HASPI dither (haspi_dither='utterance').
         defer: return a _PendingTargets instead - the kernels are enqueued on the metric streams, the caller's stream is not made to
         wait for them until .result() (run_epoch: a batch's metrics run under the next batch's generator).
-        keys [B] (host list of hashables, one per utterance): with enable_clean_cache() the clean-signal halves are reused across calls."""
-        L = min(clean_wav.shape[1], enh_wav.shape[1])          # audio_util.py:134-141
-        x = clean_wav[:, :L].contiguous()
-        y = (enh_wav[:, :L] + noise_wav[:, :L]).contiguous()
-        lengths = au._i32(lengths, self.device)
-        if resynth:
-            lengths = self.enhanced_lengths(lengths)
-        elif lengths is not None:
-            lengths = torch.clamp(lengths, max=L)
+        keys [B] (host list of hashables, one per utterance): with enable_clean_cache() the clean-signal halves are reused across calls.
+        rir_ids [B] (with a room): rows of the room's bank, -1 = anechoic; the pair scored is Room.apply's, the keys carry the RIR."""
+        if self.room is not None and rir_ids is not None:
+            x, y, lengths = self._room_pair(clean_wav, enh_wav, noise_wav, lengths, resynth, rir_ids)
+            keys = self._room_keys(keys, rir_ids)
+        else:
+            L = min(clean_wav.shape[1], enh_wav.shape[1])          # audio_util.py:134-141
+            x = clean_wav[:, :L].contiguous()
+            y = (enh_wav[:, :L] + noise_wav[:, :L]).contiguous()
+            lengths = au._i32(lengths, self.device)
+            if resynth:
+                lengths = self.enhanced_lengths(lengths)
+            elif lengths is not None:
+                lengths = torch.clamp(lengths, max=L)
         if self.clean_cache is not None and keys is not None:
             x, (y,), lengths = self._canon(x, [y], lengths)
         cols = []
@@ -485,14 +517,24 @@ class GanTrainer:
 
     @torch.no_grad()
     def true_metrics_pair(self, clean_wav, enh_wav, drc_wav, noise_wav, norm=True, lengths=None, drc_lengths=None, utt_ids=None, defer=False,
-                          keys=None, lengths_host=None, drc_lengths_host=None):
+                          keys=None, lengths_host=None, drc_lengths_host=None, rir_ids=None):
         """Targets of TWO degraded versions of one clean batch - the generated example and the pre-enhanced ('DRC') one, which the loop
         scores back to back (train_nele.py:318-340) - with the clean-signal work done once: SIIB's VAD / clean spectra / covariance /
         eigen-decomposition (its KLT basis) and HASPI's whole reference-signal chain depend on the clean signal only
         (metrics.SiibSplit / HaspiSplit: clean_part() once, degraded_part() twice).  -> (targets_enh, targets_drc), each bit-identical
         to a true_metrics() call of its own.  Falls back to two full calls when the two comparisons do not see the same clean samples
-        (different truncation lengths, audio_util.py:134-137)."""
+        (different truncation lengths, audio_util.py:134-137).  With a room and ``rir_ids``: two true_metrics calls (the direct-path clean
+        signal is cut to each comparison's own length before it is normalised, so the two share a clean-signal state only through the
+        cache, whose keys tell them apart)."""
         lengths = au._i32(lengths, self.device)
+        if self.room is not None and rir_ids is not None:
+            full_ = lambda t, w: torch.full((w.shape[0],), w.shape[1], dtype=torch.int32, device=self.device) if t is None else au._i32(t, self.device)
+            ml_d_ = torch.clamp(torch.minimum(full_(drc_lengths, drc_wav), full_(lengths, clean_wav)), max=min(clean_wav.shape[1], drc_wav.shape[1]))
+            kd_ = None if keys is None else [('drc', k_) for k_ in keys]
+            pa = self.true_metrics(clean_wav, enh_wav, noise_wav, norm=norm, lengths=lengths, utt_ids=utt_ids, defer=defer, keys=keys, rir_ids=rir_ids)
+            pb = self.true_metrics(clean_wav, drc_wav, noise_wav, norm=norm, lengths=ml_d_, resynth=False, utt_ids=utt_ids, defer=defer, keys=kd_,
+                                   rir_ids=rir_ids)
+            return _PendingTargets([], lambda: (pa.result(), pb.result())) if defer else (pa, pb)
         L = min(clean_wav.shape[1], enh_wav.shape[1])
         Ld = min(clean_wav.shape[1], drc_wav.shape[1])
         ml_e = self.enhanced_lengths(lengths)
@@ -750,9 +792,11 @@ class GanTrainer:
         if after is None:
             after = torch.cuda.Event()
             after.record(torch.cuda.current_stream())
-        return self._input_only_work(clean_wav, noise_wav, lengths, after, with_features=True, utt_ids=utt_ids, with_metrics=with_metrics)
+        # (with a room the clean-signal halves belong to the direct-path signal of (utterance, RIR): they are not taken a step ahead)
+        return self._input_only_work(clean_wav, noise_wav, lengths, after, with_features=True, utt_ids=utt_ids,
+                                     with_metrics=with_metrics and self.room is None)
 
-    def canonical_step(self, clean_wav, noise_wav, feats=None, lengths=None, pre=None, next_batch=None, utt_ids=None, early=None):
+    def canonical_step(self, clean_wav, noise_wav, feats=None, lengths=None, pre=None, next_batch=None, utt_ids=None, early=None, rir_ids=None):
         """features -> G-step -> generate -> true metrics -> D-step on the same batch.  lengths [B] (optional): samples of each
         utterance inside the padded batch (every utterance needs >= 21 frames, i.e. 5120 samples, for D).
         pre: what prefetch() returned for THIS batch (its input-only work is then already in flight or done);
@@ -760,7 +804,11 @@ class GanTrainer:
         (large batches: it fills the D backward pass) or, ``early`` (default: batches of at most ``early_prefetch_max_batch``), at the
         start of this step on the second set of side streams and workspaces: a small batch leaves most of the GPU idle and its step
         is as long as its longest dependent chain - SIIB's clean-signal half with the eigen-decomposition, 4.2 of 5.8 ms at B = 32 -
-        which then runs a step ahead.  The result is left in ``self.prefetched``; bit-identical either way."""
+        which then runs a step ahead.  The result is left in ``self.prefetched``; bit-identical either way.
+        rir_ids [B] (trainer with a room): the targets are those of true_metrics(..., rir_ids=rir_ids) - Room.apply on the metric stream
+        once the enhanced batch exists, then the metrics on its pair.  A trainer with a room prefetches features only (the metrics'
+        clean-signal halves would have to be taken on the next batch's direct-path signal), in the plain and in the pipelined step."""
+        room_on = self.room is not None and rir_ids is not None
         # The metric kernels run on a side stream.  (1) Everything SIIB derives from the CLEAN signal alone - VAD, clean spectra,
         # the covariance and its eigen-decomposition (the KLT basis) - is enqueued first and runs beside features / G-step /
         # generate.  (2) Once the enhanced signal exists the remaining metric work follows on the side stream while the main
@@ -797,7 +845,7 @@ class GanTrainer:
             assert pre['clean'] is clean_wav and pre['noise'] is noise_wav, "canonical_step: `pre` belongs to another batch"
         if pre is None or not pre['metrics']:
             # nothing prefetched, or the features only (late_prefetch = 'features'): the metrics' clean-signal halves start with the step
-            mine_ = self._input_only_work(clean_wav, noise_wav, lengths, start, with_features=False, utt_ids=utt_ids)
+            mine_ = self._input_only_work(clean_wav, noise_wav, lengths, start, with_features=False, utt_ids=utt_ids, with_metrics=not room_on)
             if pre is not None:
                 mine_['feats'], mine_['feats_ready'] = pre['feats'], pre['feats_ready']
             pre = mine_
@@ -808,7 +856,8 @@ class GanTrainer:
             mine = self._cur_set
             self._use_set(1 - mine)
             early_pre = self._input_only_work(next_batch[0], next_batch[1], next_batch[2] if len(next_batch) > 2 else None, start,
-                                              with_features=True, utt_ids=next_batch[3] if len(next_batch) > 3 else None)
+                                              with_features=True, utt_ids=next_batch[3] if len(next_batch) > 3 else None,
+                                              with_metrics=self.room is None)
             self._use_set(mine)
         side = self._side
         lengths, mlens, x, split, hsplit = pre['lengths'], pre['mlens'], pre['x'], pre['split'], pre['hsplit']
@@ -844,12 +893,19 @@ class GanTrainer:
             side.wait_event(ready)
             if pre['clean_done'] is not None and side != pre['clean_stream']:   # (same stream: FIFO; a self-wait also upsets ROCm's stream capture)
                 side.wait_event(pre['clean_done'])
-            y = (enh + noise_wav[:, :L]).contiguous()
+            if room_on:
+                # the listener's room: every metric on Room.apply's pair, on this stream, by the calls true_metrics makes
+                assert pre['metrics'] is False and split is None and hsplit is None
+                x, y, mlens = self.room.apply(x, enh, noise_wav[:, :L], rir_ids, mlens)
+                for m in self.metrics:
+                    cols[m] = self._metric(m, x, y, 'fside' if early else 'side', mlens, pre.get('utt_ids'))[1]
+            else:
+                y = (enh + noise_wav[:, :L]).contiguous()
             y_ready = torch.cuda.Event()
             y_ready.record(side)
             if split is not None:
                 cols['siib'] = split.degraded_part(y)[1]
-            if 'estoi' in self.metrics and 'haspi' in self.metrics:
+            if 'estoi' in self.metrics and 'haspi' in self.metrics and not room_on:
                 cols['estoi'] = mt.batch_estoi(x, y, lengths=mlens)[1]    # HASPI's degraded-signal chain owns the other stream: ESTOI rides behind SIIB
         haspi_info = None
         with torch.cuda.stream(side2):                     # the cheaper metrics beside SIIB's degraded-signal part
@@ -859,6 +915,8 @@ class GanTrainer:
                 if m == 'haspi' and hsplit is not None:
                     cols[m] = hsplit.degraded_part(y, dither=pre['dither'])[1]
                     haspi_info = hsplit.info
+                elif m in cols:
+                    pass
                 elif m == 'haspi':
                     _, cols[m], haspi_info = mt.batch_haspi(x, y, return_info=True, lengths=mlens, dither=self._dither(x, pre.get('utt_ids')))
                 elif m != 'siib' and m not in cols:
@@ -1159,6 +1217,12 @@ class GanTrainer:
         def ckw(b):                                                     # utterance keys travel only when the clean-signal cache is on
             return {'keys': b.get('keys', b.get('names'))} if getattr(self, 'clean_cache', None) is not None else {}
 
+        def rkw(b, rows=None):                                          # the rows' RIRs (batch key 'rir': host int32 [B]) travel when the trainer has a room
+            if getattr(self, 'room', None) is None or b.get('rir') is None:
+                return {}
+            r_ = np.asarray(b['rir'].cpu() if torch.is_tensor(b['rir']) else b['rir'], dtype=np.int32)
+            return {'rir_ids': r_ if rows is None else r_[rows]}
+
         if gan_epoch >= 2:                                              # :122
             tot = None
             n_g = len(train_batches)
@@ -1198,7 +1262,8 @@ class GanTrainer:
             if sample_dir is not None and 'names' in b:                 # :190-198 (the reference keeps the first 20 for listening)
                 self.write_samples(enh, b['names'], sample_dir + '/Test_epoch' + str(gan_epoch), gan_epoch,
                                    lengths=b.get('lengths_host', b.get('lengths')), wait=False)
-            raw.append(self.true_metrics(b['clean'], enh, b['noise'], norm=False, lengths=b.get('lengths'), utt_ids=b.get('ids'), defer=True, **ckw(b)))
+            raw.append(self.true_metrics(b['clean'], enh, b['noise'], norm=False, lengths=b.get('lengths'), utt_ids=b.get('ids'), defer=True, **ckw(b),
+                                         **rkw(b)))
         raw = [p.result() for p in raw]                                 # (a batch's metrics ran under the next batch's generator)
         if raw or (dp and valid_batches is not None):
             n_m = len(self.metrics)
@@ -1283,6 +1348,8 @@ class GanTrainer:
             # per utterance key after the first time (the reference recomputes read_batch_*_DRC every epoch); a batch whose utterances are
             # all known skips the DRC file's STFT and its three metric calls altogether.
             dkeys = ckw(b).get('keys') if b.get('drc') is not None else None
+            if dkeys is not None and rkw(b):                            # a pre-enhanced example's targets are those of (utterance, RIR)
+                dkeys = self._room_keys(dkeys, rkw(b)['rir_ids'])
             dcache = getattr(self, '_drc_cache', None)
             if b.get('noise_key') is not None:                          # mixed noise: an utterance's noise changes with the epoch, and its pre-enhanced
                 dcache = None                                           # example's D input (noise band) and targets with it - nothing of them is kept
@@ -1297,9 +1364,9 @@ class GanTrainer:
                 # generated + pre-enhanced example of the same utterances: one pass over the clean signal for both when they are compared over
                 # the same samples (audio_util.py:134-137)
                 pend = self.true_metrics_pair(b['clean'], enh, b['drc'], b['noise'], lengths=lens, drc_lengths=dl, utt_ids=b.get('ids'), defer=True,
-                                              **ckw(b), **hkw(b))
+                                              **ckw(b), **hkw(b), **rkw(b))
             else:
-                pend = self.true_metrics(b['clean'], enh, b['noise'], lengths=lens, utt_ids=b.get('ids'), defer=True, **ckw(b))
+                pend = self.true_metrics(b['clean'], enh, b['noise'], lengths=lens, utt_ids=b.get('ids'), defer=True, **ckw(b), **rkw(b))
                 if miss:
                     # some pre-enhanced examples of this batch are new (a loop that re-draws its batches every epoch): their targets and D
                     # inputs as a batch of their own - true_metrics on (clean, pre-enhanced + noise) over min(clean, pre-enhanced) samples is
@@ -1312,7 +1379,8 @@ class GanTrainer:
                         full_ = lambda t, w: torch.full((w.shape[0],), w.shape[1], dtype=torch.int32, device=self.device) if t is None else au._i32(t, self.device)
                         ml_d = torch.clamp(torch.minimum(full_(dl, b['drc']), full_(lens, b['clean'])), max=Ld_)
                     pend_sub = self.true_metrics(sub(b['clean']), sub(b['drc']), sub(b['noise']), lengths=sub(ml_d), resynth=False,
-                                                 utt_ids=sub(b.get('ids')), defer=True, keys=[('drc', dkeys[r_]) for r_ in miss])
+                                                 utt_ids=sub(b.get('ids')), defer=True, keys=[('drc', dkeys[r_]) for r_ in miss],
+                                                 **rkw(b, miss))
                     din_sub = self.d_inputs(sub(b['drc']), sub(f['noise_band']), sub(f['clean_band']),
                                             sub(au._i32(dl, self.device)) if dl is not None else None, resynth=False)
             # the targets are not waited for here: this batch's metric kernels (three streams, SIIB's a latency chain through the
@@ -1361,7 +1429,7 @@ class GanTrainer:
     # ---------------------------------------------------------------- the script's outer loop (train_nele.py:28-120, 272-277, 426-428)
     def fit(self, train_clean_files, train_noise_path, valid_clean_files=(), valid_noise_path=None, train_enh_path=None, epochs=GAN_epoch,
             sampling=num_of_sampling, valid_samples=num_of_valid_sample, batch=32, output_path='./output', pt_dir='./chkpt', log_path='./log.txt',
-            workers=8, first_epoch=1, clean_cache=False, on_epoch=None, mixer=None):
+            workers=8, first_epoch=1, clean_cache=False, on_epoch=None, mixer=None, rir_bank=None):
         """``for gan_epoch in np.arange(1, GAN_epoch+1)`` of the reference script over folders of wav files, in its order:
         every epoch the training list is shuffled and its first ``sampling`` files are drawn (train_nele.py:118-119), `run_epoch` runs on them
         (G-steps from epoch 2, validation on the first ``valid_samples`` validation files with the learning-curve line appended to
@@ -1373,8 +1441,16 @@ class GanTrainer:
         ``mixer`` (mixing.NoiseMixer; ``train_noise_path`` is then None): every epoch's training batches receive fresh noise - pool
         segment and SNR drawn per (utterance, epoch) - instead of noise files; validation stays on ``valid_noise_path`` when given, else
         it is mixed once with epoch 0, so that the learning-curve line compares like with like across epochs.
+        ``rir_bank`` (room.RirBank): the training and the validation batches carry each file's RIR (its name's '#' field, RirBank.ids) and
+        the targets are taken in that room (a trainer built without a room gets Room(rir_bank)).
         The shuffles use Python's global generator, seeded by the constructor like train_nele.py:28."""
         from . import dataio
+        if rir_bank is not None:
+            if self.room is None:
+                from . import room as _room
+                self.room = _room.Room(rir_bank)
+            elif self.room.bank is not rir_bank:
+                raise ValueError("fit: rir_bank is not the bank of this trainer's room")
         dataio.creatdir(pt_dir)                                         # :45-46
         dataio.creatdir(output_path)
         if clean_cache and self.clean_cache is None:
@@ -1390,7 +1466,7 @@ class GanTrainer:
         vb = None
         if valid_files:
             vb = dataio.FileBatches(valid_files, valid_noise_path, batch=batch, workers=workers, ahead=2, keep=2, device=self.device,
-                                    mixer=mixer if valid_noise_path is None else None, epoch=0)
+                                    mixer=mixer if valid_noise_path is None else None, epoch=0, rir_bank=rir_bank)
         results = []
         try:
             for gan_epoch in range(int(first_epoch), int(epochs) + 1):
@@ -1400,7 +1476,7 @@ class GanTrainer:
                     lo_, hi_ = ndist.shard_range(len(sel))              # rank: the constructor seeds the generator; gradients are item-weighted means)
                     sel = sel[lo_:hi_]
                 fb = dataio.FileBatches(sel, train_noise_path if mixer is None else None, batch=batch, drc_path=train_enh_path, workers=workers, ahead=2,
-                                        keep=2, device=self.device, mixer=mixer, epoch=gan_epoch)
+                                        keep=2, device=self.device, mixer=mixer, epoch=gan_epoch, rir_bank=rir_bank)
                 try:
                     res = self.run_epoch(gan_epoch, fb, vb if vb is not None else (), chkpt_path=os.path.join(pt_dir, 'chkpt_%d.pt' % gan_epoch),
                                          sample_dir=output_path, log_path=log_path, d_batch=batch)
@@ -1509,6 +1585,8 @@ class GanTrainer:
             sd['quality-model'] = self.D_Qua.state_dict()
         if self.norm != 'utterance':                 # (utterance-mode checkpoints stay what they were: the reference's two entries)
             sd['enhance-norm'] = self.norm
+        if getattr(self, 'room', None) is not None:  # the listener's room the targets were taken in: names, tau and a hash of the samples
+            sd['room'] = self.room.bank.record()
         torch.save(sd, path)
 
     def flush(self):
@@ -1525,6 +1603,12 @@ class GanTrainer:
         if recorded != self.norm and not allow_norm_mismatch:
             raise ValueError("load_checkpoint: %s was trained with norm=%r, this trainer runs norm=%r (allow_norm_mismatch=True loads it anyway)"
                              % (path, recorded, self.norm))
+        mine = self.room.bank.record() if getattr(self, 'room', None) is not None else None
+        self.loaded_room = ck.get('room')
+        if self.loaded_room != mine:
+            import warnings
+            what = lambda r: 'no room' if r is None else 'the room %s (tau %d, samples %s)' % (r['names'], r['tau'], r['hash'][:12])
+            warnings.warn("load_checkpoint: %s was trained for %s, this trainer scores in %s" % (path, what(self.loaded_room), what(mine)))
         self.G.load_state_dict(ck['enhance-model'])
         if 'intel-model' in ck:
             self.D.load_state_dict(ck['intel-model'])
@@ -1560,6 +1644,8 @@ def main(argv=None):
     ap.add_argument('--snr', default=None, help='comma-separated SNRs in dB drawn from with --noise-pool (default: -11,-9,-7,-5,-3,-1)')
     ap.add_argument('--snr-level', choices=('asl', 'rms'), default='asl', help='speech level of the SNR: ITU-T P.56 active speech level, or long-term mean square')
     ap.add_argument('--mix-seed', type=int, default=0)
+    ap.add_argument('--rir', default=None, help="folder of 16 kHz room impulse responses: targets are taken in the room a file's name gives ('<utt>#<rir>#...wav'; "
+                                                "no such RIR: anechoic)")
     from . import quality as _q
     _q.add_cli_arguments(ap)
     a = ap.parse_args(argv)
@@ -1576,7 +1662,11 @@ def main(argv=None):
     if a.quality:
         from . import quality
         scorer = quality.Scorer()
-    tr = GanTrainer(a.metrics, device='cuda:%d' % local, use_quality=a.quality, quality_scorer=scorer, norm=a.norm)
+    bank = None
+    if a.rir:
+        from . import room as _room
+        bank = _room.RirBank(a.rir, device='cuda:%d' % local)
+    tr = GanTrainer(a.metrics, device='cuda:%d' % local, use_quality=a.quality, quality_scorer=scorer, norm=a.norm, room=bank)
     for m_ in (tr.G, tr.D, tr.D_Qua):
         if m_ is not None:
             m_.precision = a.precision
@@ -1609,7 +1699,8 @@ def main(argv=None):
     try:
         tr.fit(train, None if mixer is not None else root + '/Train/Noise/', valid, valid_noise, train_enh_path=enh if os.path.isdir(enh) else None,
                epochs=a.epochs, sampling=a.sampling, valid_samples=a.valid_samples, batch=a.batch, output_path=a.output, pt_dir=a.chkpt, log_path=a.log,
-               first_epoch=a.first_epoch, clean_cache=not a.no_cache, on_epoch=report, mixer=mixer)
+               first_epoch=a.first_epoch, clean_cache=not a.no_cache, on_epoch=report, mixer=mixer,
+               rir_bank=bank)
     finally:
         if world > 1:
             import torch.distributed as tdist
