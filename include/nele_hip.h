@@ -483,7 +483,7 @@ int nele_metric_estoi_var(const float* x, const float* y, const int* lengths, in
  * {replication factor M, frames of the tiled signal, active frames, status bits: 1 M clamped, 4 active-frame
  * buffer clamped, 8 not enough active frames (reference raises; raw = NaN), 32 the utterance's covariance took the eigensolver's repair
  * path (nele_eigh_repaired: score unaffected, the call was slower)}.  The KLT eigenvectors come from
- * nele_eigh_sym_batched below. */
+ * nele_eigh_sym_batched_range below (only those of the components the score keeps). */
 long long nele_metric_siib_workspace_bytes(int B, int L);
 int nele_metric_siib(const float* x, const float* y, int B, int L, void* workspace, long long workspace_bytes, float* raw,
                      float* mapped, int* info, void* stream);
@@ -505,6 +505,10 @@ int nele_metric_siib_clean_sections(int B, int L, long long* out, int max_sectio
 /* Same with per-utterance lengths (the frame-periodic shortcut for L % 200 == 0 is not taken then; results are identical). */
 int nele_metric_siib_var(const float* x, const float* y, const int* lengths, int B, int L, void* workspace, long long workspace_bytes,
                          float* raw, float* mapped, int* info, int phase, void* stream);
+/* Diagnostic: kept_first [B] (HOST ints) = per utterance the first KLT component whose eigenvector the last phase 0 / 2 / 3 call on this
+ * workspace computed (nele_eigh_sym_batched_range with SIIB's cut 1e-10: the components below it never enter the score).  0 unless the
+ * utterance's tiled signal is frame-periodic (its length a multiple of 200 samples).  Synchronises the device. */
+int nele_metric_siib_kept_first(int B, int L, void* workspace, int* kept_first);
 
 /* Batched symmetric eigen-decomposition, float64, n <= 512 (np.linalg.eigh in pysiib's KLT): A [B][n][n] symmetric
  * (destroyed) -> lam [B][n] ascending, U [B][n][n] with ROW j = eigenvector j.  Householder tridiagonalisation,
@@ -523,6 +527,16 @@ int nele_metric_siib_var(const float* x, const float* y, const int* lengths, int
 long long nele_eigh_workspace_bytes(int B, int n);
 int nele_eigh_sym_batched(double* A, int n, int B, double* lam, double* U, void* workspace, long long workspace_bytes,
                           void* stream);
+/* Eigenvectors on request.  lam: all n eigenvalues, exactly as nele_eigh_sym_batched gives them.  U: eigenvector j only where
+ * lam[j] > rel_cut * lam[n-1], decided per matrix on the device (no read-back); rel_cut < 0 asks for all of them, rel_cut >= 1 and NaN
+ * are refused.  kept_first [B] (device ints, may be NULL) = the first such j of each matrix (n when there is none: A = 0, or no positive
+ * eigenvalue).  The inverse iteration and the back-transformation work on blocks of 64 vectors: a block that lies wholly below
+ * kept_first is skipped and its rows of U are ZERO; the block that holds kept_first is computed whole, so rows 64 * (kept_first / 64) ..
+ * n - 1 of U are bit-identical to nele_eigh_sym_batched's (a vector never depends on another one).  The contract above holds for them.
+ * A caller that discards the components of a rank-deficient matrix's null space (SIIB: rel_cut = 1e-10, half of the 420 at every
+ * length that is a multiple of 200 samples) saves their share of both kernels. */
+int nele_eigh_sym_batched_range(double* A, int n, int B, double* lam, double* U, void* workspace, long long workspace_bytes,
+                                void* stream, double rel_cut, int* kept_first);
 /* Matrices of the last nele_eigh_sym_batched call on `workspace` whose cluster tridiagonalisation gave up (its workgroups were not
  * co-resident within the spin limit, e.g. another process holds the GPU) and were redone by the single-workgroup repair kernel.
  * Synchronises the device.  0 on a GPU the launch fits on. */

@@ -21,11 +21,15 @@ int nele_set_error(int code, const char* fmt, ...);
 
 // csrc/eigh.hip (also part of the public C ABI)
 __attribute__((visibility("hidden"))) int nele_eigh_sym_batched_ex(double* A, int n, int B, double* lam, double* U, void* workspace,
-                                                                   long long workspace_bytes, void* stream, int cluster_batch);
+                                                                   long long workspace_bytes, void* stream, int cluster_batch,
+                                                                   double rel_cut, int* kept_first);
 __attribute__((visibility("hidden"))) const int* nele_eigh_flags(void* workspace, int B, int n);
+__attribute__((visibility("hidden"))) const int* nele_eigh_kfirst(void* workspace, int B, int n);
 extern "C" long long nele_eigh_workspace_bytes(int B, int n);
 extern "C" int nele_eigh_sym_batched(double* A, int n, int B, double* lam, double* U, void* workspace, long long workspace_bytes,
                                      void* stream);
+extern "C" int nele_eigh_sym_batched_range(double* A, int n, int B, double* lam, double* U, void* workspace, long long workspace_bytes,
+                                           void* stream, double rel_cut, int* kept_first);
 
 #define NELE_CHECK_ARG(cond, ...)                                   \
     do {                                                            \

@@ -37,6 +37,7 @@ struct EighWs {
     double* scl;    // [B] eigenvalue scale of matrix b: 2^k when eigh_prescale_kernel scaled T by 2^-k, 0 for T = 0
     int* flag;      // [B + 1] cluster tridiagonalisation gave up on matrix b (its workgroups were not co-resident within the spin limit):
                     //         the single-workgroup kernels skip it and eigh_tridiag_repair_kernel redoes it; [B] = matrices repaired (zeroed per call)
+    int* kfirst;    // [B] first eigenvector the last call computed (nele_eigh_sym_batched_range: those below are cut; 0 = all computed)
 };
 
 // ------------------------------------------------------------------------------------------ e1
@@ -2337,9 +2338,13 @@ __global__ __launch_bounds__(64) void eigh_invit_kernel(int n, EighWs ws, const 
 #ifndef IV2_FC
 #define IV2_FC 8           // iterate elements per prefetch chunk of the forward sweep
 #endif
-__global__ __launch_bounds__(64, IV2_OCC) void eigh_invit2_kernel(int n, EighWs ws, const double* __restrict__ lam_in, int extra) {
+// kfirst (nele_eigh_sym_batched_range; null = no cut): a workgroup whose 64 eigenvectors are all cut leaves at once.  A partly cut one runs
+// every lane as before - the kept vectors come from the same instructions whatever the cut.
+__global__ __launch_bounds__(64, IV2_OCC) void eigh_invit2_kernel(int n, EighWs ws, const double* __restrict__ lam_in, int extra,
+                                                                  const int* __restrict__ kfirst) {
     __shared__ double d[EG_MAXN], e[EG_MAXN];
     const int b = blockIdx.y, j = blockIdx.x * 64 + threadIdx.x;
+    if (kfirst && min((int)blockIdx.x * 64 + 64, n) <= kfirst[b]) return;
     for (int i = threadIdx.x; i < n; i += 64) { d[i] = ws.d[(size_t)b * n + i]; e[i] = ws.e[(size_t)b * n + i]; }
     __syncthreads();
     if (j >= n) return;
@@ -2750,9 +2755,18 @@ __global__ __launch_bounds__(256) void eigh_wy_t_kernel(const double* __restrict
 // grid (ceil(n / 64), B), block 256: wave w holds eigenvectors 64 blockIdx.x + 16 w ... + 15.  One workgroup per CU (the two V buffers
 // take 117 KB of LDS), so a wave may use the whole register file: WY_RT tiles x 4 doubles of Z per lane.
 template <int WY_RT>     // 16-row tiles held per lane: 27 covers n <= 432 (SIIB: 420), 32 covers EG_MAXN
-__global__ __launch_bounds__(256, 1) void eigh_backtransform_wy_kernel(const double* __restrict__ Aall, int n, EighWs ws, double* __restrict__ U) {
+// kfirst as in eigh_invit2_kernel: a workgroup whose eigenvectors are all cut writes zeros to its rows of U (the inverse iteration left
+// nothing in zt for them) and leaves.
+__global__ __launch_bounds__(256, 1) void eigh_backtransform_wy_kernel(const double* __restrict__ Aall, int n, EighWs ws, double* __restrict__ U,
+                                                                       const int* __restrict__ kfirst) {
     extern __shared__ double wy_sm[];                       // Vs[2][16 WY_RT][WY_LD], Ts[2][16][WY_LD]
     constexpr int NR = 16 * WY_RT;
+    if (kfirst && min((int)blockIdx.x * 64 + 64, n) <= kfirst[blockIdx.y]) {
+        const int r0 = blockIdx.x * 64, cnt = (min(r0 + 64, n) - r0) * n;           // rows r0 .. of U are contiguous
+        double* Uz = U + ((size_t)blockIdx.y * n + r0) * n;
+        for (int i = threadIdx.x; i < cnt; i += 256) Uz[i] = 0.0;
+        return;
+    }
     double* Vs = wy_sm;
     double* Ts = wy_sm + 2 * NR * WY_LD;
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, g = lane >> 4;
@@ -2903,6 +2917,29 @@ __global__ __launch_bounds__(256) void eigh_postscale_kernel(int n, EighWs ws, d
     for (int j = threadIdx.x; j < n; j += 256) lam[(size_t)b * n + j] *= back;
 }
 
+// ------------------------------------------------------------------------------------------ eigenvectors on request
+// nele_eigh_sym_batched_range: eigenvector j is wanted when lam[j] > rel_cut * lam[n - 1].  The eigenvalues are ascending, so the wanted
+// ones are j = kfirst .. n - 1 with kfirst the FIRST wanted index (equal eigenvalues may sit an ulp out of order: nothing wanted is ever
+// below kfirst).  One wave per matrix.  It runs before the inverse iteration, on the eigenvalues of the scaled T, and multiplies by the
+// scale as eigh_postscale_kernel will (a power of two, or 0 for T = 0): the comparison is the one on the eigenvalues the caller gets.
+// T = 0 or a largest eigenvalue <= 0 cuts everything (kfirst = n).
+__global__ __launch_bounds__(64) void eigh_cut_kernel(int n, EighWs ws, const double* __restrict__ lam, double rel_cut, int* __restrict__ kfirst,
+                                                      int* __restrict__ kept_first) {
+    const int b = blockIdx.x;
+    const double* l = lam + (size_t)b * n;
+    const double back = ws.scl[b];
+    const double thr = rel_cut * (l[n - 1] * back);
+    int first = n;
+    for (int j = threadIdx.x; j < n; j += 64)
+        if (l[j] * back > thr) first = min(first, j);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o, 64));
+    if (threadIdx.x == 0) {
+        kfirst[b] = first;
+        if (kept_first) kept_first[b] = first;
+    }
+}
+
 // ------------------------------------------------------------------------------------------ C ABI
 static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
@@ -2919,6 +2956,7 @@ static size_t eigh_layout(int B, int n, EighWs* w, char* base) {
     TAKE(xch, uint4, (size_t)B * EG_XCH * EG_MAXN);
     TAKE(scl, double, (size_t)B);
     TAKE(flag, int, (size_t)B + 64);
+    TAKE(kfirst, int, (size_t)B);
 #undef TAKE
     return o;
 }
@@ -2950,18 +2988,34 @@ const int* nele_eigh_flags(void* workspace, int B, int n) {
     return ws.flag;
 }
 
+// Device pointer to kfirst [B] of a workspace: the first eigenvector the last call on it computed.  Internal (SIIB's diagnostic read-back).
+const int* nele_eigh_kfirst(void* workspace, int B, int n) {
+    EighWs ws;
+    eigh_layout(B, n, &ws, (char*)workspace);
+    return ws.kfirst;
+}
+
 // A [B][n][n] symmetric (destroyed: holds the Householder reflectors on exit) -> lam [B][n] ascending,
 // U [B][n][n] with row j = eigenvector j.  U may alias A? No: U must be a different buffer.
 extern "C" int nele_eigh_sym_batched(double* A, int n, int B, double* lam, double* U, void* workspace, long long workspace_bytes,
                                      void* stream) {
-    return nele_eigh_sym_batched_ex(A, n, B, lam, U, workspace, workspace_bytes, stream, 0);
+    return nele_eigh_sym_batched_ex(A, n, B, lam, U, workspace, workspace_bytes, stream, 0, -1.0, nullptr);
+}
+
+// The same, with eigenvectors only where lam[j] > rel_cut * lam[n - 1] (decided per matrix on the device; rel_cut < 0: all of them).
+// kept_first [B] (device, may be null) receives the first computed index of each matrix.  Rows of U that belong to a 64-vector block
+// below it are zero; the cut rows of the block that holds it are computed as ever.
+extern "C" int nele_eigh_sym_batched_range(double* A, int n, int B, double* lam, double* U, void* workspace, long long workspace_bytes,
+                                           void* stream, double rel_cut, int* kept_first) {
+    return nele_eigh_sym_batched_ex(A, n, B, lam, U, workspace, workspace_bytes, stream, 0, rel_cut, kept_first);
 }
 
 // Internal entry point (not exported): `cluster_batch` = matrices per cluster launch the caller wants (8 .. 64, 0 = no preference: 64).
 // An explicit argument - it used to be a mutable global "hint" set around the call, which two host threads could read crosswise.
 int nele_eigh_sym_batched_ex(double* A, int n, int B, double* lam, double* U, void* workspace, long long workspace_bytes, void* stream,
-                             int cluster_batch) {
+                             int cluster_batch, double rel_cut, int* kept_first) {
     NELE_CHECK_ARG(A && lam && U && workspace && B > 0 && n >= 2, "nele_eigh_sym_batched: bad arguments");
+    NELE_CHECK_ARG(rel_cut == rel_cut && rel_cut < 1.0, "nele_eigh_sym_batched_range: rel_cut must be below 1");
     NELE_CHECK_ARG(A != U, "nele_eigh_sym_batched: U must not alias A");
     if (n > EG_MAXN) return nele_set_error(NELE_ERR_UNSUPPORTED, "nele_eigh_sym_batched: n=%d > %d", n, EG_MAXN);
     if (workspace_bytes < nele_eigh_workspace_bytes(B, n)) return nele_set_error(NELE_ERR_WORKSPACE, "nele_eigh_sym_batched: workspace too small");
@@ -3088,12 +3142,20 @@ int nele_eigh_sym_batched_ex(double* A, int n, int B, double* lam, double* U, vo
     // bisected to 1 ulp one is enough for every test matrix (eigenvalues 1e-13, residual 1e-11, orthogonality 1e-8, SIIB unchanged to 17
     // digits) and saves a quarter of this kernel's HBM traffic (its work arrays: 108 KB per eigenvector); 0 fails the residual test
     const int iv_extra = NELE_SWITCH_INT("NELE_EIGH_INVIT_EXTRA", 1);
+    // eigenvectors on request: only the blocked back-transformation knows how to skip (the superseded variants compute every vector)
+    const int wy_on = NELE_SWITCH_INT("NELE_EIGH_WY", 1);   // =0: the reflector-by-reflector back-transformation (A/B diagnostic)
+    const bool ranged = rel_cut >= 0.0 && wy_on && !NELE_SWITCH_INT("NELE_EIGH_INVIT_STORE", 0);
+    const int* kf = ranged ? ws.kfirst : nullptr;
+    if (ranged) hipLaunchKernelGGL(eigh_cut_kernel, dim3(B), dim3(64), 0, s, n, ws, lam, rel_cut, ws.kfirst, kept_first);
+    else {
+        if (hipMemsetAsync(ws.kfirst, 0, sizeof(int) * (size_t)B, s) != hipSuccess) return nele_set_error(NELE_ERR_HIP, "nele_eigh_sym_batched: memset failed");
+        if (kept_first && hipMemsetAsync(kept_first, 0, sizeof(int) * (size_t)B, s) != hipSuccess) return nele_set_error(NELE_ERR_HIP, "nele_eigh_sym_batched: memset failed");
+    }
     // NELE_EIGH_INVIT_STORE=1 (test library): the kernel that stores the LU factors instead of recomputing them (bit-identical; 6.2 GB per 256 matrices)
     if (NELE_SWITCH_INT("NELE_EIGH_INVIT_STORE", 0)) { NELE_AB_ONLY(hipLaunchKernelGGL(eigh_invit_kernel, dim3((n + 63) / 64, B), dim3(64), 0, s, n, ws, lam, iv_extra);) }
-    else hipLaunchKernelGGL(eigh_invit2_kernel, dim3((n + 63) / 64, B), dim3(64), 0, s, n, ws, lam, iv_extra);
+    else hipLaunchKernelGGL(eigh_invit2_kernel, dim3((n + 63) / 64, B), dim3(64), 0, s, n, ws, lam, iv_extra, kf);
     hipLaunchKernelGGL(eigh_postscale_kernel, dim3(B), dim3(256), 0, s, n, ws, lam);
     const size_t lds = sizeof(double) * (2 * (size_t)BT_CH * 16 * (n <= 448 ? 28 : 32) + 2 * BT_CH);
-    const int wy_on = NELE_SWITCH_INT("NELE_EIGH_WY", 1);   // =0: the reflector-by-reflector back-transformation (A/B diagnostic)
     NELE_ONCE_PER_DEVICE({
         NELE_AB_ONLY((void)hipFuncSetAttribute(reinterpret_cast<const void*>(eigh_backtransform_kernel<28>), hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
                      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(eigh_backtransform_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);)
@@ -3103,8 +3165,8 @@ int nele_eigh_sym_batched_ex(double* A, int n, int B, double* lam, double* U, vo
     if (wy_on) {
         const int nblk = (n - 1 + WY_NB - 1) / WY_NB;
         hipLaunchKernelGGL(eigh_wy_t_kernel, dim3((nblk + 3) / 4, B), dim3(256), 0, s, A, n, ws);
-        if (n <= 432) hipLaunchKernelGGL(eigh_backtransform_wy_kernel<27>, dim3((n + 63) / 64, B), dim3(256), sizeof(double) * (2 * 432 * WY_LD + 2 * 16 * WY_LD), s, A, n, ws, U);
-        else hipLaunchKernelGGL(eigh_backtransform_wy_kernel<32>, dim3((n + 63) / 64, B), dim3(256), sizeof(double) * (2 * 512 * WY_LD + 2 * 16 * WY_LD), s, A, n, ws, U);
+        if (n <= 432) hipLaunchKernelGGL(eigh_backtransform_wy_kernel<27>, dim3((n + 63) / 64, B), dim3(256), sizeof(double) * (2 * 432 * WY_LD + 2 * 16 * WY_LD), s, A, n, ws, U, kf);
+        else hipLaunchKernelGGL(eigh_backtransform_wy_kernel<32>, dim3((n + 63) / 64, B), dim3(256), sizeof(double) * (2 * 512 * WY_LD + 2 * 16 * WY_LD), s, A, n, ws, U, kf);
     }
     NELE_AB_ONLY(else if (n <= 448) hipLaunchKernelGGL(eigh_backtransform_kernel<28>, dim3((n + 31) / 32, B), dim3(256), lds, s, A, n, ws, U);
                  else hipLaunchKernelGGL(eigh_backtransform_kernel<32>, dim3((n + 31) / 32, B), dim3(256), lds, s, A, n, ws, U);)

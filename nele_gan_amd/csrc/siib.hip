@@ -26,6 +26,10 @@
 #define SB_EPS 2.220446049250313e-16
 #define SB_MMAX 40
 
+// KLT components with lam[j] <= SB_RELCUT * max lam carry no information (the reference's cut, oracle/siib.py): the score skips them,
+// the eigensolver is asked for the others only and the quadratic forms are formed on the others only.
+#define SB_RELCUT 1e-10
+
 struct SiibWs {
     double* g2;      // [28][201] squared gammatone magnitude responses
     double* tab;     // [3][400] cos(2 pi j / 400), sin(2 pi j / 400), hann400(j)
@@ -1150,12 +1154,19 @@ __global__ __launch_bounds__(256) void siib_assemble_kernel(SiibWs ws) {
 // S is symmetric (siib_assemble_kernel stores its upper triangle only), so q_k = 2 sum_{i<j} u_i S_ij u_j + sum_i S_ii u_i^2:
 // the product only runs over the rows i <= j of a column tile (S staged as its strict upper triangle + half the diagonal, the row sums
 // doubled) - 60 % of the multiply-adds of the full product.
-__global__ __launch_bounds__(256) void siib_quad_kernel(SiibWs ws) {
+// skip_cut: a row tile none of whose components the score keeps (siib_final_lag_kernel's own test on lam, which is part of the cached
+// clean state: phase 4 after a cache fill decides the same) is dropped - its qpart entries are never read.
+__global__ __launch_bounds__(256) void siib_quad_kernel(SiibWs ws, int skip_cut) {
     __shared__ __attribute__((aligned(32))) double Us[2][16][SG_LD], Mt[2][16][SG_LD];
     const int xw = (int)blockIdx.x, slot = xw >> 3, per_b = 7 * 14;
     const int b = (slot / per_b) * 8 + (xw & 7), tl = slot % per_b, by = tl % 7, bx = tl / 7;
     if (b >= ws.Bn) return;
     const int which = bx / 7, ti = by * 64, t0 = (bx % 7) * 64, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if (skip_cut) {
+        const double* lam = ws.lam + (size_t)b * SB_D;
+        const bool kept = tid < 64 && ti + tid < SB_D && lam[ti + tid] > SB_RELCUT * lam[SB_D - 1];
+        if (!__syncthreads_or(kept)) return;
+    }
     const int li = lane & 15, lk = lane >> 4;
     const double* U = ws.U + (size_t)b * SB_D * SB_D;
     const double* M = ws.S2 + ((size_t)b * 2 + which) * SB_D * SB_D;
@@ -1222,7 +1233,7 @@ __global__ __launch_bounds__(512) void siib_final_lag_kernel(SiibWs ws, float* _
     if (j < SB_D) lmax = lam[j];
     lmax = block_max(lmax, red);
     double I = 0.0;
-    if (j < SB_D && lam[j] > 1e-10 * lmax) {
+    if (j < SB_D && lam[j] > SB_RELCUT * lmax) {
         const double* q = ws.qpart + ((size_t)b * SB_D + j) * 14;
         double vy = 0.0, cxy = 0.0;
         for (int t = 0; t < 7; ++t) { vy += q[t]; cxy += q[7 + t]; }
@@ -1253,7 +1264,7 @@ __global__ __launch_bounds__(512) void siib_final_kernel(SiibWs ws, float* __res
     if (j < SB_D) lmax = lam[j];
     lmax = block_max(lmax, red);
     double I = 0.0;
-    if (j < SB_D && lam[j] > 1e-10 * lmax) {
+    if (j < SB_D && lam[j] > SB_RELCUT * lmax) {
         double vx = 0, vy = 0, cxy = 0;
         const double* p = ws.part + ((size_t)b * SB_D + j) * ws.NTL * 3;
         for (int t = 0; t < ws.NTL; ++t) { vx += p[3 * t]; vy += p[3 * t + 1]; cxy += p[3 * t + 2]; }
@@ -1394,6 +1405,8 @@ extern "C" int nele_metric_siib_var(const float* x, const float* y, const int* l
     int g = L, r = SB_SHIFT;
     while (r) { const int t = g % r; g = r; r = t; }
     const bool dedup = NELE_SWITCH_INT("NELE_SIIB_DEDUP", 1) != 0;
+    // NELE_SIIB_EIGRANGE=0 (A/B switch): every eigenvector and every quadratic form, also those of components the score cuts
+    const bool eigrange = NELE_SWITCH_INT("NELE_SIIB_EIGRANGE", 1) != 0;
     // frame period of the tiled signal (NELE_SIIB_DEDUP=0: A/B switch, every frame computed; per-utterance lengths: every row has its
     // own period, the shortcut is not taken)
     const int Pf = (dedup && !lengths) ? L / g : 0x7fffffff;
@@ -1446,7 +1459,8 @@ extern "C" int nele_metric_siib_var(const float* x, const float* y, const int* l
     }
     if (eig) {
         // phase 3 runs beside the G-step: 32 matrices per cluster launch leave half of the chip to it (eigh.hip)
-        int st = nele_eigh_sym_batched_ex(ws.C, SB_D, B, ws.lam, ws.U, ws.eigws, nele_eigh_workspace_bytes(B, SB_D), stream, (phase == 3) ? 32 : 64);
+        int st = nele_eigh_sym_batched_ex(ws.C, SB_D, B, ws.lam, ws.U, ws.eigws, nele_eigh_workspace_bytes(B, SB_D), stream, (phase == 3) ? 32 : 64,
+                                          eigrange ? SB_RELCUT : -1.0, nullptr);
         if (st) return st;
         if (phase == 3 && !siib_lag_path()) {               // clean-signal half of the projections, beside whatever the caller overlaps
             NELE_AB_ONLY(hipLaunchKernelGGL(siib_proj_kernel<1>, dim3(7 * ws.NTL * 8 * ((B + 7) / 8)), dim3(256), 0, s, ws);)
@@ -1454,7 +1468,7 @@ extern "C" int nele_metric_siib_var(const float* x, const float* y, const int* l
         }
     }
     if (fin && siib_lag_path()) {
-        hipLaunchKernelGGL(siib_quad_kernel, dim3(7 * 14 * 8 * ((B + 7) / 8)), dim3(256), 0, s, ws);
+        hipLaunchKernelGGL(siib_quad_kernel, dim3(7 * 14 * 8 * ((B + 7) / 8)), dim3(256), 0, s, ws, eigrange ? 1 : 0);
         hipLaunchKernelGGL(siib_final_lag_kernel, dim3(B), dim3(512), 0, s, ws, raw, mapped, nele_eigh_flags(ws.eigws, B, SB_D));
         if (info_out) (void)hipMemcpyAsync(info_out, ws.info, sizeof(int) * 4 * (size_t)B, hipMemcpyDeviceToDevice, s);
         NELE_CHECK_LAUNCH("nele_metric_siib(back, lag path)");
@@ -1465,6 +1479,18 @@ extern "C" int nele_metric_siib_var(const float* x, const float* y, const int* l
         if (info_out) (void)hipMemcpyAsync(info_out, ws.info, sizeof(int) * 4 * (size_t)B, hipMemcpyDeviceToDevice, s);
         NELE_CHECK_LAUNCH("nele_metric_siib(back)");
     }
+    return NELE_OK;
+}
+
+// First KLT component per utterance the eigensolver computed in the last phase 0 / 2 / 3 call on this workspace (host array [B];
+// synchronises the device).  0 = nothing was cut (lengths that are not frame-periodic, NELE_SIIB_EIGRANGE=0).
+extern "C" int nele_metric_siib_kept_first(int B, int L, void* workspace, int* kept_first) {
+    NELE_CHECK_ARG(B > 0 && workspace && kept_first, "nele_metric_siib_kept_first: bad arguments");
+    SiibWs ws;
+    siib_layout(B, L, &ws, (char*)workspace);
+    if (hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(kept_first, nele_eigh_kfirst(ws.eigws, B, SB_D), sizeof(int) * (size_t)B, hipMemcpyDeviceToHost) != hipSuccess)
+        return nele_set_error(NELE_ERR_HIP, "nele_metric_siib_kept_first: copy failed");
     return NELE_OK;
 }
 

@@ -67,6 +67,10 @@ _lib._SIGS['nele_haspi_dither_rows'] = _lib.lib.nele_haspi_dither_rows.argtypes
 
 declare('nele_eigh_sym_batched', [_P, c_int, c_int, _P, _P, _P, c_longlong, _P])
 _lib._SIGS['nele_eigh_sym_batched'] = _lib.lib.nele_eigh_sym_batched.argtypes
+declare('nele_eigh_sym_batched_range', [_P, c_int, c_int, _P, _P, _P, c_longlong, _P, ctypes.c_double, _P])
+_lib._SIGS['nele_eigh_sym_batched_range'] = _lib.lib.nele_eigh_sym_batched_range.argtypes
+declare('nele_metric_siib_kept_first', [c_int, c_int, _P, ctypes.POINTER(c_int)])
+_lib._SIGS['nele_metric_siib_kept_first'] = _lib.lib.nele_metric_siib_kept_first.argtypes
 _lib.lib.nele_eigh_repaired.argtypes = [_P, c_int, c_int]
 _lib.lib.nele_eigh_repaired.restype = c_int
 _lib._SIGS['nele_eigh_repaired'] = _lib.lib.nele_eigh_repaired.argtypes
@@ -265,6 +269,27 @@ def eigh_batched(A, return_repaired=False):
     if return_repaired:
         return lam, U, int(_lib.lib.nele_eigh_repaired(ptr(ws), B, n))
     return lam, U
+
+
+def eigh_batched_range(A, rel_cut, poison=False):
+    """eigh_batched with eigenvectors on request (nele_eigh_sym_batched_range): -> (eigenvalues [B,n], U [B,n,n], kept_first [B] int32).
+    Rows of U below 64 * (kept_first // 64) are zero.  poison: U and kept_first start as NaN / -1 (tests: what is not written shows)."""
+    A = A.clone().contiguous()
+    B, n, _ = A.shape
+    lam = torch.empty((B, n), dtype=torch.float64, device=A.device)
+    U = torch.full_like(A, float('nan')) if poison else torch.empty_like(A)
+    kf = torch.full((B,), -1, dtype=torch.int32, device=A.device)
+    ws = _workspace('eigh', _lib.lib.nele_eigh_workspace_bytes(B, n), A.device)
+    call('nele_eigh_sym_batched_range', ptr(A), n, B, ptr(lam), ptr(U), ptr(ws), ws.numel(), stream(), float(rel_cut), ptr(kf))
+    return lam, U, kf
+
+
+def siib_kept_first(ws, B, L):
+    """Per utterance, the first KLT component the eigensolver computed in the last SIIB call (phase 0 / 2 / 3) on workspace ``ws``
+    (numpy int32 [B]; synchronises)."""
+    out = (c_int * int(B))()
+    call('nele_metric_siib_kept_first', int(B), int(L), ptr(ws), out)
+    return np.frombuffer(out, dtype=np.int32).copy()
 
 
 def _pair(x, y):
