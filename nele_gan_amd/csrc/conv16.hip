@@ -414,13 +414,11 @@ static bool c16_plan(int N, const ConvGeom& g, int KH, int KW, C16Plan* pl, int 
     q.sps = (g.seglen + 31) >> 5;
     const int nsteps = KH * q.sps;
     // tile rows: 8 where the layer is bound by memory (little work per staged byte) and the registers / LDS allow, else 4
-    const int th_env = NELE_SWITCH_INT("NELE_CONV16_TH", 0);
     int th = (nsteps * q.TN <= 64 && q.TN <= 2) ? 8 : 4;      // (TN >= 3 with 8 rows: 256 registers, fragments no longer double-buffered - D.conv5 forward 1.54 against 1.30 ms)
     // ... except for data gradients: their epilogue loads the forward activation for the LeakyReLU mask, and twice the workgroups hide that
     // latency better than 8-row tiles save prologues (conv3's data gradient 0.285 -> 0.222 ms, conv2's 0.137 -> 0.118 at B = 256; the
     // forward passes of the same layers lose 4 - 8 % with 4 rows)
     if (epi == EPI_MASK_LRELU_GRAD) th = 4;
-    if (th_env == 4 || (th_env == 8 && q.TN <= 2)) th = th_env;
     q.TH = th;
     // 16-byte fragment reads of 16 consecutive positions: conflict-free at stride 16, 32 and 96 bytes (C = 8, 16, 48); at 64 / 128 bytes
     // the units of a position are XOR-swizzled by the position index (checked against the ds_read_b128 lane groups of MI355X_MICROARCH.md)

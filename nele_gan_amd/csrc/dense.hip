@@ -2844,38 +2844,18 @@ static int conv1d16_sb(const ConvGeom& g, int N, int KH, int KW, size_t* lds_out
     }
     return 0;
 }
-// Tile height.  Default: see below.  NELE_CONV_TH=4|8|10|11|13 forces one height where it fits; NELE_CONV_TALL=1 picks among {13, 11, 10, 8, 4} the candidate that
-// wastes the fewest output rows (D.conv5, Hout = 44: 11; D.conv4, 52: 13; the 58-row gradients: 10) - a taller tile also needs fewer LDS
-// reads per MFMA (TH + TN fragment reads per TH * TN MFMAs).  Measured at B = 256 (A/B inside one run, tools/ab.sh): D.conv5 forward alone
-// 1.70 -> 1.62 ms (0.305 -> 0.32 of the bf16 peak), but the whole step 75.6 -> 76.9 ms: the taller tile's 160 KB of LDS leaves no room for
-// the metric streams' workgroups beside it, and at B = 256 the step is bound by the sum of all kernels, not by the convolutions.  (The
-// converse also holds: 4-row tiles make the kernel 17 % slower alone and the step 0.5 ms faster.)  Hence opt-in.
+// Tile height: 4 or 8 rows.  Taller tiles (10, 11 or 13 rows, whichever wastes the fewest output rows) need fewer LDS reads per MFMA and
+// made D.conv5 forward alone faster at B = 256 (1.70 -> 1.62 ms), but the whole step slower (75.6 -> 76.9 ms): their 160 KB of LDS leaves
+// no room for the metric streams' workgroups beside them, and the step is bound by the sum of all kernels, not by the convolutions.
 static int tile16_th(const ConvGeom& g, int N, int KH, int KW) {
-    const int tall = NELE_SWITCH_INT("NELE_CONV_TALL", 0);
-    const int force = NELE_SWITCH_INT("NELE_CONV_TH", 0);                                     // NELE_CONV_TH=4|8: force one tile height where it fits (A/B)
-    if (force == 4 || force == 8 || force == 10 || force == 11 || force == 13) {
-        if ((force == 4 || g.Hout >= 8) && tile16_lds(g, N, KH, KW, force)) return force;
-    }
-    if (!tall) {
-        // 64 output channels (D.conv5 forward, the 64-wide gradients): 8-row tiles; fewer channels: 4-row tiles.  Measured inside the
-        // B = 256 step (tools/ab.sh, three alternating repetitions): all 8-row 75.5 ms, all 4-row 73.9 ms (but D.conv5 forward alone
-        // 1.96 instead of 1.70 ms), this mix 73.9 ms with D.conv5 at 1.74 ms: the narrow layers (TN <= 3) are bound by their LDS reads
-        // either way, and the smaller halo leaves room for the workgroups of the other streams.
-        if (N < 64 && tile16_lds(g, N, KH, KW, 4)) return 4;
-        if (g.Hout >= 8 && tile16_lds(g, N, KH, KW, 8)) return 8;
-        if (tile16_lds(g, N, KH, KW, 4)) return 4;
-        return 0;
-    }
-    const int cand[5] = {13, 11, 10, 8, 4};
-    int best = 0, bestrows = 1 << 30;
-    for (int q = 0; q < 5; ++q) {
-        const int th = cand[q];
-        if (th > 4 && g.Hout < 8) continue;
-        if (!tile16_lds(g, N, KH, KW, th)) continue;
-        const int rows = (g.Hout + th - 1) / th * th;
-        if (rows < bestrows) { bestrows = rows; best = th; }
-    }
-    return best;
+    // 64 output channels (D.conv5 forward, the 64-wide gradients): 8-row tiles; fewer channels: 4-row tiles.  Measured inside the
+    // B = 256 step (tools/ab.sh, three alternating repetitions): all 8-row 75.5 ms, all 4-row 73.9 ms (but D.conv5 forward alone
+    // 1.96 instead of 1.70 ms), this mix 73.9 ms with D.conv5 at 1.74 ms: the narrow layers (TN <= 3) are bound by their LDS reads
+    // either way, and the smaller halo leaves room for the workgroups of the other streams.
+    if (N < 64 && tile16_lds(g, N, KH, KW, 4)) return 4;
+    if (g.Hout >= 8 && tile16_lds(g, N, KH, KW, 8)) return 8;
+    if (tile16_lds(g, N, KH, KW, 4)) return 4;
+    return 0;
 }
 static int span16_supported(int M, int N, const ConvGeom& g, int KH, int KW) {
     if (N > 64 || g.C % 8 || g.Wout < 64 || KH * g.seglen != g.Ktot || KW * g.C != g.seglen) return 0;
@@ -2928,11 +2908,10 @@ static int conv_span_bf16_impl(const float* A, const void* Wfrag, const float* b
     NELE_CHECK_ARG(!(epi == EPI_BIAS || epi == EPI_BIAS_LRELU || epi == EPI_BIAS_EXPTANH) || bias, "nele_conv_span_bf16: epilogue needs bias");
     NELE_CHECK_ARG(epi != EPI_MASK_LRELU_GRAD || aux, "nele_conv_span_bf16: epilogue needs aux");
     hipStream_t s = as_stream(stream);
-    const int tile_on = NELE_SWITCH_INT("NELE_CONV_TILE", 1);
-    const int th = (tile_on && p.g.Wout >= 32) ? tile16_th(p.g, N, KH, KW) : 0;
+    const int th = (p.g.Wout >= 32) ? tile16_th(p.g, N, KH, KW) : 0;
     {   // Conv1d / Linear geometry (KH = 1): strip kernel
         size_t clds = 0;
-        const int csb = (tile_on && KH == 1 && p.g.Wout >= 32) ? conv1d16_sb(p.g, N, KH, KW, &clds) : 0;
+        const int csb = (KH == 1 && p.g.Wout >= 32) ? conv1d16_sb(p.g, N, KH, KW, &clds) : 0;
         if (csb) {
             Tile16Args t;
             t.A = A; t.Wfrag = p.Wfrag; t.bias = bias; t.aux = aux; t.out = out; t.N = N; t.NT = p.NT; t.epi = epi; t.slope = slope;
@@ -2946,9 +2925,8 @@ static int conv_span_bf16_impl(const float* A, const void* Wfrag, const float* b
             }
             const int nchunksN = (N > 64) ? N / 64 : 1, TNsel = (N >= 64) ? 4 : p.NT;
             const int nstrips = ((p.g.Wout + C1D_TW - 1) / C1D_TW) * BH;
-            const int walk_on = NELE_SWITCH_INT("NELE_CONV1D_WALK", 1);                       // NELE_CONV1D_WALK=0: one workgroup per (strip, N chunk) at every batch (A/B)
             const size_t ep_bytes = 4 * 16 * 68 * 4;
-            const bool walk = walk_on && nchunksN > 1 && nstrips >= 256 && clds + 4096 + ep_bytes <= 158 * 1024;
+            const bool walk = nchunksN > 1 && nstrips >= 256 && clds + 4096 + ep_bytes <= 158 * 1024;
             t.ntiles = walk ? 1 : nchunksN; t.ncl = walk ? nchunksN : 1; t.SBH = BH;
             if (walk) clds = ((clds + 2047) & ~(size_t)2047) + 4096 + ep_bytes;
             const dim3 grid((unsigned)(t.ntiles * 8 * ((nstrips + 7) / 8)));
@@ -2973,9 +2951,6 @@ static int conv_span_bf16_impl(const float* A, const void* Wfrag, const float* b
 #define TILE16_ATTR(TN_, TH_) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_tile16_kernel<TN_, TH_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
             TILE16_ATTR(1, 8); TILE16_ATTR(2, 8); TILE16_ATTR(3, 8); TILE16_ATTR(4, 8);
             TILE16_ATTR(1, 4); TILE16_ATTR(2, 4); TILE16_ATTR(3, 4); TILE16_ATTR(4, 4);
-            TILE16_ATTR(1, 10); TILE16_ATTR(2, 10); TILE16_ATTR(3, 10); TILE16_ATTR(4, 10);
-            TILE16_ATTR(1, 11); TILE16_ATTR(2, 11); TILE16_ATTR(3, 11); TILE16_ATTR(4, 11);
-            TILE16_ATTR(1, 13); TILE16_ATTR(2, 13); TILE16_ATTR(3, 13); TILE16_ATTR(4, 13);
 #undef TILE16_ATTR
         }
         t.ntiles = ((p.g.Wout + TILE16_TW - 1) / TILE16_TW) * ((p.g.Hout + th - 1) / th) * B_;
@@ -2983,9 +2958,6 @@ static int conv_span_bf16_impl(const float* A, const void* Wfrag, const float* b
 #define TILE16_LAUNCH(TN_, TH_) hipLaunchKernelGGL((conv_tile16_kernel<TN_, TH_>), grid, dim3(256), lds, s, t)
 #define TILE16_PICK(TH_) switch (p.NT) { case 1: TILE16_LAUNCH(1, TH_); break; case 2: TILE16_LAUNCH(2, TH_); break; case 3: TILE16_LAUNCH(3, TH_); break; default: TILE16_LAUNCH(4, TH_); break; }
         switch (th) {
-            case 13: TILE16_PICK(13); break;
-            case 11: TILE16_PICK(11); break;
-            case 10: TILE16_PICK(10); break;
             case 8: TILE16_PICK(8); break;
             default: TILE16_PICK(4); break;
         }
@@ -3044,15 +3016,10 @@ extern "C" int nele_conv_wgrad_bf16(const float* A, const float* dOut, float* wo
                                     const int* geom, int KH, int KW, int Cvalid, float* dW, float* db, int accumulate, void* stream) {
     return conv_wgrad_impl(A, dOut, workspace, workspace_floats, M, N, geom, KH, KW, Cvalid, dW, db, accumulate, 1, stream);
 }
-static bool wgrad_dma_on() {                               // NELE_WGRAD_DMA=0: the one-kernel-row tile kernel for bf16 operands too (A/B diagnostic)
-    const int on = NELE_SWITCH_INT("NELE_WGRAD_DMA", 1);
-    return on != 0;
-}
 static bool wgrad_tile_eligible(int M, int N, const ConvGeom& g, int KH, int KW) {
-    const int wt_on = NELE_SWITCH_INT("NELE_WGRAD_TILE", 1);
     const int nkt = (g.seglen + 15) / 16;
     const long long wt_lds = ((long long)WT_TH * (WT_TW + KW - 1) * g.C + WT_SLACK + 256 * WT_NP_OF((N + 15) / 16)) * 2;
-    return wt_on && N <= 64 && g.C % 8 == 0 && KW * g.C == g.seglen && nkt <= 28 && g.Wout >= 32 && wt_lds <= 76 * 1024 &&
+    return N <= 64 && g.C % 8 == 0 && KW * g.C == g.seglen && nkt <= 28 && g.Wout >= 32 && wt_lds <= 76 * 1024 &&
            M % (g.Hout * g.Wout) == 0;
 }
 extern "C" int nele_conv_wgrad_bf16_d16_supported(int M, int N, const int* geom, int KH, int KW) {
@@ -3119,7 +3086,6 @@ static int conv_wgrad_impl(const float* A, const float* dOut, float* workspace, 
         if (prof_w) nele_prof_mark(s);
     }
     // 2-D tile kernel (bf16): one kernel row per workgroup, accumulators in registers over all position tiles
-    const int wt_on = NELE_SWITCH_INT("NELE_WGRAD_TILE", 1);
     // Layers too wide for one workgroup's accumulators (N > 64 or more than 28 reduction tiles per kernel row: the generator's Conv1d
     // layers, 256 x 7 x 256) run on the same tile kernel as subs_n x subs_c sub-problems of 64 output x 64 input channels that share
     // every group's position tiles; a Conv1d batch is viewed as ONE image whose rows are the utterances (KH = 1: rows are independent),
@@ -3128,7 +3094,7 @@ static int conv_wgrad_impl(const float* A, const float* dOut, float* workspace, 
     ConvGeom gt = p.g;                                     // geometry the tile kernel sees
     int Nt = N, subs_n = 1, subs_c = 1, Bt = M / (p.g.Hout * p.g.Wout);
     bool sliced = false;
-    if (bf16 && (!d16 || a16) && wt_on && !wgrad_tile_eligible(M, N, p.g, KH, KW) && N % 64 == 0 && p.g.C % 64 == 0 && KW * p.g.C == p.g.seglen &&
+    if (bf16 && (!d16 || a16) && !wgrad_tile_eligible(M, N, p.g, KH, KW) && N % 64 == 0 && p.g.C % 64 == 0 && KW * p.g.C == p.g.seglen &&
         KW * 4 <= 28 && p.g.Wout >= 32 && M % (p.g.Hout * p.g.Wout) == 0) {
         gt.C = 64; gt.seglen = KW * 64; gt.Ktot = KH * KW * 64;
         Nt = 64; subs_n = N / 64; subs_c = p.g.C / 64;
@@ -3141,13 +3107,9 @@ static int conv_wgrad_impl(const float* A, const float* dOut, float* workspace, 
     const int max_splits = (M + 511) / 512;
     int G = (max_splits < 64) ? (max_splits > splits ? max_splits : splits) : 64;
     if (G < splits) G = splits;
-    {   // experiment knob: fewer groups = fewer partials to reduce, but fewer workgroups to pull the memory system
-        const int genv = NELE_SWITCH_INT("NELE_WGRAD_GROUPS", 0);
-        if (genv > 0 && genv < G) G = genv;
-    }
     bool tiled = false;
     // ---- DMA double-buffer kernel: both operands bf16 in memory (D.conv2 .. conv5 in bf16 mode)
-    if (a16 && d16 && wgrad_dma_on()) {
+    if (a16 && d16) {
         const ConvGeom& gg = p.g;
         const int nkt_ = (gg.seglen + 15) / 16, NT_ = (N + 15) / 16;
         // kernel rows per workgroup: the largest divisor of KH whose accumulators fit (NT x items-per-wave tiles of 4 registers: 176 at most)
@@ -3156,8 +3118,7 @@ static int conv_wgrad_impl(const float* A, const float* dOut, float* workspace, 
             if (KH % cand == 0 && NT_ * ((cand * nkt_ + 7) / 8) <= 44) { KR = cand; break; }
         const int NJ_ = KR ? (KR * nkt_ + 7) / 8 : 0;
         int TH_ = 0;
-        const int th_env = NELE_SWITCH_INT("NELE_WGRAD_DMA_TH", 4);                              // NELE_WGRAD_DMA_TH=2|3|4: cap on the tile height (A/B diagnostic)
-        for (int cand = th_env < 4 ? th_env : 4; cand >= 2 && KR; --cand) {
+        for (int cand = 4; cand >= 2 && KR; --cand) {
             const long long bufsz = (long long)(cand + KR - 1) * (WD_TW + KW - 1) * gg.C + WT_SLACK + (long long)cand * WD_TW * WT_NP_OF(NT_);
             const int npc = (int)(((long long)(cand + KR - 1) * (WD_TW + KW - 1) * gg.C + 511) / 512), ndp = cand * WD_TW * WT_NP_OF(NT_) / 512;
             if (bufsz * 4 <= 150 * 1024 && npc <= 8 * WD_MAXHP && ndp <= 8 * WD_MAXDP) { TH_ = cand; break; }
@@ -3228,12 +3189,10 @@ static int conv_wgrad_impl(const float* A, const float* dOut, float* workspace, 
                     const int by_regs = 512 / ((fa.numRegs + 7) & ~7);
                     if (by_regs >= 1 && by_regs < occ) occ = by_regs;
                 }
-                if (NELE_SWITCH_INT("NELE_DEBUG_WGRAD", 0)) fprintf(stderr, "wgrad tile <%d,%d>: occupancy %d (regs %d, lds %lld + %zu)\n", ni, ki, occ, fa.numRegs, wt_lds, fa.sharedSizeBytes);
                 occ_tab[ni][ki] = occ;
             }
             const long long slots = (long long)ncu * occ_tab[ni][ki];
-            const int gauto = NELE_SWITCH_INT("NELE_WGRAD_AUTOGROUPS", 1);                        // NELE_WGRAD_AUTOGROUPS=0: the fixed 64 groups (A/B diagnostic)
-            if (gauto && G >= 16) {
+            if (G >= 16) {
                 long long best = -1;
                 int bestG = G;
                 for (int cand = G & ~7; cand >= 8; cand -= 8) {    // (any count up to the workspace's partial slots works for this kernel)

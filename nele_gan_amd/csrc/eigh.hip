@@ -753,7 +753,7 @@ __global__ __launch_bounds__(512) void eigh_tridiag_cluster4_kernel(double* __re
         v_i = vn_i;
         tk = tn;
         if (s == s_stop) {
-            // hand-over to eigh_tridiag_tail_kernel: the trailing block (rows / columns >= s + 2, updated through reflector s) goes back
+            // hand-over to the next stage: the trailing block (rows / columns >= s + 2, updated through reflector s) goes back
             // to A in place - those rows only receive reflector rows later - and the per-element state of the next iteration to ws.zt
             const int base = s + 2;
 #pragma unroll
@@ -1153,7 +1153,7 @@ __global__ __launch_bounds__(512) void eigh_tridiag_clusters_kernel(double* __re
 // column per lane, 20 row slots of 16): 128 matrices per launch, half as many rounds for the steps from 320 down to the hand-over to
 // the single-workgroup kernel at 256.  Same algorithm, exchange protocol and hand-over state as eigh_tridiag_cluster4_kernel; indices are
 // LOCAL to the trailing block (global row = base + local row), the state comes from the previous stage through ws.zt / A exactly as
-// eigh_tridiag_mid_kernel takes it.  Tags continue the step numbering of the first stage (the exchange slots are zeroed once per call).
+// eigh_tridiag_midx_kernel takes it.  Tags continue the step numbering of the first stage (the exchange slots are zeroed once per call).
 #define EC2_P 2
 #define EC2_RI 20
 #define EC2_NR 4
@@ -1261,7 +1261,7 @@ __global__ __launch_bounds__(512) void eigh_tridiag_cluster2_kernel(double* __re
         // ---- fused pass: x = a - v_r w_c - w_r v_c ; acc_c += x * vnext_r  (4 register columns + 1 LDS column; dead rows / columns are updated harmlessly)
         const int lo = s + 2 - base;                       // first live local index
         {
-            // the columns go in groups of two (as in eigh_tridiag_mid_kernel): v_c, w_c and acc_c of all five columns beside the 80-double block
+            // the columns go in groups of two (as in eigh_tridiag_midx_kernel): v_c, w_c and acc_c of all five columns beside the 80-double block
             // spilled 111 registers; the row vectors are re-read from LDS per group
             const int ri0 = (lo - rs + 15) >> 4;
             const double2* pv0 = reinterpret_cast<const double2*>(&vperm[0][rs * EC2_RI]);
@@ -1387,302 +1387,19 @@ __global__ __launch_bounds__(512) void eigh_tridiag_cluster2_kernel(double* __re
     }
 }
 
-// ------------------------------------------------------------------------------------------ e1, tail
-// The last ET_M = 128 steps of the tridiagonalisation (and whole matrices with n <= 128) in ONE workgroup per matrix with the trailing
-// block in LDS: the cluster kernel's step costs 5 us whatever is left of the matrix (exchange, peer wait), and a 128 x 128 block needs
-// neither.  Same recurrences as the cluster kernel; state handed over through ws.zt (v, p = A v, pivot column, tau) when s_first >= 0.
-// grid B, block 512, dynamic LDS m * m doubles.
-#define ET_M 128
+// ------------------------------------------------------------------------------------------ e1, middle + tail in one workgroup
+// The last steps in ONE workgroup per matrix: no cross-workgroup exchange, so a step costs 2.5 us on one CU instead of the cluster
+// kernel's 4.6 us on four.  EM_M = 224 rows / columns of the trailing block sit in REGISTERS (a thread holds 7 columns x 14 rows); same
+// recurrences as the cluster kernels, state handed over through ws.zt (v, p = A v, pivot column, tau); the fused pass is the cluster
+// kernel's (rows rs + 16 ri, columns cl + 32 cj, vectors in the permuted LDS layout so that a lane's rows are contiguous).  grid B, block 512.
+#define EM_RI 14
+#define EM_NC 7
+#define EM_M (16 * EM_RI)
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the wave's outstanding GLOBAL stores (vmcnt(0)); in the
 // step loop below those are the reflector row and d / e / tau, which nothing in the kernel reads back - waiting for their
 // acknowledgement at every barrier is a store round trip per step.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-#ifdef NELE_AB                                          // superseded variant: only in the test library (libnele_hip_ab.so)
-__global__ __launch_bounds__(512) void eigh_tridiag_tail_kernel(double* __restrict__ Aall, int n, EighWs ws, int s_first) {
-    extern __shared__ double et_sm[];                    // Am[m][m]
-    __shared__ double vs[ET_M], wv[ET_M], vn[ET_M], part[8][ET_M];
-    __shared__ double red0[8], red1[8];
-    __shared__ double s_alpha, s_ppiv;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wvi = tid >> 6;
-    if (ws.flag[b] != 0) return;                         // the cluster kernel gave up on this matrix: eigh_tridiag_repair_kernel redoes it
-    const int base = s_first + 1, m = n - base;          // trailing block = rows / columns base .. n-1
-    double* A = Aall + (size_t)b * n * n;
-    double* d = ws.d + (size_t)b * n;
-    double* e = ws.e + (size_t)b * n;
-    double* tau = ws.tau + (size_t)b * n;
-    double* Am = et_sm;
-    for (int idx = tid; idx < m * m; idx += 512) {
-        const int r = idx / m, c = idx - r * m;
-        Am[idx] = A[(size_t)(base + r) * n + base + c];
-    }
-    const int i = base + tid;                            // vector element owned by this thread (tid < m)
-    const bool own = tid < m;
-    double v_i = 0.0, tk = 0.0, p_i = 0.0, col_i = 0.0;
-    if (s_first >= 0) {
-        const double* st = ws.zt + (size_t)b * n * EG_MAXN;
-        if (own) { v_i = st[i]; p_i = st[EG_MAXN + i]; col_i = st[2 * EG_MAXN + i]; }
-        tk = st[3 * EG_MAXN];
-    } else if (own) col_i = A[i];                        // whole matrix: column 0
-    __syncthreads();
-    const int c2 = (tid & 63) * 2, q = tid >> 6;         // pass: columns c2, c2 + 1 (m = ET_M is even), row group q
-#ifdef EC_PROF
-    long long tacc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, t0 = clock64(), t1;
-#endif
-    for (int s = s_first; s <= n - 2; ++s) {
-        const bool in = own && (i >= s + 1);
-        double w_i = 0.0, wpiv = 0.0;
-        if (s >= 0) {
-            if (own && i == s + 1) s_ppiv = p_i;
-            double pv = in ? tk * p_i * v_i : 0.0;
-            pv = wave_sum_dpp(pv);
-            if (lane == 0) red0[wvi] = pv;
-            lds_barrier();
-            pv = ((red0[0] + red0[1]) + (red0[2] + red0[3])) + ((red0[4] + red0[5]) + (red0[6] + red0[7]));
-            EC_T(0);
-            const double al = -0.5 * tk * pv;
-            w_i = in ? tk * p_i + al * v_i : 0.0;
-            wpiv = tk * s_ppiv + al;
-        }
-        const double x_i = in ? col_i - v_i * wpiv - w_i : 0.0;
-        double tn = 0.0, betan = 0.0, vn_i = 0.0;
-        if (s + 2 <= n - 1) {
-            if (own && i == s + 2) s_alpha = x_i;
-            double ss = (own && i >= s + 3) ? x_i * x_i : 0.0;
-            ss = wave_sum_dpp(ss);
-            if (lane == 0) red1[wvi] = ss;
-            lds_barrier();
-            ss = ((red1[0] + red1[1]) + (red1[2] + red1[3])) + ((red1[4] + red1[5]) + (red1[6] + red1[7]));
-            EC_T(1);
-            const double alpha = s_alpha;
-            double scn = 0.0;
-            betan = alpha;
-            if (ss > 0.0) {
-                const double s2 = alpha * alpha + ss, aa = fabs(alpha);
-                double y = __builtin_amdgcn_rsq(s2);
-                y = y * (1.5 - 0.5 * s2 * y * y);
-                y = y * (1.5 - 0.5 * s2 * y * y);
-                const double nrm = s2 * y;
-                betan = alpha >= 0.0 ? -nrm : nrm;
-                tn = 1.0 + aa * y;
-                const double dd = aa + nrm;
-                double r = __builtin_amdgcn_rcp(dd);
-                r = r * (2.0 - dd * r);
-                r = r * (2.0 - dd * r);
-                scn = alpha >= 0.0 ? r : -r;
-            }
-            vn_i = (own && i == s + 2) ? 1.0 : ((own && i > s + 2) ? x_i * scn : 0.0);
-        }
-        if (own && i == s + 1) { d[s + 1] = x_i; e[s + 1] = betan; tau[s + 1] = tn; }
-        if (own && i >= s + 2) A[(size_t)(s + 1) * n + i] = vn_i;
-        if (s == n - 2) break;
-        if (own) { vs[tid] = v_i; wv[tid] = w_i; vn[tid] = vn_i; }
-        lds_barrier();
-        EC_T(2);
-        // ---- fused pass on the LDS block: x = a - v_r w_c - w_r v_c ; acc_c += x * vnext_r   (rows / columns >= s + 2)
-        const int lo = s + 2 - base;                     // first live local index (>= 0)
-        // thread = (column pair c2, row group q of 8): rows lo + q, lo + q + 8, ..., eight at a time; one 16-byte LDS access serves two
-        // columns and the row's three vector values are shared by them (the pass is bound by LDS instruction issue)
-        double acc0 = 0.0, acc1 = 0.0;
-        if (c2 + 1 >= lo) {
-            const double vc0 = vs[c2], wc0 = wv[c2], vc1 = vs[c2 + 1], wc1 = wv[c2 + 1];
-            for (int r = lo + q; r < m; r += 64) {
-                double2 a[8];
-                double vr[8], wr[8], nr[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int rr = min(r + 8 * u, m - 1);
-                    a[u] = *reinterpret_cast<const double2*>(&Am[rr * m + c2]); vr[u] = vs[rr]; wr[u] = wv[rr]; nr[u] = vn[rr];
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    if (r + 8 * u < m) {
-                        const double x0 = a[u].x - (vr[u] * wc0 + wr[u] * vc0), x1 = a[u].y - (vr[u] * wc1 + wr[u] * vc1);
-                        *reinterpret_cast<double2*>(&Am[(r + 8 * u) * m + c2]) = make_double2(x0, x1);
-                        acc0 += x0 * nr[u];
-                        acc1 += x1 * nr[u];
-                    }
-                }
-            }
-        }
-        EC_T(3);
-        part[q][c2] = acc0;
-        part[q][c2 + 1] = acc1;
-        lds_barrier();
-        EC_T(4);
-        if (own) {
-            p_i = ((part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid])) + ((part[4][tid] + part[5][tid]) + (part[6][tid] + part[7][tid]));
-            col_i = (tid >= lo) ? Am[lo * m + tid] : 0.0;          // pivot row s + 2 of the updated block
-        }
-        EC_T(5);
-        v_i = vn_i;
-        tk = tn;
-        // the next iteration's first barrier orders these reads against its LDS writes (s_ppiv / red0 are written before it, but
-        // nothing reads them after this point of the current iteration)
-    }
-#ifdef EC_PROF
-    if (tid == 0 && b == 0) for (int j = 0; j < 9; ++j) ws.lamp[j] = (double)tacc[j];
-#endif
-}
-#endif  // NELE_AB
-
-// ------------------------------------------------------------------------------------------ e1, middle + tail in registers
-// The last EM_M = 224 steps in ONE workgroup per matrix with the trailing block in REGISTERS (a thread holds 7 columns x 14 rows): no
-// cross-workgroup exchange, so a step costs the tail kernel's 2.5 us on one CU instead of the cluster kernel's 4.6 us on four - the
-// cluster kernel hands over as soon as what is left of the matrix fits one register file (after 194 of 418 steps at n = 420).  Same
-// recurrences and the same hand-over state as eigh_tridiag_tail_kernel; the fused pass is the cluster kernel's (rows rs + 16 ri, columns
-// cl + 32 cj, vectors in the permuted LDS layout so that a lane's rows are contiguous).  grid B, block 512.
-#define EM_RI 14
-#define EM_NC 7
-#define EM_M (16 * EM_RI)
-#ifdef NELE_AB                                          // superseded variant: only in the test library (libnele_hip_ab.so)
-__global__ __launch_bounds__(512) void eigh_tridiag_mid_kernel(double* __restrict__ Aall, int n, EighWs ws, int s_first) {
-    __shared__ __attribute__((aligned(16))) double vperm[3][EM_M + 64];   // v, w, v_next at [(r & 15) * (EM_RI) + (r >> 4)]
-    __shared__ double vnat[EM_M], wnat[EM_M];
-    __shared__ double accb[16][EM_M];
-    __shared__ double prow[EM_M];
-    __shared__ double red0[8], red1[8];
-    __shared__ double s_alpha, s_ppiv;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wvi = tid >> 6;
-    if (ws.flag[b] != 0) return;                         // the cluster kernel gave up on this matrix: eigh_tridiag_repair_kernel redoes it
-    const int base = s_first + 1, m = n - base;          // trailing block = rows / columns base .. n-1, m <= EM_M
-    double* A = Aall + (size_t)b * n * n;
-    double* d = ws.d + (size_t)b * n;
-    double* e = ws.e + (size_t)b * n;
-    double* tau = ws.tau + (size_t)b * n;
-    const int cl0 = lane & 31, rs = 2 * wvi + (lane >> 5);
-    double a[EM_NC][EM_RI];
-#pragma unroll
-    for (int cj = 0; cj < EM_NC; ++cj)
-#pragma unroll
-        for (int ri = 0; ri < EM_RI; ++ri) {
-            const int r = rs + 16 * ri, c = cl0 + 32 * cj;
-            a[cj][ri] = (r < m && c < m) ? A[(size_t)(base + r) * n + base + c] : 0.0;
-        }
-    const int i = base + tid;                            // vector element owned by this thread (tid < m)
-    const bool own = tid < m;
-    const int pi = (tid & 15) * EM_RI + (tid >> 4);      // permuted slot of local row tid (tid < EM_M)
-    double v_i = 0.0, tk = 0.0, p_i = 0.0, col_i = 0.0;
-    if (s_first >= 0) {
-        const double* st = ws.zt + (size_t)b * n * EG_MAXN;
-        if (own) { v_i = st[i]; p_i = st[EG_MAXN + i]; col_i = st[2 * EG_MAXN + i]; }
-        tk = st[3 * EG_MAXN];
-    } else if (own) col_i = A[i];                        // whole matrix: column 0
-    __syncthreads();
-    for (int s = s_first; s <= n - 2; ++s) {
-        const bool in = own && (i >= s + 1);
-        double w_i = 0.0, wpiv = 0.0;
-        if (s >= 0) {
-            if (own && i == s + 1) s_ppiv = p_i;
-            double pv = in ? tk * p_i * v_i : 0.0;
-            pv = wave_sum_dpp(pv);
-            if (lane == 0) red0[wvi] = pv;
-            lds_barrier();
-            pv = ((red0[0] + red0[1]) + (red0[2] + red0[3])) + ((red0[4] + red0[5]) + (red0[6] + red0[7]));
-            const double al = -0.5 * tk * pv;
-            w_i = in ? tk * p_i + al * v_i : 0.0;
-            wpiv = tk * s_ppiv + al;
-        }
-        const double x_i = in ? col_i - v_i * wpiv - w_i : 0.0;
-        double tn = 0.0, betan = 0.0, vn_i = 0.0;
-        if (s + 2 <= n - 1) {
-            if (own && i == s + 2) s_alpha = x_i;
-            double ss = (own && i >= s + 3) ? x_i * x_i : 0.0;
-            ss = wave_sum_dpp(ss);
-            if (lane == 0) red1[wvi] = ss;
-            lds_barrier();
-            ss = ((red1[0] + red1[1]) + (red1[2] + red1[3])) + ((red1[4] + red1[5]) + (red1[6] + red1[7]));
-            const double alpha = s_alpha;
-            double scn = 0.0;
-            betan = alpha;
-            if (ss > 0.0) {
-                const double s2 = alpha * alpha + ss, aa = fabs(alpha);
-                double y = __builtin_amdgcn_rsq(s2);
-                y = y * (1.5 - 0.5 * s2 * y * y);
-                y = y * (1.5 - 0.5 * s2 * y * y);
-                const double nrm = s2 * y;
-                betan = alpha >= 0.0 ? -nrm : nrm;
-                tn = 1.0 + aa * y;
-                const double dd = aa + nrm;
-                double r = __builtin_amdgcn_rcp(dd);
-                r = r * (2.0 - dd * r);
-                r = r * (2.0 - dd * r);
-                scn = alpha >= 0.0 ? r : -r;
-            }
-            vn_i = (own && i == s + 2) ? 1.0 : ((own && i > s + 2) ? x_i * scn : 0.0);
-        }
-        if (own && i == s + 1) { d[s + 1] = x_i; e[s + 1] = betan; tau[s + 1] = tn; }
-        if (own && i >= s + 2) A[(size_t)(s + 1) * n + i] = vn_i;
-        if (s == n - 2) break;
-        if (tid < EM_M) {
-            vnat[tid] = v_i; wnat[tid] = w_i;
-            vperm[0][pi] = v_i; vperm[1][pi] = w_i; vperm[2][pi] = vn_i;
-        }
-        lds_barrier();
-        // ---- fused pass: x = a - v_r w_c - w_r v_c ; acc_c += x * vnext_r   (rows >= s + 2; dead rows / columns are updated harmlessly)
-        const int lo = s + 2 - base;                     // first live local index (>= 0)
-        // the columns go in groups of two: 2 x 3 x EM_NC more live doubles (v_c, w_c, acc_c of every column) do not fit beside the block
-        {
-            const int ri0 = (lo - rs + 15) >> 4;
-            const double2* pv0 = reinterpret_cast<const double2*>(&vperm[0][rs * EM_RI]);
-            const double2* pv1 = reinterpret_cast<const double2*>(&vperm[1][rs * EM_RI]);
-            const double2* pv2 = reinterpret_cast<const double2*>(&vperm[2][rs * EM_RI]);
-            constexpr int CH = 2, NH = (EM_NC + CH - 1) / CH;
-#pragma unroll
-            for (int h = 0; h < NH; ++h) {
-                double acc[CH], vc[CH], wc[CH];
-#pragma unroll
-                for (int u = 0; u < CH; ++u) {
-                    const int cj = h * CH + u;
-                    acc[u] = 0.0;
-                    vc[u] = (cj < EM_NC) ? vnat[cl0 + 32 * (cj < EM_NC ? cj : 0)] : 0.0;
-                    wc[u] = (cj < EM_NC) ? wnat[cl0 + 32 * (cj < EM_NC ? cj : 0)] : 0.0;
-                }
-#pragma unroll
-                for (int q = 0; q < EM_RI / 2; ++q) {
-                    if (2 * q + 1 >= ri0) {              // rows rs + 16 (2q), rs + 16 (2q + 1)
-                        const double2 vr = pv0[q], wr = pv1[q], nr = pv2[q];
-#pragma unroll
-                        for (int u = 0; u < CH; ++u) {
-                            const int cj = h * CH + u;
-                            if (cj < EM_NC) {
-                                double x0 = a[cj][2 * q], x1 = a[cj][2 * q + 1];
-                                x0 -= vr.x * wc[u] + wr.x * vc[u];
-                                x1 -= vr.y * wc[u] + wr.y * vc[u];
-                                a[cj][2 * q] = x0; a[cj][2 * q + 1] = x1;
-                                acc[u] += x0 * nr.x + x1 * nr.y;
-                            }
-                        }
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < CH; ++u)
-                    if (h * CH + u < EM_NC) accb[rs][cl0 + 32 * (h * CH + u)] = acc[u];
-            }
-        }
-        if (rs == (lo & 15)) {                           // the lanes that hold pivot row s + 2 of the updated block publish it
-            switch (lo >> 4) {
-#define EM_CASE(k) case k: _Pragma("unroll") for (int cj = 0; cj < EM_NC; ++cj) prow[cl0 + 32 * cj] = a[cj][k]; break;
-                EM_CASE(0) EM_CASE(1) EM_CASE(2) EM_CASE(3) EM_CASE(4) EM_CASE(5) EM_CASE(6) EM_CASE(7) EM_CASE(8) EM_CASE(9) EM_CASE(10) EM_CASE(11)
-                EM_CASE(12) EM_CASE(13)
-#undef EM_CASE
-            }
-        }
-        lds_barrier();
-        if (tid < EM_M) {
-            double t = 0.0;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) t += accb[q][tid];
-            p_i = t;
-            col_i = (tid >= lo) ? prow[tid] : 0.0;       // pivot row s + 2 of the updated block = the next pivot column
-        }
-        v_i = vn_i;
-        tk = tn;
-        // the next iteration's first barrier orders these reads against its LDS writes
-    }
-}
-#endif  // NELE_AB
-
-// The same with up to EX_E = 32 more rows / columns: the trailing block's FIRST E = m - 224 rows (the ones eliminated first) sit in an LDS
+// Up to EX_E = 32 more rows / columns: the trailing block's FIRST E = m - 224 rows (the ones eliminated first) sit in an LDS
 // strip S[E][256] (full rows: the E x E corner is stored twice, the off-diagonal block once), the other 224 x 224 in registers as above.
 // While the strip is alive (the first E steps) a step also updates it in place - pass A: thread per column, column sums; pass B: thread
 // group per row, the row sums that stand in for the transposed off-diagonal block - and takes the next pivot column from it.  The
@@ -2579,112 +2296,11 @@ __global__ __launch_bounds__(64, IV2_OCC) void eigh_invit2_kernel(int n, EighWs 
 #undef CK2
 }
 
-// ------------------------------------------------------------------------------------------ e4
-// Eigenvectors of A = Q z, Q = H_0 H_1 ... H_{n-2}, H_k = I - tau_k v_k v_k^T acting on rows k+1..n-1.
-// grid (ceil(n/32), B), block 256.  Eigenvectors live in REGISTERS: a 16-lane row holds two eigenvectors, lane t the rows
-// t + 16 q, so a reflector costs 2 x 2 FMAs per held row, a 4-step DPP row reduction and no barrier.  Reflectors are staged
-// through LDS eight at a time (zeroed below their first row, next chunk's loads in flight during the compute), so there
-// is one barrier per 8 reflectors.  The result is written as U[j][i] (row j = eigenvector j), the layout the SIIB
-// projection reads.
-#define BT_CH 8
-#ifdef NELE_AB                                          // superseded variant: only in the test library (libnele_hip_ab.so)
-template <int BT_Q>     // 16-row groups held per lane: 28 covers n <= 448 (SIIB: 420), 32 covers EG_MAXN
-__global__ __launch_bounds__(256, 2) void eigh_backtransform_kernel(const double* __restrict__ Aall, int n, EighWs ws, double* __restrict__ U) {
-    // reflector chunk in LDS, PERMUTED: element i of reflector r at r * RS + (i & 15) * BT_Q + (i >> 4), so the BT_Q values a lane needs
-    // (rows t, t + 16, ...) are contiguous and go out as 16-byte reads (the kernel is bound by LDS instruction issue: 2 x BT_Q reads per
-    // reflector and wave in the plain layout)
-    extern __shared__ double bt_sm[];         // vch[2][BT_CH][16][BT_Q], tch[2][BT_CH]
-    const int nld = (n + 15) & ~15;
-    constexpr int RS = 16 * BT_Q;
-    double* vch = bt_sm;
-    double* tch = bt_sm + 2 * BT_CH * RS;
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, t = lane & 15, g = lane >> 4;
-    const int j0 = blockIdx.x * 32 + w * 8 + g * 2;
-    const double* A = Aall + (size_t)b * n * n;
-    const double* tau = ws.tau + (size_t)b * n;
-    const double* zt = ws.zt + (size_t)b * n * EG_MAXN;
-    double z0[BT_Q], z1[BT_Q];
-#pragma unroll
-    for (int q = 0; q < BT_Q; ++q) {
-        const int i = t + 16 * q;
-        z0[q] = (i < n && j0 < n) ? zt[(size_t)i * EG_MAXN + j0] : 0.0;
-        z1[q] = (i < n && j0 + 1 < n) ? zt[(size_t)i * EG_MAXN + j0 + 1] : 0.0;
-    }
-    const int nchunks = (n - 1 + BT_CH - 1) / BT_CH;
-    const int per = BT_CH * nld;              // <= 8 * 512 = 16 * 256
-    constexpr int NPRE = BT_Q / 2;            // 8 * 16 * BT_Q staged values / 256 threads
-    double pre[NPRE];
-    double pret = 0.0;
-    auto gload = [&](int c) {
-        const int kc = n - 2 - BT_CH * c;
-#pragma unroll
-        for (int u = 0; u < NPRE; ++u) {
-            const int idx = tid + 256 * u;
-            const int r = idx / nld, i = idx - r * nld, k = kc - r;
-            pre[u] = (idx < per && k >= 0 && i > k && i < n) ? A[(size_t)k * n + i] : 0.0;
-        }
-        if (tid < BT_CH) pret = (kc - tid >= 0) ? tau[kc - tid] : 0.0;
-    };
-    auto lstore = [&](int buf) {
-#pragma unroll
-        for (int u = 0; u < NPRE; ++u) {
-            const int idx = tid + 256 * u;
-            const int r = idx / nld, i = idx - r * nld;
-            if (idx < per) vch[buf * BT_CH * RS + r * RS + (i & 15) * BT_Q + (i >> 4)] = pre[u];
-        }
-        if (tid < BT_CH) tch[buf * BT_CH + tid] = pret;
-    };
-    for (int e_ = tid; e_ < 2 * BT_CH * RS; e_ += 256) vch[e_] = 0.0;      // slots of rows >= nld are never staged: they must read as zero
-    __syncthreads();
-    gload(0);
-    lstore(0);
-    __syncthreads();
-    for (int c = 0; c < nchunks; ++c) {
-        const int buf = c & 1, kc = n - 2 - BT_CH * c;
-        if (c + 1 < nchunks) gload(c + 1);
-        for (int r = 0; r < BT_CH; ++r) {
-            const int k = kc - r;
-            if (k < 0) break;
-            const double tk = tch[buf * BT_CH + r];
-            if (tk == 0.0) continue;
-            const double2* vr2 = reinterpret_cast<const double2*>(vch + buf * BT_CH * RS + r * RS + t * BT_Q);
-            const int q0 = (k + 1) >> 4;      // rows below 16 q0 are zero in this reflector
-            double d0 = 0.0, d1 = 0.0;
-#pragma unroll
-            for (int qq = 0; qq < BT_Q / 4; ++qq) {
-                if (4 * qq + 3 >= q0) {
-                    const double2 va = vr2[2 * qq], vb = vr2[2 * qq + 1];
-                    d0 += va.x * z0[4 * qq] + va.y * z0[4 * qq + 1] + vb.x * z0[4 * qq + 2] + vb.y * z0[4 * qq + 3];
-                    d1 += va.x * z1[4 * qq] + va.y * z1[4 * qq + 1] + vb.x * z1[4 * qq + 2] + vb.y * z1[4 * qq + 3];
-                }
-            }
-            d0 = tk * row16_sum_dpp(d0);
-            d1 = tk * row16_sum_dpp(d1);
-#pragma unroll
-            for (int qq = 0; qq < BT_Q / 4; ++qq) {
-                if (4 * qq + 3 >= q0) {
-                    const double2 va = vr2[2 * qq], vb = vr2[2 * qq + 1];
-                    z0[4 * qq] -= d0 * va.x; z0[4 * qq + 1] -= d0 * va.y; z0[4 * qq + 2] -= d0 * vb.x; z0[4 * qq + 3] -= d0 * vb.y;
-                    z1[4 * qq] -= d1 * va.x; z1[4 * qq + 1] -= d1 * va.y; z1[4 * qq + 2] -= d1 * vb.x; z1[4 * qq + 3] -= d1 * vb.y;
-                }
-            }
-        }
-        if (c + 1 < nchunks) lstore(buf ^ 1);
-        __syncthreads();
-    }
-    double* Ub = U + (size_t)b * n * n;
-#pragma unroll
-    for (int q = 0; q < BT_Q; ++q) {
-        const int i = t + 16 * q;
-        if (i < n && j0 < n) Ub[(size_t)j0 * n + i] = z0[q];
-        if (i < n && j0 + 1 < n) Ub[(size_t)(j0 + 1) * n + i] = z1[q];
-    }
-}
-#endif  // NELE_AB
-
 // ------------------------------------------------------------------------------------------ e4, blocked (compact WY) on the matrix cores
-// The reflector-by-reflector kernel above is bound by LDS instruction issue (2 x BT_Q reads per reflector and wave for 4 x BT_Q FMAs):
-// 3.0 ms for 256 matrices of 420.  Here 16 consecutive reflectors H_klo ... H_khi are applied at once as I - V T V^T (LAPACK dlarft
+// Eigenvectors of A = Q z, Q = H_0 H_1 ... H_{n-2}, H_k = I - tau_k v_k v_k^T acting on rows k+1..n-1.  The result is written as U[j][i]
+// (row j = eigenvector j), the layout the SIIB projection reads.
+// Applying the reflectors one by one (eigenvectors in registers, reflectors staged through LDS) is bound by LDS instruction issue (2 reads
+// per reflector, held row and wave for 4 FMAs): 3.0 ms for 256 matrices of 420.  Here 16 consecutive reflectors H_klo ... H_khi are applied at once as I - V T V^T (LAPACK dlarft
 // "forward, columnwise": T upper triangular, T_jj = tau_j, T_(0:j, j) = -tau_j T_(0:j, 0:j) V_(:, 0:j)^T v_j):
 //     W = V^T Z (16 x 16 per wave),  W' = -T W,  Z += V W'
 // with v_mfma_f64_16x16x4_f64.  A wave keeps 16 eigenvectors in the MFMA accumulator layout (reg q of lane l = row (l >> 4) + 4 q of the
@@ -3032,8 +2648,6 @@ int nele_eigh_sym_batched_ex(double* A, int n, int B, double* lam, double* U, vo
             cluster_cap = ((long long)ncu * (occ > 0 ? 1 : 0) / (8 * EC_P)) * 8;   // one workgroup per CU: never rely on sharing a CU
         else cluster_cap = 0;
         if (cluster_cap > 32) cluster_cap = 32;
-        const int capenv = NELE_SWITCH_INT("NELE_EIGH_CLUSTER_CAP", 0);    // matrices per launch (multiple of 8): fewer leaves CUs to other streams
-        if (capenv >= 8 && capenv < cluster_cap) cluster_cap = capenv / 8 * 8;
     }
     int c2_first = -1;                                     // first step of the second cluster stage when it runs (its give-ups are repaired from there)
     bool repaired_inline = false;                          // eigh_tridiag_midx_kernel redoes flagged matrices itself
@@ -3053,29 +2667,25 @@ int nele_eigh_sym_batched_ex(double* A, int n, int B, double* lam, double* U, vo
         // two half-size launches, which leaves half of the CUs to the other streams (measured 2 % on the whole step at B = 32)
         const int p4_on = NELE_SWITCH_INT("NELE_EIGH_P4", 1);
         if (p4_on && n <= 16 * E4_RI && cluster_cap >= 32) {
-            // four workgroups per matrix: 64 matrices per launch would fill the chip; 32 use half of it.  The last ET_M steps run in
-            // eigh_tridiag_tail_kernel (one workgroup per matrix, block in LDS): s_stop = last iteration of the cluster kernel
-            const int tail_on = NELE_SWITCH_INT("NELE_EIGH_TAIL", 1);
-            NELE_AB_ONLY(NELE_ONCE_PER_DEVICE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(eigh_tridiag_tail_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                                        (int)(sizeof(double) * ET_M * ET_M)));)
-            const int mid_on = NELE_SWITCH_INT("NELE_EIGH_MID", 1);                        // NELE_EIGH_MID=0: hand over to the LDS tail kernel at 128 instead (A/B diagnostic)
-            const int midx_on = NELE_SWITCH_INT("NELE_EIGH_MIDX", 1);   // =0: hand over at 224 (registers only) instead of 256 (registers + LDS strip)
+            // four workgroups per matrix: 64 matrices per launch would fill the chip; 32 use half of it.  The last EM_M + EX_E steps run in
+            // eigh_tridiag_midx_kernel (one workgroup per matrix): s_stop = last iteration of the cluster kernels, -2 = a matrix too small
+            // for a hand-over, which the four-workgroup kernel finishes by itself
             NELE_ONCE_PER_DEVICE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(eigh_tridiag_midx_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 104 * 1024));
-            const int mhand = (tail_on != 0 && mid_on != 0) ? (midx_on ? EM_M + EX_E : EM_M) : ET_M;
-            const int s_stop = (tail_on && n > mhand + 2) ? n - mhand - 2 : -2;
+            constexpr int mhand = EM_M + EX_E;
+            const int s_stop = (n > mhand + 2) ? n - mhand - 2 : -2;
             // second cluster stage (round 4): once 320 rows are left, two workgroups per matrix hold the block - twice the matrices per launch
-            // for the steps from 320 down to the single-workgroup hand-over (NELE_EIGH_C2=0: the four-workgroup kernel runs them all)
-            const int c2_on = NELE_SWITCH_INT("NELE_EIGH_C2", 1);
+            // for the steps from 320 down to the single-workgroup hand-over
+            static_assert(mhand < EC2_M, "the second cluster stage ends where the single-workgroup kernel takes over");
             NELE_ONCE_PER_DEVICE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(eigh_tridiag_cluster2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                            (int)(sizeof(double) * EC2_RI * 16 * 32)));
-            const bool two_stage = c2_on && s_stop >= 0 && mhand < EC2_M && n > EC2_M + 8;
+            const bool two_stage = n > EC2_M + 8;
             const int s_stop1 = two_stage ? n - EC2_M - 2 : s_stop;
             // first stage on the lower triangle with two workgroups per matrix (round 4; NELE_EIGH_SYM=0: the four-workgroup full-storage kernel)
             const int sym_on = NELE_SWITCH_INT("NELE_EIGH_SYM", 1);
             NELE_ONCE_PER_DEVICE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(eigh_tridiag_clusters_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                            (int)(sizeof(double) * ECS_RI * 16 * 32)));
             const bool sym_stage = sym_on && two_stage && n <= 16 * ECS_RI && s_stop1 + 2 < 128;
-            // NELE_EIGH_P4_BATCH: matrices per launch (32 = half of the chip inside a training step, 64 = all of it otherwise).  The spinning workgroups own
+            // Matrices per launch (32 = half of the chip inside a training step, 64 = all of it otherwise).  The spinning workgroups own
             // their CU - registers full, issue slots mostly idle - so 32 per launch (twice the launches) leaves room for the step's other
             // streams while the chain's own time doubles (8 x 1.2 instead of 4 x 1.2 ms per 256 matrices).  Measured twice on the
             // B = 256 step, alternating on one box: 45.4 / 45.5 / 46.0 against 46.1 / 46.2 / 46.3 ms (second session), 42.8 / 42.5
@@ -3083,10 +2693,7 @@ int nele_eigh_sym_batched_ex(double* A, int n, int B, double* lam, double* U, vo
             // The caller says which: SIIB's clean-signal phase inside a training step (nele_metric_siib phase 3, which runs beside the
             // G-step) asks for 32 through nele_eigh_sym_batched_ex's argument; a stand-alone call (one-shot SIIB, nele_eigh_sym_batched by
             // itself) has nothing to share the chip with and takes 64 - one SIIB call at B = 256 is 17 ms that way and 21.5 ms with 32.
-            const int p4_raw = NELE_SWITCH_INT("NELE_EIGH_P4_BATCH", 0);
-            const int p4_env = (p4_raw >= 8 && p4_raw <= 64) ? p4_raw / 8 * 8 : 0;
-            const int hint = cluster_batch;
-            const int p4_batch = p4_env ? p4_env : (hint >= 8 && hint <= 64 ? hint / 8 * 8 : 64);
+            const int p4_batch = (cluster_batch >= 8 && cluster_batch <= 64) ? cluster_batch / 8 * 8 : 64;
             const int fail_every = NELE_SWITCH_INT("NELE_EIGH_FAIL_EVERY", 0);                     // NELE_EIGH_FAIL_EVERY=k (tests): every k-th matrix takes the give-up / repair path
             if (sym_stage) {
                 const int cs_batch = 2 * p4_batch;
@@ -3112,15 +2719,12 @@ int nele_eigh_sym_batched_ex(double* A, int n, int B, double* lam, double* U, vo
                                                  Bc, ws, s_stop1 + 1, s_stop, fail_every));
                 }
             }
-            if (s_stop >= -1) {
-                const int mt = n - (s_stop + 2);
-                if (mhand == EM_M + EX_E) { hipLaunchKernelGGL(eigh_tridiag_midx_kernel, dim3(B), dim3(512), sizeof(double) * EX_E * EX_LD, s, A, n, ws, s_stop + 1, B, c2_first); repaired_inline = true; }
-                NELE_AB_ONLY(else if (mhand == EM_M) hipLaunchKernelGGL(eigh_tridiag_mid_kernel, dim3(B), dim3(512), 0, s, A, n, ws, s_stop + 1);
-                             else hipLaunchKernelGGL(eigh_tridiag_tail_kernel, dim3(B), dim3(512), sizeof(double) * (size_t)mt * mt, s, A, n, ws, s_stop + 1);)
+            if (s_stop >= 0) {
+                hipLaunchKernelGGL(eigh_tridiag_midx_kernel, dim3(B), dim3(512), sizeof(double) * EX_E * EX_LD, s, A, n, ws, s_stop + 1, B, c2_first);
+                repaired_inline = true;
             }
         } else {
-        const int split_small = NELE_SWITCH_INT("NELE_EIGH_SPLIT", 1);
-        const int per = (split_small && B <= 32 && cluster_cap >= 32) ? 16 : cluster_cap;
+        const int per = (B <= 32 && cluster_cap >= 32) ? 16 : cluster_cap;
         for (int b0 = 0; b0 < B; b0 += per) {
             const int Bc = (B - b0 < per) ? B - b0 : per;
             hipLaunchKernelGGL(eigh_tridiag_cluster_kernel, dim3(64 * ((Bc + 7) / 8)), dim3(512), 0, s, A, n, b0, Bc, ws);
@@ -3141,10 +2745,9 @@ int nele_eigh_sym_batched_ex(double* A, int n, int B, double* lam, double* U, vo
     // sweeps after the growth criterion is met: LAPACK's dstein uses EXTRA = 2 and documents "should be at least 1"; with the eigenvalues
     // bisected to 1 ulp one is enough for every test matrix (eigenvalues 1e-13, residual 1e-11, orthogonality 1e-8, SIIB unchanged to 17
     // digits) and saves a quarter of this kernel's HBM traffic (its work arrays: 108 KB per eigenvector); 0 fails the residual test
-    const int iv_extra = NELE_SWITCH_INT("NELE_EIGH_INVIT_EXTRA", 1);
-    // eigenvectors on request: only the blocked back-transformation knows how to skip (the superseded variants compute every vector)
-    const int wy_on = NELE_SWITCH_INT("NELE_EIGH_WY", 1);   // =0: the reflector-by-reflector back-transformation (A/B diagnostic)
-    const bool ranged = rel_cut >= 0.0 && wy_on && !NELE_SWITCH_INT("NELE_EIGH_INVIT_STORE", 0);
+    const int iv_extra = 1;
+    // eigenvectors on request (the storing inverse iteration of the test library computes every vector)
+    const bool ranged = rel_cut >= 0.0 && !NELE_SWITCH_INT("NELE_EIGH_INVIT_STORE", 0);
     const int* kf = ranged ? ws.kfirst : nullptr;
     if (ranged) hipLaunchKernelGGL(eigh_cut_kernel, dim3(B), dim3(64), 0, s, n, ws, lam, rel_cut, ws.kfirst, kept_first);
     else {
@@ -3155,21 +2758,14 @@ int nele_eigh_sym_batched_ex(double* A, int n, int B, double* lam, double* U, vo
     if (NELE_SWITCH_INT("NELE_EIGH_INVIT_STORE", 0)) { NELE_AB_ONLY(hipLaunchKernelGGL(eigh_invit_kernel, dim3((n + 63) / 64, B), dim3(64), 0, s, n, ws, lam, iv_extra);) }
     else hipLaunchKernelGGL(eigh_invit2_kernel, dim3((n + 63) / 64, B), dim3(64), 0, s, n, ws, lam, iv_extra, kf);
     hipLaunchKernelGGL(eigh_postscale_kernel, dim3(B), dim3(256), 0, s, n, ws, lam);
-    const size_t lds = sizeof(double) * (2 * (size_t)BT_CH * 16 * (n <= 448 ? 28 : 32) + 2 * BT_CH);
     NELE_ONCE_PER_DEVICE({
-        NELE_AB_ONLY((void)hipFuncSetAttribute(reinterpret_cast<const void*>(eigh_backtransform_kernel<28>), hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
-                     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(eigh_backtransform_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(eigh_backtransform_wy_kernel<27>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(eigh_backtransform_wy_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
     });
-    if (wy_on) {
-        const int nblk = (n - 1 + WY_NB - 1) / WY_NB;
-        hipLaunchKernelGGL(eigh_wy_t_kernel, dim3((nblk + 3) / 4, B), dim3(256), 0, s, A, n, ws);
-        if (n <= 432) hipLaunchKernelGGL(eigh_backtransform_wy_kernel<27>, dim3((n + 63) / 64, B), dim3(256), sizeof(double) * (2 * 432 * WY_LD + 2 * 16 * WY_LD), s, A, n, ws, U, kf);
-        else hipLaunchKernelGGL(eigh_backtransform_wy_kernel<32>, dim3((n + 63) / 64, B), dim3(256), sizeof(double) * (2 * 512 * WY_LD + 2 * 16 * WY_LD), s, A, n, ws, U, kf);
-    }
-    NELE_AB_ONLY(else if (n <= 448) hipLaunchKernelGGL(eigh_backtransform_kernel<28>, dim3((n + 31) / 32, B), dim3(256), lds, s, A, n, ws, U);
-                 else hipLaunchKernelGGL(eigh_backtransform_kernel<32>, dim3((n + 31) / 32, B), dim3(256), lds, s, A, n, ws, U);)
+    const int nblk = (n - 1 + WY_NB - 1) / WY_NB;
+    hipLaunchKernelGGL(eigh_wy_t_kernel, dim3((nblk + 3) / 4, B), dim3(256), 0, s, A, n, ws);
+    if (n <= 432) hipLaunchKernelGGL(eigh_backtransform_wy_kernel<27>, dim3((n + 63) / 64, B), dim3(256), sizeof(double) * (2 * 432 * WY_LD + 2 * 16 * WY_LD), s, A, n, ws, U, kf);
+    else hipLaunchKernelGGL(eigh_backtransform_wy_kernel<32>, dim3((n + 63) / 64, B), dim3(256), sizeof(double) * (2 * 512 * WY_LD + 2 * 16 * WY_LD), s, A, n, ws, U, kf);
     NELE_CHECK_LAUNCH("nele_eigh_sym_batched");
     return NELE_OK;
 }

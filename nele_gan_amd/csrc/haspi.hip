@@ -2068,7 +2068,6 @@ static size_t haspi_layout(int B, int L, int fs_in, HaspiWs* w, char* base) {
     TAKE(bw, double, (size_t)B * 2 * HP_NCH);
     TAKE(loss, double, 2 * 5 * HP_NCH);
     int lc = GS_LC;
-    { const int lcenv = NELE_SWITCH_INT("NELE_HASPI_LC", 0); if (lcenv >= GS_LC) lc = lcenv / GS_LC * GS_LC; }
     while ((n24p + lc - 1) / lc > GS_MAXC) lc += GS_LC;
     const int nchunk = (n24p + lc - 1) / lc, ncg = (n24p + (lc < GL_N ? lc : GL_N) - 1) / (lc < GL_N ? lc : GL_N);
     TAKE(ssp, double, (size_t)B * 2 * nchunk * HP_NCH);
@@ -2143,11 +2142,10 @@ extern "C" int nele_metric_haspi_nsub(int L, int fs_in) {
 }
 
 // A/B switches of the chain, read once
-struct HaspiFlags { int bank_gain, par_iir, fused_gain, fir9; };
+struct HaspiFlags { int par_iir, fused_gain, fir9; };
 static const HaspiFlags& haspi_flags() {
     static HaspiFlags f = [] {
         HaspiFlags v;
-        v.bank_gain = NELE_SWITCH_INT("NELE_HASPI_BANK_GAIN", 1) != 0;   // =0: the gain pass as its own kernel
         v.par_iir = NELE_SWITCH_INT("NELE_HASPI_PAR_IIR", 1) != 0;       // =0: the serial recurrence kernels
         v.fused_gain = NELE_SWITCH_INT("NELE_HASPI_FUSED_GAIN", 1) != 0;
         v.fir9 = NELE_SWITCH_INT("NELE_HASPI_FIR9", 1) != 0;             // =0: the 8-sample-group IHC + envelope-filter kernel with per-sample phase counters
@@ -2170,10 +2168,9 @@ static void haspi_chain(const float* x, const float* y, int B, int L, int fs_in,
     const int rows = B * nsig;
     HaspiWs ws = ws_in;
     const HaspiFlags& fl = haspi_flags();
-    const int bank_gain = fl.bank_gain;
     int par_iir = fl.par_iir, fused_gain = fl.fused_gain;
     if (quality) par_iir = fused_gain = 1;                     // the quality path exists for the scan kernels only
-    const bool in_bank = bank_gain && par_iir && fused_gain && !quality;     // gain pass inside pass 2 of the signal bank
+    const bool in_bank = par_iir && fused_gain && !quality;     // gain pass inside pass 2 of the signal bank
     ws.lcg = in_bank ? ws.lc : GL_N;
     ws.fmul = 1;
     hipLaunchKernelGGL(haspi_rms_kernel, dim3(B, nsig), dim3(256), 0, s, x, y, L, fs_in, ws, sig0);

@@ -212,7 +212,6 @@ class GanTrainer:
         self._cur_set = 0
         self._wstreams_plain = None                  # D's weight-gradient streams outside the pipelined step (see _pipeline_queues)
         self._queues_checked = False                 # _pipeline_queues has verified that the three pipelined streams sit on three hardware queues
-        self.split_haspi = os.environ.get('NELE_HASPI_SPLIT', '1') != '0'   # HASPI's clean-signal half beside the G-step (A/B switch)
         # metric status, accumulated on the device without a host synchronisation and read by check_status():
         # [SIIB undefined (too few active frames: pysiib raises), SIIB clamped (M / frame caps hit: truncated score),
         #  HASPI below threshold (pyhaspi2.py:357-358 raises)] - one accumulator per stream that folds into it
@@ -760,7 +759,7 @@ class GanTrainer:
             w['clean_done'] = torch.cuda.Event()
             w['clean_done'].record(side)
             w['clean_stream'] = side
-        if 'haspi' in self.metrics and self.split_haspi and with_metrics:
+        if 'haspi' in self.metrics and with_metrics:
             # HASPI's reference-signal half (ear model .. modulation filters of the CLEAN signal) needs no enhanced signal either
             with torch.cuda.stream(side2):
                 side2.wait_event(after)

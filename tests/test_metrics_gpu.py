@@ -207,14 +207,13 @@ np.save(sys.argv[2], np.concatenate(out))
 
 def test_siib_period_shortcut_is_bit_identical_to_computing_every_frame(tmp_path):
     """L a multiple of 200: the tiled signal is frame-periodic; spectra / masking of the repeats are copied, not recomputed.
-    A/B against the same library with the shortcut switched off (separate processes: the switch is read once)."""
+    A/B inside the test library, with and without the shortcut (separate processes: the switch is read once)."""
     import subprocess
     import sys
     res = []
     for flag in ('1', '0'):
         out = str(tmp_path / ('siib_%s.npy' % flag))
-        env = dict(os.environ, NELE_SIIB_DEDUP=flag)
-        subprocess.run([sys.executable, '-c', _AB_CHILD, os.path.dirname(HERE), out], check=True, env=env, timeout=240)
+        subprocess.run([sys.executable, '-c', _AB_CHILD, os.path.dirname(HERE), out], check=True, env=ab_env(NELE_SIIB_DEDUP=flag), timeout=240)
         res.append(np.load(out))
     assert res[0].tobytes() == res[1].tobytes()
 

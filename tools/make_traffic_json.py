@@ -19,7 +19,7 @@ WANT = ('glayer16_kernel<2, 8, 4, 0>', 'glayer16_kernel<2, 8, 4, 1>', 'glayer16_
         'conv_wgrad_tile16_kernel<4, 7, true, true>', 'conv_wgrad_tile16_kernel<3, 4, true, true>', 'conv_wgrad_tile16_kernel<2, 2, true, true>', 'conv_tile16_kernel<4, 8>', 'conv_tile16_kernel<3, 8>', 'conv_tile16_kernel<2, 8>', 'conv_tile16_kernel<3, 4>', 'conv_tile16_kernel<2, 4>', 'conv_tile16_kernel<1, 4>', 'conv_span16_kernel<3>', 'conv_wgrad_tile16_kernel<4, 7, true>', 'conv_wgrad_tile16_kernel<4, 7, false>', 'conv_wgrad_tile16_kernel<3, 4, false>',
         'haspi_gain_lp_sl_kernel', 'haspi_ihc_fir_kernel', 'haspi_ihc_fir9_kernel', 'haspi_mod_slide_kernel<0>', 'haspi_cep_kernel', 'haspi_resample_kernel', 'haspi_bank_tail_kernel<true>', 'haspi_bank_tail_kernel<false>',
         'siib_quad_kernel', 'siib_lag_kernel<0, 1, -14, 29>', 'eigh_invit_kernel', 'eigh_bisect_kernel', 'conv_wgrad_tile16_kernel<1, 2, true, true>', 'haspi_bank_scan_kernel<true, true, false, true>', 'haspi_bank_scan_kernel<false, true, false, false>',
-        'eigh_backtransform_wy_kernel', 'eigh_tridiag_mid_kernel', 'siib_stack_kernel',
+        'eigh_backtransform_wy_kernel', 'siib_stack_kernel',
         'haspi_mod_slide_kernel<1>', 'stft_band_kernel', 'gain_istft_kernel', 'siib_proj_kernel<2>', 'siib_cov_kernel',
         'eigh_tridiag_cluster4_kernel', 'eigh_tridiag_clusters_kernel', 'eigh_invit2_kernel', 'conv1d_tile16_kernel<4>', 'adam_guarded_kernel',
         'siib_spec_wave_kernel', 'siib_spec_kernel', 'siib_db_kernel', 'stft_band_wave_kernel', 'gain_istft_wave_kernel', 'eigh_tridiag_midx_kernel', 'estoi_resample5_kernel')
