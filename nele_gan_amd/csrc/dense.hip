@@ -527,6 +527,39 @@ __device__ __forceinline__ int g_hout(const Tile16Args& p) { return p.g.Hout; }
 #define TILE16_TW 64
 #define TILE16_SBMAX 9
 
+// 2-D tile kernels, 1-D grid, XCD-aware: workgroup w runs on XCD w % 8; each XCD takes a contiguous run of tiles (tile columns fastest, then
+// tile rows, then utterances), so the tiles that share halo rows / columns are neighbours in one L2 instead of strangers in eight.
+// false: this workgroup has no tile
+template <int TH>
+__device__ __forceinline__ bool tile16_decode(const Tile16Args& p, int& wo0, int& ho0, int& b) {
+    const int ntw = (g_wout(p) + TILE16_TW - 1) / TILE16_TW, nth = (g_hout(p) + TH - 1) / TH;
+    const int per = (int)((gridDim.x + 7) >> 3);
+    const int tile = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
+    if (tile >= p.ntiles) return false;
+    const int tw_i = tile % ntw, rem = tile / ntw;
+    wo0 = tw_i * TILE16_TW; ho0 = (rem % nth) * TH; b = rem / nth;
+    return true;
+}
+// Tail of the store epilogue of the 2-D tile and the strip kernels: bias, LeakyReLU, mask-gradient or exp-tanh on the 4 channels from n of
+// output position (b, ho, wo), then the float4 store at o_off
+__device__ __forceinline__ void tile16_epi_store(const Tile16Args& p, float4 v, size_t o_off, int b, int ho, int wo, int n) {
+    const ConvGeom& g = p.g;
+    if (p.epi == EPI_BIAS || p.epi == EPI_BIAS_LRELU || p.epi == EPI_BIAS_EXPTANH) {
+        v.x += p.bias[n]; v.y += p.bias[n + 1]; v.z += p.bias[n + 2]; v.w += p.bias[n + 3];   // bias may be only 4-byte aligned
+    }
+    if (p.epi == EPI_BIAS_LRELU) {
+        v.x = v.x > 0.f ? v.x : p.slope * v.x; v.y = v.y > 0.f ? v.y : p.slope * v.y;
+        v.z = v.z > 0.f ? v.z : p.slope * v.z; v.w = v.w > 0.f ? v.w : p.slope * v.w;
+    } else if (p.epi == EPI_MASK_LRELU_GRAD) {
+        const float4 x = *reinterpret_cast<const float4*>(p.aux + (((size_t)b * g.Hout + ho) * g.Wout + wo) * g.OC + n);
+        v.x = x.x > 0.f ? v.x : p.slope * v.x; v.y = x.y > 0.f ? v.y : p.slope * v.y;
+        v.z = x.z > 0.f ? v.z : p.slope * v.z; v.w = x.w > 0.f ? v.w : p.slope * v.w;
+    } else if (p.epi == EPI_BIAS_EXPTANH) {
+        v.x = expf(3.2f * tanhf(v.x)); v.y = expf(3.2f * tanhf(v.y)); v.z = expf(3.2f * tanhf(v.z)); v.w = expf(3.2f * tanhf(v.w));
+    }
+    *reinterpret_cast<float4*>(p.out + o_off) = v;
+}
+
 template <int TN, int TH>
 __global__ __launch_bounds__(256) void conv_tile16_kernel(Tile16Args p) {
     extern __shared__ __attribute__((aligned(16))) __bf16 halo[];    // [TH+KH-1][RS] + 64 slack, then the weight chunk [SB][TN][64][8]
@@ -535,17 +568,8 @@ __global__ __launch_bounds__(256) void conv_tile16_kernel(Tile16Args p) {
 #endif
     const ConvGeom& g = p.g;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
-    // 1-D grid, XCD-aware: workgroup w runs on XCD w % 8; each XCD takes a contiguous run of tiles (tile columns fastest, then tile
-    // rows, then utterances), so the tiles that share halo rows / columns are neighbours in one L2 instead of strangers in eight
     int wo0, ho0, b;
-    {
-        const int ntw = (g_wout(p) + TILE16_TW - 1) / TILE16_TW, nth = (g_hout(p) + TH - 1) / TH;
-        const int per = (int)((gridDim.x + 7) >> 3);
-        const int tile = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
-        if (tile >= p.ntiles) return;
-        const int tw_i = tile % ntw, rem = tile / ntw;
-        wo0 = tw_i * TILE16_TW; ho0 = (rem % nth) * TH; b = rem / nth;
-    }
+    if (!tile16_decode<TH>(p, wo0, ho0, b)) return;
     const int wcols = TILE16_TW + p.KW - 1;            // halo columns
     const int RS = wcols * g.C;                        // halo row stride (elements)
     const int nrows = TH + p.KH - 1;
@@ -756,20 +780,7 @@ __global__ __launch_bounds__(256) void conv_tile16_kernel(Tile16Args p) {
             if (wo < g.Wout && n < p.N) {
                 float4 v = *reinterpret_cast<const float4*>(&ep[pr * 68 + n]);
                 const size_t o_off = (((size_t)b * g.OH + ho + g.oh0) * g.OW + wo + g.ow0) * g.OC + n;
-                if (p.epi == EPI_BIAS || p.epi == EPI_BIAS_LRELU || p.epi == EPI_BIAS_EXPTANH) {
-                    v.x += p.bias[n]; v.y += p.bias[n + 1]; v.z += p.bias[n + 2]; v.w += p.bias[n + 3];   // bias may be only 4-byte aligned
-                }
-                if (p.epi == EPI_BIAS_LRELU) {
-                    v.x = v.x > 0.f ? v.x : p.slope * v.x; v.y = v.y > 0.f ? v.y : p.slope * v.y;
-                    v.z = v.z > 0.f ? v.z : p.slope * v.z; v.w = v.w > 0.f ? v.w : p.slope * v.w;
-                } else if (p.epi == EPI_MASK_LRELU_GRAD) {
-                    const float4 x = *reinterpret_cast<const float4*>(p.aux + (((size_t)b * g.Hout + ho) * g.Wout + wo) * g.OC + n);
-                    v.x = x.x > 0.f ? v.x : p.slope * v.x; v.y = x.y > 0.f ? v.y : p.slope * v.y;
-                    v.z = x.z > 0.f ? v.z : p.slope * v.z; v.w = x.w > 0.f ? v.w : p.slope * v.w;
-                } else if (p.epi == EPI_BIAS_EXPTANH) {
-                    v.x = expf(3.2f * tanhf(v.x)); v.y = expf(3.2f * tanhf(v.y)); v.z = expf(3.2f * tanhf(v.z)); v.w = expf(3.2f * tanhf(v.w));
-                }
-                *reinterpret_cast<float4*>(p.out + o_off) = v;
+                tile16_epi_store(p, v, o_off, b, ho, wo, n);
             }
         }
     }
@@ -780,7 +791,7 @@ __global__ __launch_bounds__(256) void conv_tile16_kernel(Tile16Args p) {
 
 // Split-operand form of conv_tile16_kernel (bf16x3 mode): the halo is staged twice (hi = bf16(x), lo = bf16(x - hi)), each weight chunk
 // carries the hi and the lo fragments (p.Wfrag, wlo: the same layout), and every k-step issues lo*hi, hi*lo, then hi*hi.  Twice the halo
-// bytes of the bf16 kernel: tile heights 4 and 2, weight chunks of at most TILE16_SBMAX_X3 steps (tile16x3_lds).
+// bytes of the bf16 kernel: tile heights 4 and 2, weight chunks of at most TILE16_SBMAX_X3 steps (tile16_lds with x3 = true).
 #define TILE16_SBMAX_X3 4
 template <int TN, int TH>
 __global__ __launch_bounds__(256) void conv_tile16x3_kernel(Tile16Args p, const __bf16* wlo) {
@@ -788,14 +799,7 @@ __global__ __launch_bounds__(256) void conv_tile16x3_kernel(Tile16Args p, const 
     const ConvGeom& g = p.g;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
     int wo0, ho0, b;
-    {
-        const int ntw = (g_wout(p) + TILE16_TW - 1) / TILE16_TW, nth = (g_hout(p) + TH - 1) / TH;
-        const int per = (int)((gridDim.x + 7) >> 3);
-        const int tile = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
-        if (tile >= p.ntiles) return;
-        const int tw_i = tile % ntw, rem = tile / ntw;
-        wo0 = tw_i * TILE16_TW; ho0 = (rem % nth) * TH; b = rem / nth;
-    }
+    if (!tile16_decode<TH>(p, wo0, ho0, b)) return;
     const int wcols = TILE16_TW + p.KW - 1;
     const int RS = wcols * g.C;
     const int nrows = TH + p.KH - 1;
@@ -961,20 +965,7 @@ __global__ __launch_bounds__(256) void conv_tile16x3_kernel(Tile16Args p, const 
             if (wo < g.Wout && n < p.N) {
                 float4 v = *reinterpret_cast<const float4*>(&ep[pr * 68 + n]);
                 const size_t o_off = (((size_t)b * g.OH + ho + g.oh0) * g.OW + wo + g.ow0) * g.OC + n;
-                if (p.epi == EPI_BIAS || p.epi == EPI_BIAS_LRELU || p.epi == EPI_BIAS_EXPTANH) {
-                    v.x += p.bias[n]; v.y += p.bias[n + 1]; v.z += p.bias[n + 2]; v.w += p.bias[n + 3];
-                }
-                if (p.epi == EPI_BIAS_LRELU) {
-                    v.x = v.x > 0.f ? v.x : p.slope * v.x; v.y = v.y > 0.f ? v.y : p.slope * v.y;
-                    v.z = v.z > 0.f ? v.z : p.slope * v.z; v.w = v.w > 0.f ? v.w : p.slope * v.w;
-                } else if (p.epi == EPI_MASK_LRELU_GRAD) {
-                    const float4 x = *reinterpret_cast<const float4*>(p.aux + (((size_t)b * g.Hout + ho) * g.Wout + wo) * g.OC + n);
-                    v.x = x.x > 0.f ? v.x : p.slope * v.x; v.y = x.y > 0.f ? v.y : p.slope * v.y;
-                    v.z = x.z > 0.f ? v.z : p.slope * v.z; v.w = x.w > 0.f ? v.w : p.slope * v.w;
-                } else if (p.epi == EPI_BIAS_EXPTANH) {
-                    v.x = expf(3.2f * tanhf(v.x)); v.y = expf(3.2f * tanhf(v.y)); v.z = expf(3.2f * tanhf(v.z)); v.w = expf(3.2f * tanhf(v.w));
-                }
-                *reinterpret_cast<float4*>(p.out + o_off) = v;
+                tile16_epi_store(p, v, o_off, b, ho, wo, n);
             }
         }
     }
@@ -995,6 +986,18 @@ __global__ __launch_bounds__(256) void conv_tile16x3_kernel(Tile16Args p, const 
 #define C1D_PADE 8
 #endif
 #define C1D_PAD(C_) (((C_) % 128 == 0) ? C1D_PADE : 0)
+// strip kernels, 1-D grid, XCD-aware: the N-chunk workgroups of one input strip (they stage the same strip) get ids of one XCD.
+// false: this workgroup has no strip
+__device__ __forceinline__ bool c1d_decode(const Tile16Args& p, int& wo0, int& nb, int& bz) {
+    const int nchN = p.ntiles;                        // N chunks per strip (host)
+    const int gx = (p.g.Wout + C1D_TW - 1) / C1D_TW;
+    const int w = (int)blockIdx.x, slot = w >> 3;
+    const int strip = (slot / nchN) * 8 + (w & 7);
+    nb = slot % nchN;
+    if (strip >= gx * p.SBH) return false;
+    wo0 = (strip % gx) * C1D_TW; bz = strip / gx;
+    return true;
+}
 // -DC1_PROF: phase clocks of thread 0 of every workgroup (diagnostic build; tools/g_check.py prints them)
 #ifdef C1_PROF
 __device__ unsigned long long c1_prof[8];        // 0 strip staging, 1 first weights + barrier, 2 MFMA chunks, 3 chunk-end store + barrier, 4 epilogue, 5 workgroups
@@ -1013,17 +1016,8 @@ __global__ __launch_bounds__(256) void conv1d_tile16_kernel(Tile16Args p) {
     extern __shared__ __attribute__((aligned(16))) __bf16 halo[];    // [RS] + 64 slack, then the weight chunk [SB][TN][64][8]
     const ConvGeom& g = p.g;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
-    // 1-D grid, XCD-aware: the N-chunk workgroups of one input strip (they stage the same strip) get ids of one XCD
     int wo0, nb, bz;
-    {
-        const int nchN = p.ntiles;                        // N chunks per strip (host)
-        const int gx = (g.Wout + C1D_TW - 1) / C1D_TW;
-        const int w = (int)blockIdx.x, slot = w >> 3;
-        const int strip = (slot / nchN) * 8 + (w & 7);
-        nb = slot % nchN;
-        if (strip >= gx * p.SBH) return;
-        wo0 = (strip % gx) * C1D_TW; bz = strip / gx;
-    }
+    if (!c1d_decode(p, wo0, nb, bz)) return;
     const int b = bz / g.Hout, ho = bz - b * g.Hout;
     const int wcols = C1D_TW + p.KW - 1;
     const int CP = g.C + (((g.C & (g.C - 1)) == 0) ? C1D_PAD(g.C) : 0);   // position stride in LDS (see C1D_PAD; padded only for powers of two)
@@ -1198,20 +1192,7 @@ __global__ __launch_bounds__(256) void conv1d_tile16_kernel(Tile16Args p) {
             if (wo < g.Wout && n < p.N) {
                 float4 v = *reinterpret_cast<const float4*>(&ep[pr * 68 + 4 * cq]);
                 const size_t o_off = (((size_t)b * g.OH + ho + g.oh0) * g.OW + wo + g.ow0) * g.OC + n;
-                if (p.epi == EPI_BIAS || p.epi == EPI_BIAS_LRELU || p.epi == EPI_BIAS_EXPTANH) {
-                    v.x += p.bias[n]; v.y += p.bias[n + 1]; v.z += p.bias[n + 2]; v.w += p.bias[n + 3];
-                }
-                if (p.epi == EPI_BIAS_LRELU) {
-                    v.x = v.x > 0.f ? v.x : p.slope * v.x; v.y = v.y > 0.f ? v.y : p.slope * v.y;
-                    v.z = v.z > 0.f ? v.z : p.slope * v.z; v.w = v.w > 0.f ? v.w : p.slope * v.w;
-                } else if (p.epi == EPI_MASK_LRELU_GRAD) {
-                    const float4 x = *reinterpret_cast<const float4*>(p.aux + (((size_t)b * g.Hout + ho) * g.Wout + wo) * g.OC + n);
-                    v.x = x.x > 0.f ? v.x : p.slope * v.x; v.y = x.y > 0.f ? v.y : p.slope * v.y;
-                    v.z = x.z > 0.f ? v.z : p.slope * v.z; v.w = x.w > 0.f ? v.w : p.slope * v.w;
-                } else if (p.epi == EPI_BIAS_EXPTANH) {
-                    v.x = expf(3.2f * tanhf(v.x)); v.y = expf(3.2f * tanhf(v.y)); v.z = expf(3.2f * tanhf(v.z)); v.w = expf(3.2f * tanhf(v.w));
-                }
-                *reinterpret_cast<float4*>(p.out + o_off) = v;
+                tile16_epi_store(p, v, o_off, b, ho, wo, n);
             }
         }
     }
@@ -1233,17 +1214,8 @@ __global__ __launch_bounds__(256) void conv1d_tile16x3_kernel(Tile16Args p, cons
     extern __shared__ __attribute__((aligned(16))) __bf16 halo[];    // hi [RS] + 64 slack, lo [RS] + 64, then two weight slots (hi, lo chunks)
     const ConvGeom& g = p.g;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
-    // 1-D grid, XCD-aware: the N-chunk workgroups of one input strip (they stage the same strip) get ids of one XCD
     int wo0, nb, bz;
-    {
-        const int nchN = p.ntiles;                        // N chunks per strip (host)
-        const int gx = (g.Wout + C1D_TW - 1) / C1D_TW;
-        const int w = (int)blockIdx.x, slot = w >> 3;
-        const int strip = (slot / nchN) * 8 + (w & 7);
-        nb = slot % nchN;
-        if (strip >= gx * p.SBH) return;
-        wo0 = (strip % gx) * C1D_TW; bz = strip / gx;
-    }
+    if (!c1d_decode(p, wo0, nb, bz)) return;
     const int b = bz / g.Hout, ho = bz - b * g.Hout;
     const int wcols = C1D_TW + p.KW - 1;
     const int CP = g.C + (((g.C & (g.C - 1)) == 0) ? C1D_PAD(g.C) : 0);   // position stride in LDS (see C1D_PAD; padded only for powers of two)
@@ -1430,20 +1402,7 @@ __global__ __launch_bounds__(256) void conv1d_tile16x3_kernel(Tile16Args p, cons
             if (wo < g.Wout && n < p.N) {
                 float4 v = *reinterpret_cast<const float4*>(&ep[pr * 68 + 4 * cq]);
                 const size_t o_off = (((size_t)b * g.OH + ho + g.oh0) * g.OW + wo + g.ow0) * g.OC + n;
-                if (p.epi == EPI_BIAS || p.epi == EPI_BIAS_LRELU || p.epi == EPI_BIAS_EXPTANH) {
-                    v.x += p.bias[n]; v.y += p.bias[n + 1]; v.z += p.bias[n + 2]; v.w += p.bias[n + 3];
-                }
-                if (p.epi == EPI_BIAS_LRELU) {
-                    v.x = v.x > 0.f ? v.x : p.slope * v.x; v.y = v.y > 0.f ? v.y : p.slope * v.y;
-                    v.z = v.z > 0.f ? v.z : p.slope * v.z; v.w = v.w > 0.f ? v.w : p.slope * v.w;
-                } else if (p.epi == EPI_MASK_LRELU_GRAD) {
-                    const float4 x = *reinterpret_cast<const float4*>(p.aux + (((size_t)b * g.Hout + ho) * g.Wout + wo) * g.OC + n);
-                    v.x = x.x > 0.f ? v.x : p.slope * v.x; v.y = x.y > 0.f ? v.y : p.slope * v.y;
-                    v.z = x.z > 0.f ? v.z : p.slope * v.z; v.w = x.w > 0.f ? v.w : p.slope * v.w;
-                } else if (p.epi == EPI_BIAS_EXPTANH) {
-                    v.x = expf(3.2f * tanhf(v.x)); v.y = expf(3.2f * tanhf(v.y)); v.z = expf(3.2f * tanhf(v.z)); v.w = expf(3.2f * tanhf(v.w));
-                }
-                *reinterpret_cast<float4*>(p.out + o_off) = v;
+                tile16_epi_store(p, v, o_off, b, ho, wo, n);
             }
         }
     }
@@ -1914,6 +1873,24 @@ struct WgradTileArgs {
     int ics, subs_n, subs_c, Kfull;
 };
 
+// Grid of the 2-D tile weight-gradient kernels: 1-D, KH * G workgroups.  Workgroup w runs on XCD w % 8 (round-robin dispatch), and the KH
+// kernel-row workgroups of a group read the same input / dOut tiles at about the same time: they are given ids of one XCD so that its L2
+// serves the repeats (with the natural (kh, group) order the KH readers of a tile sat on different XCDs and every read went to HBM:
+// 1.55 GB per launch for 160 MB of operands)
+__device__ __forceinline__ void wgrad_tile_decode(const WgradTileArgs& p, int& kh, int& grp, int& sub) {
+    const int inner = p.KH * p.subs_n * p.subs_c;      // the workgroups that read one group's tiles: ids of one XCD
+    int rest;
+    if ((p.G & 7) == 0) {
+        const int w = blockIdx.x, xcd = w & 7, slot = w >> 3;
+        rest = slot % inner;
+        grp = (slot / inner) * 8 + xcd;
+    } else {
+        rest = blockIdx.x % inner;
+        grp = blockIdx.x / inner;
+    }
+    kh = rest % p.KH;
+    sub = rest / p.KH;
+}
 template <int NT, int KTW, bool D16 = false, bool A16 = false>      // n tiles (16 each), kk tiles per wave (16 each; tile index = wave + 4 * jj); D16 / A16: dOut / the input activation is bf16 in memory
 __global__ __launch_bounds__(256, 2) void conv_wgrad_tile16_kernel(WgradTileArgs p) {
     static_assert(!A16 || D16, "a bf16 activation comes with a bf16 output gradient");
@@ -1923,25 +1900,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tile16_kernel(WgradTileArgs
     const ConvGeom& g = p.g;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);          // wave-uniform: the tile tests below are scalar branches
-    // grid: 1-D, KH * G workgroups.  Workgroup w runs on XCD w % 8 (round-robin dispatch), and the KH kernel-row workgroups of a group
-    // read the same input / dOut tiles at about the same time: they are given ids of one XCD so that its L2 serves the repeats
-    // (with the natural (kh, group) order the KH readers of a tile sat on different XCDs and every read went to HBM: 1.55 GB per launch
-    // for 160 MB of operands)
     int kh, grp, sub;
-    {
-        const int inner = p.KH * p.subs_n * p.subs_c;      // the workgroups that read one group's tiles: ids of one XCD
-        int rest;
-        if ((p.G & 7) == 0) {
-            const int w = blockIdx.x, xcd = w & 7, slot = w >> 3;
-            rest = slot % inner;
-            grp = (slot / inner) * 8 + xcd;
-        } else {
-            rest = blockIdx.x % inner;
-            grp = blockIdx.x / inner;
-        }
-        kh = rest % p.KH;
-        sub = rest / p.KH;
-    }
+    wgrad_tile_decode(p, kh, grp, sub);
     const int sn = sub / p.subs_c, sc = sub - sn * p.subs_c;
     const int n0 = sn * p.N, ic0 = sc * g.C, Nfull = p.N * p.subs_n;
     const int wcols = WT_TW + p.KW - 1, RS = wcols * g.C;
@@ -2180,20 +2140,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tile16x3_kernel(WgradTileAr
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int kh, grp, sub;
-    {
-        const int inner = p.KH * p.subs_n * p.subs_c;
-        int rest;
-        if ((p.G & 7) == 0) {
-            const int w = blockIdx.x, xcd = w & 7, slot = w >> 3;
-            rest = slot % inner;
-            grp = (slot / inner) * 8 + xcd;
-        } else {
-            rest = blockIdx.x % inner;
-            grp = blockIdx.x / inner;
-        }
-        kh = rest % p.KH;
-        sub = rest / p.KH;
-    }
+    wgrad_tile_decode(p, kh, grp, sub);
     const int sn = sub / p.subs_c, sc = sub - sn * p.subs_c;
     const int n0 = sn * p.N, ic0 = sc * g.C, Nfull = p.N * p.subs_n;
     const int wcols = WT_TW + p.KW - 1, RS = wcols * g.C;
@@ -2808,35 +2755,36 @@ extern "C" int nele_weight_prep_frag16(const float* Wg, int N, int Ktot, int seg
     return NELE_OK;
 }
 
-// LDS bytes of the 2-D tile kernel, or 0 when the geometry does not fit it
-static size_t tile16_lds(const ConvGeom& g, int N, int KH, int KW, int TH) {
-    if (N > 64 || N % 4 || g.OC % 4 || g.C % 8 || KH * g.seglen != g.Ktot || KW * g.C != g.seglen) return 0;
-    const long long RS = (long long)(TILE16_TW + KW - 1) * g.C;
-    if (RS > 4096) return 0;                                            // one row travels as 2 x 8 floats per thread
-    const int sps = (g.seglen + 31) / 32, NT = (N + 15) / 16;
-    int SB = 1;
-    for (int d = 1; d <= TILE16_SBMAX; ++d)
-        if (sps % d == 0) SB = d;
-    const long long bytes = ((long long)(TH + KH - 1) * RS + 64) * 2 + (((long long)SB * NT * 1024 + 4095) & ~4095LL);
-    if (bytes > 158 * 1024) return 0;
-    return (size_t)(bytes < 4 * 16 * 68 * 4 ? 4 * 16 * 68 * 4 : bytes);        // the epilogue transposes through 4 x 4352 B
-}
-static int tile16_sb(const ConvGeom& g) {
+// ---- host selectors of the 2-D tile and the strip kernel.  x3: the bf16x3 mode, which stages two images of the halo / strip and of every
+// weight chunk in the same 158 KB and therefore gets shorter chunks (tile16_sbmax, c1d_sbmax), lower tiles and no N-chunk walk.
+constexpr int tile16_sbmax(bool x3) { return x3 ? TILE16_SBMAX_X3 : TILE16_SBMAX; }   // k-steps per weight chunk at most: 2-D tile kernel
+constexpr int c1d_sbmax(bool x3) { return x3 ? C1D_SBMAX_X3 : TILE16_SBMAX; }         // ... Conv1d strip kernel
+static int tile16_sb(const ConvGeom& g, bool x3) {
     const int sps = (g.seglen + 31) / 32;
     int SB = 1;
-    for (int d = 1; d <= TILE16_SBMAX; ++d)
+    for (int d = 1; d <= tile16_sbmax(x3); ++d)
         if (sps % d == 0) SB = d;
     return SB;
 }
+// LDS bytes of the 2-D tile kernel, or 0 when the geometry does not fit it
+static size_t tile16_lds(const ConvGeom& g, int N, int KH, int KW, int TH, bool x3) {
+    if (N > 64 || N % 4 || g.OC % 4 || g.C % 8 || KH * g.seglen != g.Ktot || KW * g.C != g.seglen) return 0;
+    const long long RS = (long long)(TILE16_TW + KW - 1) * g.C;
+    if (RS > 4096) return 0;                                            // one row travels as 2 x 8 floats per thread
+    const int NT = (N + 15) / 16, img = x3 ? 2 : 1;
+    const long long bytes = img * ((long long)(TH + KH - 1) * RS + 64) * 2 + img * (((long long)tile16_sb(g, x3) * NT * 1024 + 4095) & ~4095LL);
+    if (bytes > 158 * 1024) return 0;
+    return (size_t)(bytes < 4 * 16 * 68 * 4 ? 4 * 16 * 68 * 4 : bytes);        // the epilogue transposes through 4 x 4352 B
+}
 // Conv1d / Linear tile kernel: steps per weight chunk and LDS bytes, or 0
-static int conv1d16_sb(const ConvGeom& g, int N, int KH, int KW, size_t* lds_out) {
+static int conv1d16_sb(const ConvGeom& g, int N, int KH, int KW, size_t* lds_out, bool x3) {
     if (KH != 1 || N % 4 || g.OC % 4 || g.C % 8 || KW * g.C != g.seglen || g.seglen != g.Ktot || g.seglen % 32) return 0;
     if (N > 64 && N % 64) return 0;
     const long long RS = (long long)(C1D_TW + KW - 1) * (g.C + (((g.C & (g.C - 1)) == 0) ? C1D_PAD(g.C) : 0));
-    const int sps = g.seglen / 32, TNsel = (N >= 64) ? 4 : (N + 15) / 16;
-    for (int d = TILE16_SBMAX; d >= 1; --d) {
+    const int sps = g.seglen / 32, TNsel = (N >= 64) ? 4 : (N + 15) / 16, img = x3 ? 2 : 1;
+    for (int d = c1d_sbmax(x3); d >= 1; --d) {
         if (sps % d) continue;
-        const long long bytes = (RS + 64) * 2 + 2 * (((long long)d * TNsel * 1024 + 4095) & ~4095LL);     // strip + two weight slots
+        const long long bytes = img * (RS + 64) * 2 + 2 * img * (((long long)d * TNsel * 1024 + 4095) & ~4095LL);     // strip + two weight slots
         if (bytes <= 158 * 1024) {
             if (lds_out) *lds_out = (size_t)(bytes < 4 * 16 * 68 * 4 ? 4 * 16 * 68 * 4 : bytes);
             return d;
@@ -2844,18 +2792,74 @@ static int conv1d16_sb(const ConvGeom& g, int N, int KH, int KW, size_t* lds_out
     }
     return 0;
 }
-// Tile height: 4 or 8 rows.  Taller tiles (10, 11 or 13 rows, whichever wastes the fewest output rows) need fewer LDS reads per MFMA and
-// made D.conv5 forward alone faster at B = 256 (1.70 -> 1.62 ms), but the whole step slower (75.6 -> 76.9 ms): their 160 KB of LDS leaves
-// no room for the metric streams' workgroups beside them, and the step is bound by the sum of all kernels, not by the convolutions.
-static int tile16_th(const ConvGeom& g, int N, int KH, int KW) {
+// Tile height: 4 or 8 rows (x3: 4, or 2 where 4 does not fit).  Taller tiles (10, 11 or 13 rows, whichever wastes the fewest output rows)
+// need fewer LDS reads per MFMA and made D.conv5 forward alone faster at B = 256 (1.70 -> 1.62 ms), but the whole step slower (75.6 ->
+// 76.9 ms): their 160 KB of LDS leaves no room for the metric streams' workgroups beside them, and the step is bound by the sum of all
+// kernels, not by the convolutions.
+static int tile16_th(const ConvGeom& g, int N, int KH, int KW, bool x3) {
+    if (x3) return tile16_lds(g, N, KH, KW, 4, true) ? 4 : (tile16_lds(g, N, KH, KW, 2, true) ? 2 : 0);
     // 64 output channels (D.conv5 forward, the 64-wide gradients): 8-row tiles; fewer channels: 4-row tiles.  Measured inside the
     // B = 256 step (tools/ab.sh, three alternating repetitions): all 8-row 75.5 ms, all 4-row 73.9 ms (but D.conv5 forward alone
     // 1.96 instead of 1.70 ms), this mix 73.9 ms with D.conv5 at 1.74 ms: the narrow layers (TN <= 3) are bound by their LDS reads
     // either way, and the smaller halo leaves room for the workgroups of the other streams.
-    if (N < 64 && tile16_lds(g, N, KH, KW, 4)) return 4;
-    if (g.Hout >= 8 && tile16_lds(g, N, KH, KW, 8)) return 8;
-    if (tile16_lds(g, N, KH, KW, 4)) return 4;
+    if (N < 64 && tile16_lds(g, N, KH, KW, 4, false)) return 4;
+    if (g.Hout >= 8 && tile16_lds(g, N, KH, KW, 8, false)) return 8;
+    if (tile16_lds(g, N, KH, KW, 4, false)) return 4;
     return 0;
+}
+
+// ---- launches of the two kernels in either mode: t holds the operands, epilogue and geometry; wlo is the lo weight stream (x3)
+typedef void (*Tile16Launch)(dim3 grid, size_t lds, hipStream_t s, const Tile16Args& t, const __bf16* wlo);
+template <int TN, int TH, bool X3>
+static void tile16_launch(dim3 grid, size_t lds, hipStream_t s, const Tile16Args& t, const __bf16* wlo) {
+    if constexpr (X3) {
+        NELE_ONCE_PER_DEVICE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_tile16x3_kernel<TN, TH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        hipLaunchKernelGGL((conv_tile16x3_kernel<TN, TH>), grid, dim3(256), lds, s, t, wlo);
+    } else {
+        NELE_ONCE_PER_DEVICE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_tile16_kernel<TN, TH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        hipLaunchKernelGGL((conv_tile16_kernel<TN, TH>), grid, dim3(256), lds, s, t);
+    }
+}
+template <int TN, bool X3>
+static void conv1d16_launch(dim3 grid, size_t lds, hipStream_t s, const Tile16Args& t, const __bf16* wlo) {
+    if constexpr (X3) {
+        NELE_ONCE_PER_DEVICE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_tile16x3_kernel<TN>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        hipLaunchKernelGGL((conv1d_tile16x3_kernel<TN>), grid, dim3(256), lds, s, t, wlo);
+    } else {
+        NELE_ONCE_PER_DEVICE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_tile16_kernel<TN>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        hipLaunchKernelGGL((conv1d_tile16_kernel<TN>), grid, dim3(256), lds, s, t);
+    }
+}
+template <bool X3>
+static void conv1d16_run(Tile16Args& t, const __bf16* wlo, int M, int csb, size_t clds, hipStream_t s) {
+    static const Tile16Launch launch[4] = {conv1d16_launch<1, X3>, conv1d16_launch<2, X3>, conv1d16_launch<3, X3>, conv1d16_launch<4, X3>};
+    const int BH = M / t.g.Wout;
+    const int nchunksN = (t.N > 64) ? t.N / 64 : 1, TNsel = (t.N >= 64) ? 4 : t.NT;
+    const int nstrips = ((t.g.Wout + C1D_TW - 1) / C1D_TW) * BH;
+    const size_t ep_bytes = 4 * 16 * 68 * 4;
+    const bool walk = !X3 && nchunksN > 1 && nstrips >= 256 && clds + 4096 + ep_bytes <= 158 * 1024;
+    t.SB = csb; t.steps_per_seg = t.g.seglen / 32;
+    t.ntiles = walk ? 1 : nchunksN; t.ncl = walk ? nchunksN : 1; t.SBH = BH;
+    if (walk) clds = ((clds + 2047) & ~(size_t)2047) + 4096 + ep_bytes;
+    launch[TNsel - 1](dim3((unsigned)(t.ntiles * 8 * ((nstrips + 7) / 8))), clds, s, t, wlo);
+}
+template <bool X3>
+static void tile16_run(Tile16Args& t, const __bf16* wlo, int M, int th, hipStream_t s) {
+    constexpr int THA = X3 ? 4 : 8, THB = X3 ? 2 : 4;     // the two tile heights of the mode
+    static const Tile16Launch launch[2][4] = {{tile16_launch<1, THA, X3>, tile16_launch<2, THA, X3>, tile16_launch<3, THA, X3>, tile16_launch<4, THA, X3>},
+                                              {tile16_launch<1, THB, X3>, tile16_launch<2, THB, X3>, tile16_launch<3, THB, X3>, tile16_launch<4, THB, X3>}};
+    t.SB = tile16_sb(t.g, X3);
+    const int B_ = M / (t.g.Hout * t.g.Wout);
+    const size_t lds = tile16_lds(t.g, t.N, t.KH, t.KW, th, X3);
+    t.ntiles = ((t.g.Wout + TILE16_TW - 1) / TILE16_TW) * ((t.g.Hout + th - 1) / th) * B_;
+    const dim3 grid((unsigned)((t.ntiles + 7) / 8 * 8));      // a multiple of 8: every XCD gets the same number of ids
+    // measurement hook (x3): "tile16x3_N<N>_K<Ktot>" times one layer's launch (D.conv5 forward: tile16x3_N64_K3888)
+    char ptag[48] = "";
+    if (X3 && nele_prof_armed()) snprintf(ptag, sizeof(ptag), "tile16x3_N%d_K%d", t.N, t.g.Ktot);
+    const bool prof_t = ptag[0] && nele_prof_match(ptag);
+    if (prof_t) nele_prof_mark(s);
+    launch[th == THA ? 0 : 1][t.NT - 1](grid, lds, s, t, wlo);
+    if (prof_t) nele_prof_mark(s);
 }
 static int span16_supported(int M, int N, const ConvGeom& g, int KH, int KW) {
     if (N > 64 || g.C % 8 || g.Wout < 64 || KH * g.seglen != g.Ktot || KW * g.C != g.seglen) return 0;
@@ -2869,8 +2873,8 @@ static int span16_supported(int M, int N, const ConvGeom& g, int KH, int KW) {
 extern "C" int nele_conv_span_bf16_supported(int M, int N, const int* geom, int KH, int KW) {
     ConvGeom g;
     memcpy(&g, geom, sizeof(ConvGeom));
-    if (g.Wout >= 32 && tile16_th(g, N, KH, KW)) return 1;
-    if (g.Wout >= 32 && conv1d16_sb(g, N, KH, KW, nullptr)) return 1;
+    if (g.Wout >= 32 && tile16_th(g, N, KH, KW, false)) return 1;
+    if (g.Wout >= 32 && conv1d16_sb(g, N, KH, KW, nullptr, false)) return 1;
     return span16_supported(M, N, g, KH, KW);
 }
 static int conv_span_bf16_impl(const float* A, const void* Wfrag, const float* bias, const float* aux, float* out, int M, int N, int epi,
@@ -2888,8 +2892,8 @@ extern "C" int nele_conv_span_bf16_a16(const void* A16, const void* Wfrag, const
 extern "C" int nele_conv_span_bf16_a16_supported(int M, int N, const int* geom, int KH, int KW) {
     ConvGeom g;
     memcpy(&g, geom, sizeof(ConvGeom));
-    if (g.Wout >= 32 && tile16_th(g, N, KH, KW)) return 0;
-    if (g.Wout >= 32 && conv1d16_sb(g, N, KH, KW, nullptr)) return 0;
+    if (g.Wout >= 32 && tile16_th(g, N, KH, KW, false)) return 0;
+    if (g.Wout >= 32 && conv1d16_sb(g, N, KH, KW, nullptr, false)) return 0;
     return span16_supported(M, N, g, KH, KW);
 }
 static int conv_span_bf16_impl(const float* A, const void* Wfrag, const float* bias, const float* aux, float* out, int M, int N, int epi,
@@ -2908,61 +2912,19 @@ static int conv_span_bf16_impl(const float* A, const void* Wfrag, const float* b
     NELE_CHECK_ARG(!(epi == EPI_BIAS || epi == EPI_BIAS_LRELU || epi == EPI_BIAS_EXPTANH) || bias, "nele_conv_span_bf16: epilogue needs bias");
     NELE_CHECK_ARG(epi != EPI_MASK_LRELU_GRAD || aux, "nele_conv_span_bf16: epilogue needs aux");
     hipStream_t s = as_stream(stream);
-    const int th = (p.g.Wout >= 32) ? tile16_th(p.g, N, KH, KW) : 0;
-    {   // Conv1d / Linear geometry (KH = 1): strip kernel
-        size_t clds = 0;
-        const int csb = (KH == 1 && p.g.Wout >= 32) ? conv1d16_sb(p.g, N, KH, KW, &clds) : 0;
-        if (csb) {
-            Tile16Args t;
-            t.A = A; t.Wfrag = p.Wfrag; t.bias = bias; t.aux = aux; t.out = out; t.N = N; t.NT = p.NT; t.epi = epi; t.slope = slope;
-            t.KH = KH; t.KW = KW; t.steps_per_seg = p.g.seglen / 32; t.g = p.g; t.SB = csb; t.dbg = nullptr;
-            const int BH = M / p.g.Wout;
-            static unsigned long long cattr = 0;            // (per device: a process that switches devices sets the attribute on each)
-            if (nele_first_use_on_device(&cattr)) {
-#define C1D_ATTR(TN_) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_tile16_kernel<TN_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-                C1D_ATTR(1); C1D_ATTR(2); C1D_ATTR(3); C1D_ATTR(4);
-#undef C1D_ATTR
-            }
-            const int nchunksN = (N > 64) ? N / 64 : 1, TNsel = (N >= 64) ? 4 : p.NT;
-            const int nstrips = ((p.g.Wout + C1D_TW - 1) / C1D_TW) * BH;
-            const size_t ep_bytes = 4 * 16 * 68 * 4;
-            const bool walk = nchunksN > 1 && nstrips >= 256 && clds + 4096 + ep_bytes <= 158 * 1024;
-            t.ntiles = walk ? 1 : nchunksN; t.ncl = walk ? nchunksN : 1; t.SBH = BH;
-            if (walk) clds = ((clds + 2047) & ~(size_t)2047) + 4096 + ep_bytes;
-            const dim3 grid((unsigned)(t.ntiles * 8 * ((nstrips + 7) / 8)));
-            switch (TNsel) {
-                case 1: hipLaunchKernelGGL((conv1d_tile16_kernel<1>), grid, dim3(256), clds, s, t); break;
-                case 2: hipLaunchKernelGGL((conv1d_tile16_kernel<2>), grid, dim3(256), clds, s, t); break;
-                case 3: hipLaunchKernelGGL((conv1d_tile16_kernel<3>), grid, dim3(256), clds, s, t); break;
-                default: hipLaunchKernelGGL((conv1d_tile16_kernel<4>), grid, dim3(256), clds, s, t); break;
-            }
-            NELE_CHECK_LAUNCH("nele_conv_span_bf16(conv1d)");
-            return NELE_OK;
-        }
+    Tile16Args t;
+    t.A = A; t.Wfrag = p.Wfrag; t.bias = bias; t.aux = aux; t.out = out; t.N = N; t.NT = p.NT; t.epi = epi; t.slope = slope;
+    t.KH = KH; t.KW = KW; t.steps_per_seg = p.steps_per_seg; t.g = p.g; t.dbg = nullptr;
+    size_t clds = 0;
+    const int csb = (KH == 1 && p.g.Wout >= 32) ? conv1d16_sb(p.g, N, KH, KW, &clds, false) : 0;
+    if (csb) {      // Conv1d / Linear geometry (KH = 1): strip kernel
+        conv1d16_run<false>(t, nullptr, M, csb, clds, s);
+        NELE_CHECK_LAUNCH("nele_conv_span_bf16(conv1d)");
+        return NELE_OK;
     }
+    const int th = (p.g.Wout >= 32) ? tile16_th(p.g, N, KH, KW, false) : 0;
     if (th) {
-        Tile16Args t;
-        t.A = A; t.Wfrag = p.Wfrag; t.bias = bias; t.aux = aux; t.out = out; t.N = N; t.NT = p.NT; t.epi = epi; t.slope = slope;
-        t.KH = KH; t.KW = KW; t.steps_per_seg = p.steps_per_seg; t.g = p.g; t.SB = tile16_sb(p.g); t.dbg = nullptr;
-        const int B_ = M / (p.g.Hout * p.g.Wout);
-        const size_t lds = tile16_lds(p.g, N, KH, KW, th);
-        static unsigned long long tattr = 0;            // (per device: a process that switches devices sets the attribute on each)
-        if (nele_first_use_on_device(&tattr)) {
-#define TILE16_ATTR(TN_, TH_) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_tile16_kernel<TN_, TH_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-            TILE16_ATTR(1, 8); TILE16_ATTR(2, 8); TILE16_ATTR(3, 8); TILE16_ATTR(4, 8);
-            TILE16_ATTR(1, 4); TILE16_ATTR(2, 4); TILE16_ATTR(3, 4); TILE16_ATTR(4, 4);
-#undef TILE16_ATTR
-        }
-        t.ntiles = ((p.g.Wout + TILE16_TW - 1) / TILE16_TW) * ((p.g.Hout + th - 1) / th) * B_;
-        const dim3 grid((unsigned)((t.ntiles + 7) / 8 * 8));      // a multiple of 8: every XCD gets the same number of ids
-#define TILE16_LAUNCH(TN_, TH_) hipLaunchKernelGGL((conv_tile16_kernel<TN_, TH_>), grid, dim3(256), lds, s, t)
-#define TILE16_PICK(TH_) switch (p.NT) { case 1: TILE16_LAUNCH(1, TH_); break; case 2: TILE16_LAUNCH(2, TH_); break; case 3: TILE16_LAUNCH(3, TH_); break; default: TILE16_LAUNCH(4, TH_); break; }
-        switch (th) {
-            case 8: TILE16_PICK(8); break;
-            default: TILE16_PICK(4); break;
-        }
-#undef TILE16_PICK
-#undef TILE16_LAUNCH
+        tile16_run<false>(t, nullptr, M, th, s);
         NELE_CHECK_LAUNCH("nele_conv_span_bf16(tile)");
         return NELE_OK;
     }
@@ -3016,11 +2978,23 @@ extern "C" int nele_conv_wgrad_bf16(const float* A, const float* dOut, float* wo
                                     const int* geom, int KH, int KW, int Cvalid, float* dW, float* db, int accumulate, void* stream) {
     return conv_wgrad_impl(A, dOut, workspace, workspace_floats, M, N, geom, KH, KW, Cvalid, dW, db, accumulate, 1, stream);
 }
+// dynamic LDS of the 2-D tile weight-gradient kernel; x3 (bf16x3 mode): a hi and a lo image of both operands.  The bf16 form keeps two
+// workgroups per CU (76 KB each); the split form gets 160 KB less its 4 KB of static bias-reduction scratch (and checks that its input
+// rows fit the 9 staging pieces of 8 elements per thread: 4 x RS <= 18432 elements).
+#define WTX3_LDS_MAX (156 * 1024)
+static long long wgrad_tile16_lds(int NT, int KW, int C, bool x3) {
+    return (x3 ? 2 : 1) * ((long long)WT_TH * (WT_TW + KW - 1) * C + WT_SLACK + 256 * WT_NP_OF(NT)) * 2;
+}
 static bool wgrad_tile_eligible(int M, int N, const ConvGeom& g, int KH, int KW) {
     const int nkt = (g.seglen + 15) / 16;
-    const long long wt_lds = ((long long)WT_TH * (WT_TW + KW - 1) * g.C + WT_SLACK + 256 * WT_NP_OF((N + 15) / 16)) * 2;
-    return N <= 64 && g.C % 8 == 0 && KW * g.C == g.seglen && nkt <= 28 && g.Wout >= 32 && wt_lds <= 76 * 1024 &&
+    return N <= 64 && g.C % 8 == 0 && KW * g.C == g.seglen && nkt <= 28 && g.Wout >= 32 && wgrad_tile16_lds((N + 15) / 16, KW, g.C, false) <= 76 * 1024 &&
            M % (g.Hout * g.Wout) == 0;
+}
+// groups of position tiles (partial slots of the workspace) the tile kernels are asked for
+static int wgrad_groups(int M, int splits) {
+    const int max_splits = (M + 511) / 512;
+    const int G = (max_splits < 64) ? (max_splits > splits ? max_splits : splits) : 64;
+    return G < splits ? splits : G;
 }
 extern "C" int nele_conv_wgrad_bf16_d16_supported(int M, int N, const int* geom, int KH, int KW) {
     ConvGeom g;
@@ -3058,6 +3032,91 @@ extern "C" int nele_conv_wgrad_bf16_a16d16(const void* A16, const void* dOut16, 
                            accumulate, 7, stream);
 }
 
+// Layers too wide for one workgroup's accumulators (N > 64 or more than 28 reduction tiles per kernel row: the generator's Conv1d
+// layers, 256 x 7 x 256) run on the 2-D tile kernel as subs_n x subs_c sub-problems of 64 output x 64 input channels that share
+// every group's position tiles; a Conv1d batch is viewed as ONE image whose rows are the utterances (KH = 1: rows are independent),
+// so that a tile is 4 utterances x 64 frames.  The im2col-gathering kernel read the input KW times per 128-column block of the
+// gradient: 1.44 GB per launch for 130 MB of operands, 240 us per layer at B = 256.
+static bool wgrad_sliceable(int M, int N, const ConvGeom& g, int KW, bool x3) {
+    return N % 64 == 0 && g.C % 64 == 0 && KW * g.C == g.seglen && KW * 4 <= 28 && g.Wout >= 32 && M % (g.Hout * g.Wout) == 0 &&
+           (!x3 || WT_TH * (WT_TW + KW - 1) * 64 <= 9 * 2048) && wgrad_tile16_lds(4, KW, 64, x3) <= (x3 ? WTX3_LDS_MAX : 76 * 1024);
+}
+enum WgradOperands { WG_F32 = 0, WG_D16, WG_A16D16, WG_X3 };   // float32 in memory; dOut bf16; input and dOut bf16; float32 split (bf16x3)
+typedef void (*WgradTileKernel)(WgradTileArgs);
+// the kernels of one (n tiles, kk tiles per wave), by operand form
+template <int NT, int K>
+static WgradTileKernel wgrad_tile16_fn(WgradOperands ops) {
+    static const WgradTileKernel tab[4] = {conv_wgrad_tile16_kernel<NT, K>, conv_wgrad_tile16_kernel<NT, K, true>, conv_wgrad_tile16_kernel<NT, K, true, true>,
+                                           conv_wgrad_tile16x3_kernel<NT, K>};
+    return tab[ops];
+}
+template <int K>
+static WgradTileKernel wgrad_tile16_fn(int NT, WgradOperands ops) {
+    return NT <= 1 ? wgrad_tile16_fn<1, K>(ops) : NT == 2 ? wgrad_tile16_fn<2, K>(ops) : NT == 3 ? wgrad_tile16_fn<3, K>(ops) : wgrad_tile16_fn<4, K>(ops);
+}
+// One launch of the 2-D tile weight-gradient kernel.  g: the layer; sliced: as 64 x 64-channel sub-problems; G: the group count asked for.
+// Returns the group count used and the bias partials: the partials are workspace [G][N][Ktot], then (db) the bias partials [G][N].
+struct WgradTileRun { int G; float* bpart; };
+static WgradTileRun wgrad_tile16_run(const float* A, const float* dOut, float* workspace, float* db, int M, int N, const ConvGeom& g, int KH,
+                                     int KW, bool sliced, WgradOperands ops, int G, hipStream_t s) {
+    const bool x3 = ops == WG_X3;
+    ConvGeom gt = g;                                       // geometry the tile kernel sees
+    int Nt = N, subs_n = 1, subs_c = 1, Bt = M / (g.Hout * g.Wout);
+    if (sliced) {
+        gt.C = 64; gt.seglen = KW * 64; gt.Ktot = KH * KW * 64;
+        Nt = 64; subs_n = N / 64; subs_c = g.C / 64;
+        if (KH == 1 && g.H == 1 && g.Hout == 1 && g.OH == 1 && g.ih0 == 0 && g.oh0 == 0) { gt.H = Bt; gt.Hout = Bt; gt.OH = Bt; Bt = 1; }
+    }
+    const int nkt = (gt.seglen + 15) / 16, NT = (Nt + 15) / 16, ktw = (nkt + 3) / 4;
+    const size_t lds = (size_t)wgrad_tile16_lds(NT, KW, gt.C, x3);
+    const size_t lds_max = x3 ? WTX3_LDS_MAX : 80 * 1024;
+    const int ki = ktw <= 2 ? 0 : (ktw <= 4 ? 1 : 2), ni = NT < 1 ? 1 : (NT > 4 ? 4 : NT);
+    auto fn_of = [&](WgradOperands v) { return ki == 0 ? wgrad_tile16_fn<2>(ni, v) : (ki == 1 ? wgrad_tile16_fn<4>(ni, v) : wgrad_tile16_fn<7>(ni, v)); };
+    WgradTileArgs t;
+    t.A = A; t.dOut = dOut; t.part = workspace; t.N = Nt; t.B = Bt; t.KH = KH; t.KW = KW; t.d16 = (ops == WG_D16 || ops == WG_A16D16);
+    t.ics = g.C; t.subs_n = subs_n; t.subs_c = subs_c; t.Kfull = g.Ktot;
+    t.nth = (gt.Hout + WT_TH - 1) / WT_TH; t.ntw = (gt.Wout + WT_TW - 1) / WT_TW; t.ntiles = t.B * t.nth * t.ntw;
+    if (G > t.ntiles) G = t.ntiles;
+    const int wg_per_group = KH * subs_n * subs_c;
+    {   // Workgroups that do not fit the chip at once run as a second, nearly empty round: KH * 64 = 576 workgroups on 512 slots (two
+        // per CU for D.conv5) took 1.64 x as long as KH * 56 = 504 (3.20 -> 1.95 ms at B = 256).  Pick the group count (a multiple
+        // of 8, at most the partial slots of the workspace) that minimises rounds x tiles per workgroup.
+        static int ncu = 0;
+        static int occ_tab[5][3] = {{0}};
+        if (!ncu) { int dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev); if (ncu <= 0) ncu = 256; }
+        if (!x3 && !occ_tab[ni][ki]) {                       // workgroups per CU of the bf16 forms
+            int occ = 0;
+            const void* fn = reinterpret_cast<const void*>(fn_of(WG_F32));
+            (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 256, lds) != hipSuccess || occ < 1) occ = 1;
+            hipFuncAttributes fa;
+            if (hipFuncGetAttributes(&fa, fn) == hipSuccess && fa.numRegs > 0) {      // registers: 512 per SIMD lane, one wave of the workgroup per SIMD
+                const int by_regs = 512 / ((fa.numRegs + 7) & ~7);
+                if (by_regs >= 1 && by_regs < occ) occ = by_regs;
+            }
+            occ_tab[ni][ki] = occ;
+        }
+        const long long slots = x3 ? ncu : (long long)ncu * occ_tab[ni][ki];     // x3: one workgroup per CU, by its LDS
+        if (G >= 16) {
+            long long best = -1;
+            int bestG = G;
+            for (int cand = G & ~7; cand >= 8; cand -= 8) {    // (any count up to the workspace's partial slots works for this kernel)
+                const long long rounds = ((long long)wg_per_group * cand + slots - 1) / slots, per = (t.ntiles + cand - 1) / cand;
+                const long long cost = rounds * per;
+                if (best < 0 || cost < best) { best = cost; bestG = cand; }
+            }
+            G = bestG;
+        }
+    }
+    t.G = G; t.g = gt;
+    t.bpart = db ? workspace + (size_t)G * N * g.Ktot : nullptr;
+    const WgradTileKernel fn = fn_of(ops);
+    static unsigned long long wattr[4][5][3] = {{{0}}};     // (per kernel and device: a process that switches devices sets the attribute on each)
+    if (nele_first_use_on_device(&wattr[ops][ni][ki]))
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
+    hipLaunchKernelGGL(fn, dim3(wg_per_group * G), dim3(256), lds, s, t);
+    return {G, t.bpart};
+}
 static int conv_wgrad_impl(const float* A, const float* dOut, float* workspace, long long workspace_floats, int M, int N,
                            const int* geom, int KH, int KW, int Cvalid, float* dW, float* db, int accumulate, int bf16, void* stream) {
     NELE_CHECK_ARG(A && dOut && workspace && geom && dW, "nele_conv_wgrad: null pointer");
@@ -3085,28 +3144,9 @@ static int conv_wgrad_impl(const float* A, const float* dOut, float* workspace, 
         prof_w = nele_prof_match(ptag);
         if (prof_w) nele_prof_mark(s);
     }
-    // 2-D tile kernel (bf16): one kernel row per workgroup, accumulators in registers over all position tiles
-    // Layers too wide for one workgroup's accumulators (N > 64 or more than 28 reduction tiles per kernel row: the generator's Conv1d
-    // layers, 256 x 7 x 256) run on the same tile kernel as subs_n x subs_c sub-problems of 64 output x 64 input channels that share
-    // every group's position tiles; a Conv1d batch is viewed as ONE image whose rows are the utterances (KH = 1: rows are independent),
-    // so that a tile is 4 utterances x 64 frames.  The im2col-gathering kernel read the input KW times per 128-column block of the
-    // gradient: 1.44 GB per launch for 130 MB of operands, 240 us per layer at B = 256.
-    ConvGeom gt = p.g;                                     // geometry the tile kernel sees
-    int Nt = N, subs_n = 1, subs_c = 1, Bt = M / (p.g.Hout * p.g.Wout);
-    bool sliced = false;
-    if (bf16 && (!d16 || a16) && !wgrad_tile_eligible(M, N, p.g, KH, KW) && N % 64 == 0 && p.g.C % 64 == 0 && KW * p.g.C == p.g.seglen &&
-        KW * 4 <= 28 && p.g.Wout >= 32 && M % (p.g.Hout * p.g.Wout) == 0) {
-        gt.C = 64; gt.seglen = KW * 64; gt.Ktot = KH * KW * 64;
-        Nt = 64; subs_n = N / 64; subs_c = p.g.C / 64;
-        if (KH == 1 && p.g.H == 1 && p.g.Hout == 1 && p.g.OH == 1 && p.g.ih0 == 0 && p.g.oh0 == 0) { gt.H = Bt; gt.Hout = Bt; gt.OH = Bt; Bt = 1; }
-        sliced = (((long long)WT_TH * (WT_TW + KW - 1) * 64 + WT_SLACK + 256 * WT_NP_OF(4)) * 2 <= 76 * 1024);
-        if (!sliced) { gt = p.g; Nt = N; subs_n = subs_c = 1; Bt = M / (p.g.Hout * p.g.Wout); }
-    }
-    const int nkt = (gt.seglen + 15) / 16, NT = (Nt + 15) / 16;
-    const long long wt_lds = ((long long)WT_TH * (WT_TW + KW - 1) * gt.C + WT_SLACK + 256 * WT_NP_OF(NT)) * 2;
-    const int max_splits = (M + 511) / 512;
-    int G = (max_splits < 64) ? (max_splits > splits ? max_splits : splits) : 64;
-    if (G < splits) G = splits;
+    // 2-D tile kernel (bf16): one kernel row per workgroup, accumulators in registers over all position tiles; the wide layers sliced
+    const bool sliced = bf16 && (!d16 || a16) && !wgrad_tile_eligible(M, N, p.g, KH, KW) && wgrad_sliceable(M, N, p.g, KW, false);
+    const int G = wgrad_groups(M, splits);
     bool tiled = false;
     // ---- DMA double-buffer kernel: both operands bf16 in memory (D.conv2 .. conv5 in bf16 mode)
     if (a16 && d16) {
@@ -3160,73 +3200,12 @@ static int conv_wgrad_impl(const float* A, const float* dOut, float* workspace, 
         }
     }
     if (!tiled && bf16 && (sliced || wgrad_tile_eligible(M, N, p.g, KH, KW))) {
-        WgradTileArgs t;
-        t.A = A; t.dOut = dOut; t.part = workspace; t.N = Nt; t.B = Bt; t.KH = KH; t.KW = KW; t.d16 = d16;
-        t.ics = p.g.C; t.subs_n = subs_n; t.subs_c = subs_c; t.Kfull = p.g.Ktot;
-        t.nth = (gt.Hout + WT_TH - 1) / WT_TH; t.ntw = (gt.Wout + WT_TW - 1) / WT_TW; t.ntiles = t.B * t.nth * t.ntw;
-        if (G > t.ntiles) G = t.ntiles;
-        const int wg_per_group = KH * subs_n * subs_c;
-        const int ktw = (nkt + 3) / 4;
-        {   // Workgroups that do not fit the chip at once run as a second, nearly empty round: KH * 64 = 576 workgroups on 512 slots (two
-            // per CU for D.conv5) took 1.64 x as long as KH * 56 = 504 (3.20 -> 1.95 ms at B = 256).  Pick the group count (a multiple
-            // of 8, at most the partial slots of the workspace) that minimises rounds x tiles per workgroup.
-            static int ncu = 0;
-            static int occ_tab[5][3] = {{0}};
-            const int ki = ktw <= 2 ? 0 : (ktw <= 4 ? 1 : 2), ni = NT < 1 ? 1 : (NT > 4 ? 4 : NT);
-            if (!ncu) { int dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev); if (ncu <= 0) ncu = 256; }
-            if (!occ_tab[ni][ki]) {
-                int occ = 0;
-                const void* fn = nullptr;
-#define WT_FN(NT_, K_) reinterpret_cast<const void*>(conv_wgrad_tile16_kernel<NT_, K_>)
-#define WT_FNK(K_) (ni == 1 ? WT_FN(1, K_) : ni == 2 ? WT_FN(2, K_) : ni == 3 ? WT_FN(3, K_) : WT_FN(4, K_))
-                fn = ki == 0 ? WT_FNK(2) : (ki == 1 ? WT_FNK(4) : WT_FNK(7));
-#undef WT_FNK
-#undef WT_FN
-                (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 256, (size_t)wt_lds) != hipSuccess || occ < 1) occ = 1;
-                hipFuncAttributes fa;
-                if (hipFuncGetAttributes(&fa, fn) == hipSuccess && fa.numRegs > 0) {      // registers: 512 per SIMD lane, one wave of the workgroup per SIMD
-                    const int by_regs = 512 / ((fa.numRegs + 7) & ~7);
-                    if (by_regs >= 1 && by_regs < occ) occ = by_regs;
-                }
-                occ_tab[ni][ki] = occ;
-            }
-            const long long slots = (long long)ncu * occ_tab[ni][ki];
-            if (G >= 16) {
-                long long best = -1;
-                int bestG = G;
-                for (int cand = G & ~7; cand >= 8; cand -= 8) {    // (any count up to the workspace's partial slots works for this kernel)
-                    const long long rounds = ((long long)wg_per_group * cand + slots - 1) / slots, per = (t.ntiles + cand - 1) / cand;
-                    const long long cost = rounds * per;
-                    if (best < 0 || cost < best) { best = cost; bestG = cand; }
-                }
-                G = bestG;
-            }
-        }
-        t.G = G; t.g = gt;
-        t.bpart = db ? workspace + (size_t)G * N * p.g.Ktot : nullptr;
-        const dim3 grid(wg_per_group * G);
-        static unsigned long long wattr = 0;            // (per device: a process that switches devices sets the attribute on each)
-        if (nele_first_use_on_device(&wattr)) {
-#define WT_ATTR(NT_, K_) do { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_tile16_kernel<NT_, K_>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); \
-                              (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_tile16_kernel<NT_, K_, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); \
-                              (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_tile16_kernel<NT_, K_, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); } while (0)
-            WT_ATTR(1, 2); WT_ATTR(2, 2); WT_ATTR(3, 2); WT_ATTR(4, 2); WT_ATTR(1, 4); WT_ATTR(2, 4); WT_ATTR(3, 4); WT_ATTR(4, 4);
-            WT_ATTR(1, 7); WT_ATTR(2, 7); WT_ATTR(3, 7); WT_ATTR(4, 7);
-#undef WT_ATTR
-        }
-#define WT_LAUNCH(NT_, K_) do { if (a16) hipLaunchKernelGGL((conv_wgrad_tile16_kernel<NT_, K_, true, true>), grid, dim3(256), (size_t)wt_lds, s, t); \
-                                else if (d16) hipLaunchKernelGGL((conv_wgrad_tile16_kernel<NT_, K_, true>), grid, dim3(256), (size_t)wt_lds, s, t); \
-                                else hipLaunchKernelGGL((conv_wgrad_tile16_kernel<NT_, K_>), grid, dim3(256), (size_t)wt_lds, s, t); } while (0)
-#define WT_PICK(K_) switch (NT) { case 1: WT_LAUNCH(1, K_); break; case 2: WT_LAUNCH(2, K_); break; case 3: WT_LAUNCH(3, K_); break; default: WT_LAUNCH(4, K_); break; }
-        if (ktw <= 2) { WT_PICK(2) } else if (ktw <= 4) { WT_PICK(4) } else { WT_PICK(7) }
-#undef WT_PICK
-#undef WT_LAUNCH
+        const WgradTileRun r = wgrad_tile16_run(A, dOut, workspace, db, M, N, p.g, KH, KW, sliced, a16 ? WG_A16D16 : (d16 ? WG_D16 : WG_F32), G, s);
+        splits = r.G;
+        p.bpart = r.bpart;
         NELE_CHECK_LAUNCH("nele_conv_wgrad(tile)");
         tiled = true;
-        splits = G;
         p.part = workspace;
-        p.bpart = t.bpart;
     }
     if (!tiled && d16) return nele_set_error(NELE_ERR_UNSUPPORTED, "nele_conv_wgrad_bf16_d16: this layer does not run on the tile kernel");
     if (a16 && !d16) return nele_set_error(NELE_ERR_INVALID_ARG, "nele_conv_wgrad: a bf16 activation needs a bf16 output gradient");
@@ -3392,51 +3371,12 @@ extern "C" int nele_weight_prep_frag16x3(const float* Wg, int N, int Ktot, int s
     return nele_weight_prep_frag16x3_batch(ptrs, dims, 1, stream);
 }
 
-// LDS budgets of the split kernels (160 KB per CU, 158 KB usable as in the bf16 selectors).  Both stage twice the bf16 kernels' bytes, so
-// they get their own, smaller choices: 2-D tiles of 4 or 2 rows with weight chunks of at most TILE16_SBMAX_X3 steps; Conv1d strips with
-// chunks of at most C1D_SBMAX_X3 steps and one workgroup per (strip, 64-channel chunk).
-static int tile16x3_sb(const ConvGeom& g) {
-    const int sps = (g.seglen + 31) / 32;
-    int SB = 1;
-    for (int d = 1; d <= TILE16_SBMAX_X3; ++d)
-        if (sps % d == 0) SB = d;
-    return SB;
-}
-static size_t tile16x3_lds(const ConvGeom& g, int N, int KH, int KW, int TH) {
-    if (N > 64 || N % 4 || g.OC % 4 || g.C % 8 || KH * g.seglen != g.Ktot || KW * g.C != g.seglen) return 0;
-    const long long RS = (long long)(TILE16_TW + KW - 1) * g.C;
-    if (RS > 4096) return 0;
-    const int NT = (N + 15) / 16;
-    const long long bytes = 2 * ((long long)(TH + KH - 1) * RS + 64) * 2 + 2 * (((long long)tile16x3_sb(g) * NT * 1024 + 4095) & ~4095LL);
-    if (bytes > 158 * 1024) return 0;
-    return (size_t)(bytes < 4 * 16 * 68 * 4 ? 4 * 16 * 68 * 4 : bytes);
-}
-static int tile16x3_th(const ConvGeom& g, int N, int KH, int KW) {
-    if (tile16x3_lds(g, N, KH, KW, 4)) return 4;
-    if (tile16x3_lds(g, N, KH, KW, 2)) return 2;
-    return 0;
-}
-static int conv1d16x3_sb(const ConvGeom& g, int N, int KH, int KW, size_t* lds_out) {
-    if (KH != 1 || N % 4 || g.OC % 4 || g.C % 8 || KW * g.C != g.seglen || g.seglen != g.Ktot || g.seglen % 32) return 0;
-    if (N > 64 && N % 64) return 0;
-    const long long RS = (long long)(C1D_TW + KW - 1) * (g.C + (((g.C & (g.C - 1)) == 0) ? C1D_PAD(g.C) : 0));
-    const int sps = g.seglen / 32, TNsel = (N >= 64) ? 4 : (N + 15) / 16;
-    for (int d = C1D_SBMAX_X3; d >= 1; --d) {
-        if (sps % d) continue;
-        const long long bytes = 2 * (RS + 64) * 2 + 4 * (((long long)d * TNsel * 1024 + 4095) & ~4095LL);    // hi + lo strip, two (hi, lo) weight slots
-        if (bytes <= 158 * 1024) {
-            if (lds_out) *lds_out = (size_t)(bytes < 4 * 16 * 68 * 4 ? 4 * 16 * 68 * 4 : bytes);
-            return d;
-        }
-    }
-    return 0;
-}
 extern "C" int nele_conv_span_bf16x3_supported(int M, int N, const int* geom, int KH, int KW) {
     ConvGeom g;
     memcpy(&g, geom, sizeof(ConvGeom));
     if (g.Wout < 32) return 0;
-    if (KH == 1 && conv1d16x3_sb(g, N, KH, KW, nullptr)) return 1;
-    return tile16x3_th(g, N, KH, KW) ? 1 : 0;
+    if (KH == 1 && conv1d16_sb(g, N, KH, KW, nullptr, true)) return 1;
+    return tile16_th(g, N, KH, KW, true) ? 1 : 0;
 }
 
 // nele_conv_span_bf16 with split operands: Whi / Wlo from nele_weight_prep_frag16x3 (same fragment layout as Wfrag there)
@@ -3451,80 +3391,30 @@ extern "C" int nele_conv_span_bf16x3(const float* A, const void* Whi, const void
     memcpy(&t.g, geom, sizeof(ConvGeom));
     t.A = A; t.Wfrag = (const __bf16*)Whi; t.bias = bias; t.aux = aux; t.out = out; t.N = N; t.NT = (N + 15) / 16; t.epi = epi; t.slope = slope;
     t.KH = KH; t.KW = KW; t.steps_per_seg = (t.g.seglen + 31) / 32; t.dbg = nullptr;
-    const __bf16* wlo = (const __bf16*)Wlo;
     hipStream_t s = as_stream(stream);
     size_t clds = 0;
-    const int csb = KH == 1 ? conv1d16x3_sb(t.g, N, KH, KW, &clds) : 0;
+    const int csb = KH == 1 ? conv1d16_sb(t.g, N, KH, KW, &clds, true) : 0;
     if (csb) {
-        static unsigned long long cattr = 0;
-        if (nele_first_use_on_device(&cattr)) {
-#define C1DX3_ATTR(TN_) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_tile16x3_kernel<TN_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-            C1DX3_ATTR(1); C1DX3_ATTR(2); C1DX3_ATTR(3); C1DX3_ATTR(4);
-#undef C1DX3_ATTR
-        }
-        const int BH = M / t.g.Wout;
-        const int nchunksN = (N > 64) ? N / 64 : 1, TNsel = (N >= 64) ? 4 : t.NT;
-        const int nstrips = ((t.g.Wout + C1D_TW - 1) / C1D_TW) * BH;
-        t.SB = csb; t.steps_per_seg = t.g.seglen / 32; t.ntiles = nchunksN; t.ncl = 1; t.SBH = BH;
-        const dim3 grid((unsigned)(t.ntiles * 8 * ((nstrips + 7) / 8)));
-        switch (TNsel) {
-            case 1: hipLaunchKernelGGL((conv1d_tile16x3_kernel<1>), grid, dim3(256), clds, s, t, wlo); break;
-            case 2: hipLaunchKernelGGL((conv1d_tile16x3_kernel<2>), grid, dim3(256), clds, s, t, wlo); break;
-            case 3: hipLaunchKernelGGL((conv1d_tile16x3_kernel<3>), grid, dim3(256), clds, s, t, wlo); break;
-            default: hipLaunchKernelGGL((conv1d_tile16x3_kernel<4>), grid, dim3(256), clds, s, t, wlo); break;
-        }
+        conv1d16_run<true>(t, (const __bf16*)Wlo, M, csb, clds, s);
         NELE_CHECK_LAUNCH("nele_conv_span_bf16x3(conv1d)");
         return NELE_OK;
     }
-    const int th = tile16x3_th(t.g, N, KH, KW);
-    t.SB = tile16x3_sb(t.g);
-    const int B_ = M / (t.g.Hout * t.g.Wout);
-    const size_t lds = tile16x3_lds(t.g, N, KH, KW, th);
-    static unsigned long long tattr = 0;
-    if (nele_first_use_on_device(&tattr)) {
-#define T16X3_ATTR(TN_, TH_) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_tile16x3_kernel<TN_, TH_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-        T16X3_ATTR(1, 4); T16X3_ATTR(2, 4); T16X3_ATTR(3, 4); T16X3_ATTR(4, 4);
-        T16X3_ATTR(1, 2); T16X3_ATTR(2, 2); T16X3_ATTR(3, 2); T16X3_ATTR(4, 2);
-#undef T16X3_ATTR
-    }
-    t.ntiles = ((t.g.Wout + TILE16_TW - 1) / TILE16_TW) * ((t.g.Hout + th - 1) / th) * B_;
-    const dim3 grid((unsigned)((t.ntiles + 7) / 8 * 8));
-#define T16X3_LAUNCH(TN_, TH_) hipLaunchKernelGGL((conv_tile16x3_kernel<TN_, TH_>), grid, dim3(256), lds, s, t, wlo)
-#define T16X3_PICK(TH_) switch (t.NT) { case 1: T16X3_LAUNCH(1, TH_); break; case 2: T16X3_LAUNCH(2, TH_); break; case 3: T16X3_LAUNCH(3, TH_); break; default: T16X3_LAUNCH(4, TH_); break; }
-    // measurement hook: "tile16x3_N<N>_K<Ktot>" times one layer's launch (D.conv5 forward: tile16x3_N64_K3888)
-    char ptag[48] = "";
-    if (nele_prof_armed()) snprintf(ptag, sizeof(ptag), "tile16x3_N%d_K%d", N, t.g.Ktot);
-    const bool prof_t = ptag[0] && nele_prof_match(ptag);
-    if (prof_t) nele_prof_mark(s);
-    if (th == 4) { T16X3_PICK(4) } else { T16X3_PICK(2) }
-    if (prof_t) nele_prof_mark(s);
-#undef T16X3_PICK
-#undef T16X3_LAUNCH
+    tile16_run<true>(t, (const __bf16*)Wlo, M, tile16_th(t.g, N, KH, KW, true), s);
     NELE_CHECK_LAUNCH("nele_conv_span_bf16x3(tile)");
     return NELE_OK;
 }
 
 // Weight gradient with split operands.  Layers the split tile kernel declines (too wide for its LDS budget, short rows) run on the float32
 // kernels: the result is float32-grade either way, and never a single bf16 product.
-// dynamic LDS of the split weight-gradient kernel: 160 KB less its 4 KB of static bias-reduction scratch; the input rows are staged as
-// 9 pieces of 8 elements per thread (at most 4 x RS = 18432 elements)
-#define WTX3_LDS_MAX (156 * 1024)
-static long long wgrad_tile16x3_lds(int NT, int KW, int C) {
-    return 2 * ((long long)WT_TH * (WT_TW + KW - 1) * C + WT_SLACK + 256 * WT_NP_OF(NT)) * 2;
-}
-static bool wgrad_x3_sliced(int M, int N, const ConvGeom& g, int KH, int KW) {
-    return N % 64 == 0 && g.C % 64 == 0 && KW * g.C == g.seglen && KW * 4 <= 28 && g.Wout >= 32 && M % (g.Hout * g.Wout) == 0 &&
-           WT_TH * (WT_TW + KW - 1) * 64 <= 9 * 2048 && wgrad_tile16x3_lds(4, KW, 64) <= WTX3_LDS_MAX;
-}
 static bool wgrad_x3_tile(int M, int N, const ConvGeom& g, int KH, int KW) {
     return N <= 64 && g.C % 8 == 0 && KW * g.C == g.seglen && (g.seglen + 15) / 16 <= 28 && g.Wout >= 32 &&
-           (long long)WT_TH * (WT_TW + KW - 1) * g.C <= 9 * 2048 && wgrad_tile16x3_lds((N + 15) / 16, KW, g.C) <= WTX3_LDS_MAX && M % (g.Hout * g.Wout) == 0;
+           (long long)WT_TH * (WT_TW + KW - 1) * g.C <= 9 * 2048 && wgrad_tile16_lds((N + 15) / 16, KW, g.C, true) <= WTX3_LDS_MAX && M % (g.Hout * g.Wout) == 0;
 }
 extern "C" int nele_conv_wgrad_bf16x3_supported(int M, int N, const int* geom, int KH, int KW) {
     ConvGeom g;
     memcpy(&g, geom, sizeof(ConvGeom));
     if (N % 4 || g.OC % 4 || KH * KW * g.C != g.Ktot) return 0;
-    return (wgrad_x3_tile(M, N, g, KH, KW) || wgrad_x3_sliced(M, N, g, KH, KW)) ? 1 : 0;
+    return (wgrad_x3_tile(M, N, g, KH, KW) || wgrad_sliceable(M, N, g, KW, true)) ? 1 : 0;
 }
 extern "C" int nele_conv_wgrad_bf16x3(const float* A, const float* dOut, float* workspace, long long workspace_floats, int M, int N,
                                       const int* geom, int KH, int KW, int Cvalid, float* dW, float* db, int accumulate, void* stream) {
@@ -3544,55 +3434,10 @@ extern "C" int nele_conv_wgrad_bf16x3(const float* A, const float* dOut, float* 
     if (nele_prof_armed()) snprintf(ptag, sizeof(ptag), "wgrad_N%d_K%d", N, g.Ktot);
     const bool prof_w = ptag[0] && nele_prof_match(ptag);
     if (prof_w) nele_prof_mark(s);
-    ConvGeom gt = g;                                       // sub-problems of 64 x 64 channels for the wide layers, as in conv_wgrad_impl
-    int Nt = N, subs_n = 1, subs_c = 1, Bt = M / (g.Hout * g.Wout);
-    if (!wgrad_x3_tile(M, N, g, KH, KW)) {
-        gt.C = 64; gt.seglen = KW * 64; gt.Ktot = KH * KW * 64;
-        Nt = 64; subs_n = N / 64; subs_c = g.C / 64;
-        if (KH == 1 && g.H == 1 && g.Hout == 1 && g.OH == 1 && g.ih0 == 0 && g.oh0 == 0) { gt.H = Bt; gt.Hout = Bt; gt.OH = Bt; Bt = 1; }
-    }
-    const int nkt = (gt.seglen + 15) / 16, NT = (Nt + 15) / 16, ktw = (nkt + 3) / 4;
-    const size_t lds = (size_t)wgrad_tile16x3_lds(NT, KW, gt.C);
-    WgradTileArgs t;
-    t.A = A; t.dOut = dOut; t.part = workspace; t.N = Nt; t.B = Bt; t.KH = KH; t.KW = KW; t.d16 = 0;
-    t.ics = g.C; t.subs_n = subs_n; t.subs_c = subs_c; t.Kfull = g.Ktot;
-    t.nth = (gt.Hout + WT_TH - 1) / WT_TH; t.ntw = (gt.Wout + WT_TW - 1) / WT_TW; t.ntiles = t.B * t.nth * t.ntw;
-    const int max_splits = (M + 511) / 512;
-    int G = (max_splits < 64) ? (max_splits > splits ? max_splits : splits) : 64;
-    if (G < splits) G = splits;
-    if (G > t.ntiles) G = t.ntiles;
-    const int wg_per_group = KH * subs_n * subs_c;
-    {   // one workgroup per CU (LDS): the group count (a multiple of 8) that minimises rounds x tiles per workgroup
-        static int ncu = 0;
-        if (!ncu) { int dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev); if (ncu <= 0) ncu = 256; }
-        if (G >= 16) {
-            long long best = -1;
-            int bestG = G;
-            for (int cand = G & ~7; cand >= 8; cand -= 8) {
-                const long long rounds = ((long long)wg_per_group * cand + ncu - 1) / ncu, per = (t.ntiles + cand - 1) / cand;
-                if (best < 0 || rounds * per < best) { best = rounds * per; bestG = cand; }
-            }
-            G = bestG;
-        }
-    }
-    t.G = G; t.g = gt;
-    t.bpart = db ? workspace + (size_t)G * N * g.Ktot : nullptr;
-    static unsigned long long wattr = 0;
-    if (nele_first_use_on_device(&wattr)) {
-#define WTX3_ATTR(NT_, K_) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_tile16x3_kernel<NT_, K_>), hipFuncAttributeMaxDynamicSharedMemorySize, WTX3_LDS_MAX)
-        WTX3_ATTR(1, 2); WTX3_ATTR(2, 2); WTX3_ATTR(3, 2); WTX3_ATTR(4, 2); WTX3_ATTR(1, 4); WTX3_ATTR(2, 4); WTX3_ATTR(3, 4); WTX3_ATTR(4, 4);
-        WTX3_ATTR(1, 7); WTX3_ATTR(2, 7); WTX3_ATTR(3, 7); WTX3_ATTR(4, 7);
-#undef WTX3_ATTR
-    }
-    const dim3 grid(wg_per_group * G);
-#define WTX3_LAUNCH(NT_, K_) hipLaunchKernelGGL((conv_wgrad_tile16x3_kernel<NT_, K_>), grid, dim3(256), lds, s, t)
-#define WTX3_PICK(K_) switch (NT) { case 1: WTX3_LAUNCH(1, K_); break; case 2: WTX3_LAUNCH(2, K_); break; case 3: WTX3_LAUNCH(3, K_); break; default: WTX3_LAUNCH(4, K_); break; }
-    if (ktw <= 2) { WTX3_PICK(2) } else if (ktw <= 4) { WTX3_PICK(4) } else { WTX3_PICK(7) }
-#undef WTX3_PICK
-#undef WTX3_LAUNCH
+    const WgradTileRun r = wgrad_tile16_run(A, dOut, workspace, db, M, N, g, KH, KW, !wgrad_x3_tile(M, N, g, KH, KW), WG_X3, wgrad_groups(M, splits), s);
     NELE_CHECK_LAUNCH("nele_conv_wgrad_bf16x3(tile)");
     const int total = N * g.Ktot;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(min(1024, (total + 255) / 256)), dim3(256), 0, s, workspace, t.bpart, G, N, KH, KW, g.C, Cvalid, dW, db,
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(min(1024, (total + 255) / 256)), dim3(256), 0, s, workspace, r.bpart, r.G, N, KH, KW, g.C, Cvalid, dW, db,
                        accumulate);
     NELE_CHECK_LAUNCH("nele_conv_wgrad_bf16x3(reduce)");
     if (prof_w) nele_prof_mark(s);

@@ -21,7 +21,7 @@ from weights_recipe import digest, seeded_state_arrays        # noqa: E402
 
 M = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'model.npz'))
 PREC_BF16X3 = 2
-EPI_NONE = 0
+EPI_NONE, EPI_BIAS, EPI_BIAS_LRELU, EPI_MASK_LRELU_GRAD, EPI_BIAS_EXPTANH = 0, 1, 2, 3, 4
 
 
 def _lib():
@@ -48,7 +48,7 @@ def _conv_case(B, H, W, C, KH, KW, N, seed):
     return A, Wt
 
 
-def _fwd(L, A, Wt, x3):
+def _fwd(L, A, Wt, x3, epi=EPI_NONE, bias=None, aux=None, slope=0.0):
     B, H, W, C = A.shape
     N, _, KH, KW = Wt.shape
     geom, Mrows, Ho, Wo = _geom(B, H, W, C, KH, KW, N)
@@ -56,19 +56,20 @@ def _fwd(L, A, Wt, x3):
     ne = int(L.lib.nele_weight_frag16_elems(N, KW * C, KH))
     out = torch.full((B, Ho, Wo, N), float('nan'), device='cuda')
     s = L.stream()
+    bp, ap = (L.ptr(bias) if bias is not None else None), (L.ptr(aux) if aux is not None else None)
     if x3:
         if not L.lib.nele_conv_span_bf16x3_supported(Mrows, N, geom, KH, KW):
             return None
         hi = torch.empty(ne, dtype=torch.bfloat16, device='cuda')
         lo = torch.empty(ne, dtype=torch.bfloat16, device='cuda')
         L.call('nele_weight_prep_frag16x3', L.ptr(Wg), N, Wg.shape[1], KW * C, KH, L.ptr(hi), L.ptr(lo), s)
-        L.call('nele_conv_span_bf16x3', L.ptr(A), L.ptr(hi), L.ptr(lo), None, None, L.ptr(out), Mrows, N, EPI_NONE, 0.0, geom, KH, KW, A.numel(), s)
+        L.call('nele_conv_span_bf16x3', L.ptr(A), L.ptr(hi), L.ptr(lo), bp, ap, L.ptr(out), Mrows, N, epi, slope, geom, KH, KW, A.numel(), s)
     else:
         if not L.lib.nele_conv_span_bf16_supported(Mrows, N, geom, KH, KW):
             return None
         wf = torch.empty(ne, dtype=torch.bfloat16, device='cuda')
         L.call('nele_weight_prep_frag16', L.ptr(Wg), N, Wg.shape[1], KW * C, KH, L.ptr(wf), s)
-        L.call('nele_conv_span_bf16', L.ptr(A), L.ptr(wf), None, None, L.ptr(out), Mrows, N, EPI_NONE, 0.0, geom, KH, KW, A.numel(), s)
+        L.call('nele_conv_span_bf16', L.ptr(A), L.ptr(wf), bp, ap, L.ptr(out), Mrows, N, epi, slope, geom, KH, KW, A.numel(), s)
     torch.cuda.synchronize()
     return out
 
@@ -91,6 +92,53 @@ def _wgrad(L, A, dO, KH, KW, x3):
 G_SHAPES = [(128, 256, 1, 5, 1), (256, 256, 1, 7, 1), (256, 64, 1, 5, 1), (256, 128, 1, 5, 1), (64, 256, 1, 5, 1)]
 D_SHAPES = [(8, 16, 3, 3, 12), (16, 32, 5, 5, 14), (32, 48, 7, 7, 16), (48, 64, 9, 9, 18), (16, 8, 3, 3, 12), (32, 16, 5, 5, 14),
             (48, 32, 7, 7, 16)]
+
+
+# EPI_BIAS_EXPTANH against exp(3.2 * tanh(x + bias)) in float64, x the EPI_NONE output of the same call.  The figures of the commit before the
+# store epilogue became one helper were never measured, so the bound is the worst case of the float32 steps instead, each as a relative error
+# of the result (= an absolute error of the exponent): the float32 add x + bias, half an ulp through 3.2 sech^2, at most 8e-8 (|v| in [1, 2));
+# tanhf, 2 ulp of a value below 1, times 3.2: 3.8e-7; the product with 3.2f, half an ulp below 4: 1.2e-7; 3.2f against 3.2: 5e-8; expf, 1 ulp:
+# 1.2e-7.  Sum 7.5e-7.  A wrong bias element or a missing tanh is off by tens of percent.
+EXPTANH_ERR = 7.5e-7
+# (C, N, KH, KW, Hout, B) at T = 40: a strip with two 64-channel chunks and a partial 128-position strip; a 2-D tile with a partial column
+# tile and row tiles beyond Hout
+EPI_CASES = {'strip': (64, 128, 1, 5, 1, 2), 'tile': (16, 32, 5, 5, 14, 1)}
+
+
+@pytest.mark.parametrize('x3', [False, True])
+@pytest.mark.parametrize('kind', ['strip', 'tile'])
+def test_store_epilogues_equal_the_plain_output_post_processed(kind, x3):
+    """EPI_BIAS, EPI_BIAS_LRELU and EPI_MASK_LRELU_GRAD are one float32 add and one select or multiply on the EPI_NONE output: bit for bit;
+    EPI_BIAS_EXPTANH within the float32 rounding of its steps (EXPTANH_ERR)."""
+    L = _lib()
+    C, N, KH, KW, Ho, B = EPI_CASES[kind]
+    A, Wt = _conv_case(B, Ho + KH - 1, 40 + KW - 1, C, KH, KW, N, 4242)
+    g = torch.Generator(device='cuda').manual_seed(4243)
+    bias = torch.randn(N, device='cuda', generator=g)
+    plain = _fwd(L, A, Wt, x3)
+    assert plain is not None and not torch.isnan(plain).any()
+    aux = torch.randn(plain.shape, device='cuda', generator=g)
+    slope = 0.3
+    sl = torch.tensor(slope, dtype=torch.float32, device='cuda')
+    vb = plain + bias
+    assert torch.equal(_fwd(L, A, Wt, x3, EPI_BIAS, bias=bias), vb)
+    assert torch.equal(_fwd(L, A, Wt, x3, EPI_BIAS_LRELU, bias=bias, slope=slope), torch.where(vb > 0, vb, sl * vb))
+    assert torch.equal(_fwd(L, A, Wt, x3, EPI_MASK_LRELU_GRAD, aux=aux, slope=slope), torch.where(aux > 0, plain, sl * plain))
+    ref = torch.exp(3.2 * torch.tanh(plain.double() + bias.double()))
+    err = float(((_fwd(L, A, Wt, x3, EPI_BIAS_EXPTANH, bias=bias).double() - ref).abs() / ref).max())
+    print('exptanh relative error', kind, x3, err)
+    assert err <= EXPTANH_ERR, (kind, x3, err)
+
+
+def test_n_chunk_walk_equals_one_workgroup_per_chunk():
+    """bf16, C = 64 -> N = 128, k = 5, T = 32 at B = 256: 256 strips, so one workgroup per strip walks both 64-channel chunks; utterances 0
+    and 255 must come out bit for bit as at B = 2, where every chunk has a workgroup of its own"""
+    L = _lib()
+    A, Wt = _conv_case(256, 1, 32 + 4, 64, 1, 5, 128, 777)
+    big = _fwd(L, A, Wt, False)
+    small = _fwd(L, A[[0, 255]].contiguous(), Wt, False)
+    assert big is not None and small is not None and not torch.isnan(big).any()
+    assert torch.equal(big[[0, 255]], small)
 
 
 @pytest.mark.parametrize('T', [24, 40, 41, 77, 251, 501])

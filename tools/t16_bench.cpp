@@ -14,8 +14,8 @@ int main(int argc, char** argv) {
     hipMalloc(&wf, (size_t)KH * sps * NT * 64 * 8 * 2 + 65536);
     hipMemset(A, 0, na * 4); hipMemset(wf, 0, (size_t)KH * sps * NT * 64 * 8 * 2 + 65536); hipMemset(bias, 0, 256);
     Tile16Args t; t.A = A; t.Wfrag = wf; t.bias = bias; t.aux = nullptr; t.out = out; t.N = N; t.NT = NT; t.epi = EPI_BIAS_LRELU; t.slope = 0.3f;
-    t.KH = KH; t.KW = KW; t.steps_per_seg = sps; t.g = g; t.SB = tile16_sb(g); t.dbg = dbg;
-    const size_t lds = tile16_lds(g, N, KH, KW, 8);
+    t.KH = KH; t.KW = KW; t.steps_per_seg = sps; t.g = g; t.SB = tile16_sb(g, false); t.dbg = dbg;
+    const size_t lds = tile16_lds(g, N, KH, KW, 8, false);
     hipFuncSetAttribute(reinterpret_cast<const void*>(conv_tile16_kernel<4, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     t.ntiles = ((g.Wout + 63) / 64) * ((g.Hout + 7) / 8) * B;
     const dim3 grid((unsigned)((t.ntiles + 7) / 8 * 8));          // 1-D, XCD-aware ids (see conv_tile16_kernel)
