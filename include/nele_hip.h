@@ -691,6 +691,40 @@ int nele_mix_noise_var(const float* pool, const int* pool_lengths, int N, int Ln
                        const double* snr_db, const double* level, const int* lengths, int B, int Lmax, float* noise, double* gain,
                        int* status, void* stream);
 
+/* ---- SSDRC: spectral shaping and dynamic range compression of clean speech (csrc/ssdrc.hip) ----------------------------------------
+ * The pre-enhanced example of an utterance from its clean signal alone, as DESIGN.md section 11 specifies it: x [B][Lmax] float32 at
+ * 16 kHz, lengths [B] (device, NULL = Lmax each; samples at and behind a row's length count as zero); y [B][Lmax] float32 with exact zeros
+ * behind each row's length.  Stage 1 (`shape`): 512 / 256 sqrt-Hann frames t = 0 .. ceil(L / 256), zero padding; per frame the voicing
+ * probability P_v = v / max_t v, v = rms / max(zero crossings, 1); formant sharpening exp(beta P_v ln(E/T)) with ln(E/T) the cepstrum
+ * liftered to quefrencies 2 .. lifter_q; pre-emphasis 1 + preemph P_v max(f - 1000, 0) / 7000; the fixed shaping table.  Stage 2
+ * (`compress`): Hilbert-FIR envelope (|m| <= 64, Hamming), its centred 161-sample mean e, attack / release smoothing, the static curve
+ * through the knots (input dB, output dB; unity slope below the first, constant above the last) relative to e0 = e0_ratio max e.  Then
+ * y is scaled to the input row's energy (always; with both stages off y is x bit for bit).  All arithmetic is float64.  A row's output
+ * does not depend on B, on Lmax or on the other rows.
+ * ws: nele_ssdrc_ws_bytes(B, Lmax) bytes, 256-byte aligned.  nele_ssdrc_shape: stage 1 alone -> s [B][Lmax] float64 (no energy scaling);
+ * nele_ssdrc_compress: stage 2 alone on s [B][Lmax] float64 -> y [B][Lmax] float64 (may be s itself; no energy scaling) and, unless
+ * NULL, ehat [B][Lmax] float64: the smoothed envelope.  Both ignore the `shape` / `compress` flags except that nele_ssdrc_shape with
+ * shape = 0 copies x.  nele_ssdrc_params_default writes the defaults of section 11. */
+#define NELE_SSDRC_MAX_KNOTS 8
+#define NELE_SSDRC_MAX_SAMPLES (1 << 30) /* Lmax above it (18 h at 16 kHz), B above 65535 or a non-finite parameter: -1 */
+typedef struct nele_ssdrc_params {
+    int shape, compress;     /* stage switches */
+    int lifter_q;            /* Q: 2 .. 255 */
+    int n_knots;             /* 2 .. NELE_SSDRC_MAX_KNOTS */
+    double beta;             /* formant sharpening */
+    double preemph;          /* g of the adaptive pre-emphasis */
+    double attack, release;  /* a_a, a_r in [0, 1) */
+    double e0_ratio;         /* e0 = e0_ratio max e */
+    double knot_in_db[NELE_SSDRC_MAX_KNOTS], knot_out_db[NELE_SSDRC_MAX_KNOTS];
+} nele_ssdrc_params;
+long long nele_ssdrc_ws_bytes(int B, int Lmax);
+int nele_ssdrc_params_default(nele_ssdrc_params* params);
+int nele_ssdrc(const float* x, const int* lengths, int B, int Lmax, const nele_ssdrc_params* params, float* y, void* ws, void* stream);
+int nele_ssdrc_shape(const float* x, const int* lengths, int B, int Lmax, const nele_ssdrc_params* params, double* s, void* ws,
+                     void* stream);
+int nele_ssdrc_compress(const double* s, const int* lengths, int B, int Lmax, const nele_ssdrc_params* params, double* y, double* ehat,
+                        void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

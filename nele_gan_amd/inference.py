@@ -298,6 +298,36 @@ def score_rooms(clean_path, noise_path, enhanced_names, bank, batch=32, metrics=
     return res
 
 
+BASELINES = ('clean', 'ssdrc')
+
+
+def baseline_files(tag, clean_files, work_dir, batch=32):
+    """The files a baseline is scored from, named like the clean files: 'clean' - the unprocessed speech itself; 'ssdrc' - SSDRC of every
+    clean file (ssdrc.py), written as PCM_16 under ``work_dir/baseline_ssdrc/MultiEnh/`` like every enhanced file that is scored."""
+    import os
+    if tag == 'clean':
+        return list(clean_files)
+    if tag != 'ssdrc':
+        raise ValueError("baseline must be one of %s" % (BASELINES,))
+    from . import ssdrc as _ssdrc
+    root = os.path.join(work_dir, 'baseline_ssdrc')
+    _ssdrc.ssdrc_corpus(clean_files, root, batch=batch)
+    return [os.path.join(root, 'MultiEnh', f.split('/')[-1]) for f in clean_files]
+
+
+def score_baseline(tag, clean_path, noise_path, clean_files, work_dir, groups=('Cafeteria', 'AirportAnnouncement'), bank=None, batch=32, quality=None,
+                   out=None):
+    """eval_metrics.py:107-108: a baseline (``tag``: 'clean' or 'ssdrc') through the very path the generator's files take - score_enhanced
+    per noise group and, with ``bank``, score_rooms per RIR.  -> (score_enhanced's dict, score_rooms' dict or None)."""
+    import sys
+    out = sys.stdout if out is None else out
+    names = baseline_files(tag, clean_files, work_dir, batch=batch)
+    out.write('baseline %s\n' % tag)
+    res = score_enhanced(clean_path, noise_path, names, groups=groups, quality=quality, out=out)
+    rooms = score_rooms(clean_path, noise_path, names, bank, batch=batch, out=out) if bank is not None else None
+    return res, rooms
+
+
 def main(argv=None):
     """``python -m nele_gan_amd.inference --chkpt ./trained_model/chkpt_GD.pt --clean <dir> --noise <dir> --output <dir>`` = the
     reference's usage step 4 (`python inference.py`, README; inference.py:28-146): every wav under --clean is enhanced against the noise file
@@ -316,9 +346,13 @@ def main(argv=None):
     ap.add_argument('--groups', default='Cafeteria,AirportAnnouncement', help='noise types (substrings of the file names) reported separately; empty = all files together')
     ap.add_argument('--rir', default=None, help="with --score: folder of 16 kHz room impulse responses; the files are also scored in the room their name gives "
                                                 "('<utt>#<rir>#...wav'), reported per RIR")
+    ap.add_argument('--baseline', action='append', choices=BASELINES, default=None,
+                    help="with --score: also score a baseline beside the generator - 'ssdrc' (SSDRC of the clean files) or 'clean' (the unprocessed speech); may repeat")
     from . import quality as _q
     _q.add_cli_arguments(ap)
     a = ap.parse_args(argv)
+    if a.baseline and not a.score:
+        ap.error('--baseline needs --score')
     _q.backends_from_cli(a)
     e = Enhancer(a.chkpt, norm=a.norm)
     e.G.precision = a.precision
@@ -327,10 +361,15 @@ def main(argv=None):
     out = enhance_files(e, files, noise, a.output, batch=a.batch)
     print('%d files -> %s' % (len(out), a.output))
     if a.score:
-        score_enhanced(a.clean.rstrip('/') + '/', noise, out, groups=tuple(g for g in a.groups.split(',') if g))
+        groups = tuple(g for g in a.groups.split(',') if g)
+        bank = None
+        score_enhanced(a.clean.rstrip('/') + '/', noise, out, groups=groups)
         if a.rir:
             from . import room
-            score_rooms(a.clean.rstrip('/') + '/', noise, out, room.RirBank(a.rir), batch=a.batch)
+            bank = room.RirBank(a.rir)
+            score_rooms(a.clean.rstrip('/') + '/', noise, out, bank, batch=a.batch)
+        for tag in a.baseline or ():
+            score_baseline(tag, a.clean.rstrip('/') + '/', noise, files, a.output, groups=groups, bank=bank, batch=a.batch)
     return 0
 
 

@@ -143,6 +143,10 @@ class _MetricForkCtx:
 
 
 class GanTrainer:
+    # fit(multienh='ssdrc') sets it on the instance: a batch without 'drc' then gets ssdrc.ssdrc(clean) as its pre-enhanced example.  A class
+    # attribute, so that a trainer assembled without the constructor (the epoch tests' doubles) has the default too.
+    multienh = None
+
     def __init__(self, target_metric=TargetMetric, device='cuda', lr_g=5e-4, lr_d=2.5e-4, use_quality=False, pcm16=True, seed=666,
                  haspi_dither=None, dither_seed=0, quality_scorer=None, norm='utterance', room=None):
         """room: a ``room.Room`` (or a ``room.RirBank``): the listener's room.  The metric targets of every batch that brings ``rir_ids``
@@ -1342,11 +1346,12 @@ class GanTrainer:
                 out['sample_files'] += self.write_samples(enh, b['names'], sample_dir + '/For_discriminator_training', gan_epoch,
                                                           lengths=b.get('lengths_host', lens), wait=False)
             dl = b.get('drc_lengths', lens)
+            lazy = self.multienh == 'ssdrc' and b.get('drc') is None   # the pre-enhanced example is made here, when it is needed
             # The pre-enhanced ('DRC') example of an utterance (:318-340; audio_util.py:267-321) never changes: its files are fixed, so its D
             # input and its true targets are the same in every epoch the utterance is drawn.  With the clean-signal cache on they are kept
             # per utterance key after the first time (the reference recomputes read_batch_*_DRC every epoch); a batch whose utterances are
             # all known skips the DRC file's STFT and its three metric calls altogether.
-            dkeys = ckw(b).get('keys') if b.get('drc') is not None else None
+            dkeys = ckw(b).get('keys') if (b.get('drc') is not None or lazy) else None
             if dkeys is not None and rkw(b):                            # a pre-enhanced example's targets are those of (utterance, RIR)
                 dkeys = self._room_keys(dkeys, rkw(b)['rir_ids'])
             dcache = getattr(self, '_drc_cache', None)
@@ -1359,6 +1364,11 @@ class GanTrainer:
                 if len(miss) == len(dkeys):
                     drc_items, miss = None, None                         # nothing known: the ordinary path for the whole batch
             pend_sub = din_sub = None
+            if lazy and (drc_items is None or miss):
+                # SSDRC of the clean rows as a PCM_16 file of it reads back (ssdrc.py): bit-identical to the folder route; utterances whose
+                # pre-enhanced D items are all cached need none
+                from . import ssdrc as _ssdrc
+                b = dict(b, drc=_ssdrc.ssdrc(b['clean'], lens, pcm16=True), drc_lengths=lens, drc_lengths_host=b.get('lengths_host'))
             if b.get('drc') is not None and drc_items is None:
                 # generated + pre-enhanced example of the same utterances: one pass over the clean signal for both when they are compared over
                 # the same samples (audio_util.py:134-137)
@@ -1428,7 +1438,7 @@ class GanTrainer:
     # ---------------------------------------------------------------- the script's outer loop (train_nele.py:28-120, 272-277, 426-428)
     def fit(self, train_clean_files, train_noise_path, valid_clean_files=(), valid_noise_path=None, train_enh_path=None, epochs=GAN_epoch,
             sampling=num_of_sampling, valid_samples=num_of_valid_sample, batch=32, output_path='./output', pt_dir='./chkpt', log_path='./log.txt',
-            workers=8, first_epoch=1, clean_cache=False, on_epoch=None, mixer=None, rir_bank=None):
+            workers=8, first_epoch=1, clean_cache=False, on_epoch=None, mixer=None, rir_bank=None, multienh=None):
         """``for gan_epoch in np.arange(1, GAN_epoch+1)`` of the reference script over folders of wav files, in its order:
         every epoch the training list is shuffled and its first ``sampling`` files are drawn (train_nele.py:118-119), `run_epoch` runs on them
         (G-steps from epoch 2, validation on the first ``valid_samples`` validation files with the learning-curve line appended to
@@ -1442,8 +1452,16 @@ class GanTrainer:
         it is mixed once with epoch 0, so that the learning-curve line compares like with like across epochs.
         ``rir_bank`` (room.RirBank): the training and the validation batches carry each file's RIR (its name's '#' field, RirBank.ids) and
         the targets are taken in that room (a trainer built without a room gets Room(rir_bank)).
+        ``multienh='ssdrc'`` (``train_enh_path`` is then None): the pre-enhanced example of every training utterance is the SSDRC of its
+        clean signal, computed on the GPU (ssdrc.py) instead of read from a folder - bit-identical to reading the files
+        ``python -m nele_gan_amd.ssdrc`` writes; with ``mixer`` a run needs clean speech and a noise pool alone.
         The shuffles use Python's global generator, seeded by the constructor like train_nele.py:28."""
         from . import dataio
+        if multienh not in (None, 'ssdrc'):
+            raise ValueError("fit: multienh must be None or 'ssdrc'")
+        if multienh is not None and train_enh_path is not None:
+            raise ValueError("fit: multienh='ssdrc' makes the pre-enhanced examples itself; pass no train_enh_path")
+        self.multienh = multienh
         if rir_bank is not None:
             if self.room is None:
                 from . import room as _room
@@ -1645,6 +1663,8 @@ def main(argv=None):
     ap.add_argument('--mix-seed', type=int, default=0)
     ap.add_argument('--rir', default=None, help="folder of 16 kHz room impulse responses: targets are taken in the room a file's name gives ('<utt>#<rir>#...wav'; "
                                                 "no such RIR: anechoic)")
+    ap.add_argument('--multienh', choices=('folder', 'ssdrc'), default='folder', help="pre-enhanced examples: the files under Train/MultiEnh (when the folder exists), "
+                                                                                       "or 'ssdrc': SSDRC of the clean files computed on the GPU (Train/MultiEnh is not read)")
     from . import quality as _q
     _q.add_cli_arguments(ap)
     a = ap.parse_args(argv)
@@ -1676,8 +1696,10 @@ def main(argv=None):
     if a.valid_filter:
         valid = [x for x in valid if a.valid_filter in x]
     enh = root + '/Train/MultiEnh/'
+    enh_path = enh if (a.multienh == 'folder' and os.path.isdir(enh)) else None
     if ndist.rank() == 0:
-        print('%d training files, %d validation files, %s' % (len(train), len(valid), 'pre-enhanced examples: ' + enh if os.path.isdir(enh) else 'no pre-enhanced examples'))
+        print('%d training files, %d validation files, %s' % (len(train), len(valid), 'pre-enhanced examples: SSDRC of the clean files' if a.multienh == 'ssdrc' else
+                                                              'pre-enhanced examples: ' + enh if enh_path else 'no pre-enhanced examples'))
 
     def report(res):
         if ndist.rank() == 0:
@@ -1696,10 +1718,10 @@ def main(argv=None):
     if mixer is not None and not os.path.isdir(valid_noise):
         valid_noise = None                                               # mixed once (epoch 0)
     try:
-        tr.fit(train, None if mixer is not None else root + '/Train/Noise/', valid, valid_noise, train_enh_path=enh if os.path.isdir(enh) else None,
+        tr.fit(train, None if mixer is not None else root + '/Train/Noise/', valid, valid_noise, train_enh_path=enh_path,
                epochs=a.epochs, sampling=a.sampling, valid_samples=a.valid_samples, batch=a.batch, output_path=a.output, pt_dir=a.chkpt, log_path=a.log,
                first_epoch=a.first_epoch, clean_cache=not a.no_cache, on_epoch=report, mixer=mixer,
-               rir_bank=bank)
+               rir_bank=bank, multienh='ssdrc' if a.multienh == 'ssdrc' else None)
     finally:
         if world > 1:
             import torch.distributed as tdist
