@@ -940,7 +940,7 @@ __global__ __launch_bounds__(256) void siib_proj_kernel(SiibWs ws) {
 // written.  vx_k = (ncols - 1) lambda_k comes from the eigenvalue.  Same mathematics, different summation order: scores agree with
 // the projection path to 1e-9 relative (tests/test_metrics_gpu.py), both are kept (NELE_SIIB_LAG=0: projections).
 #define SL_ND 29                   // lags -14 .. 14
-#define SL_CH 58                   // frames per LDS chunk (a multiple of SL_ND: the rotating register window keeps its phase)
+#define SL_CH 58                   // granule of the segment lengths (the LDS chunk of the vector-FMA lag kernel: the boundaries stay where they were)
 // window means of the stacked rows: mu[k][j] = mean_t v_j[t + k], t < ncols.  grid (B, signals), block 256
 __global__ __launch_bounds__(256) void siib_mu_kernel(SiibWs ws, int sig0) {
     __shared__ double red[8];
@@ -975,101 +975,111 @@ __global__ __launch_bounds__(256) void siib_mu_kernel(SiibWs ws, int sig0) {
 // batch size) changes who computes a segment, not the association - an utterance's covariance, and so its SIIB score, does not depend on the
 // batch it is scored in.  (Until round 5 the segment boundaries followed ws.nseg: 1e-6 relative between batch-size classes.)
 #define SL_NSEG 4
-// L_ab partials.  grid (4, nseg, B), block 256: thread p = 256 blockIdx.x + tid < 784 owns the band pair (j1, j2) = (p / 28, p % 28)
-// and ND consecutive lags D0 .. D0 + ND - 1: b_j2[s + D0 .. s + D0 + ND - 1] lives in a ROTATING register window (slot = frame index
-// mod ND; the step loop is unrolled ND times so that every slot index is a compile-time constant), so a frame costs ND multiply-adds,
-// one new window element and one a value from LDS ([frame][band] tiles: a wave's read is one 224-byte run).  Frames outside [0, na)
-// are staged as zeros: the full-lag sums need no bounds in the loop.  The symmetric matrices (Sxx, Syy) only need the lags 0 .. 14
-// (the other half is the mirror image); the cross term needs all 29.
+// L_ab partials as a float64 MFMA product: M = the 28 bands of a (two 16-row tiles, rows 28 .. 31 are never stored), N = (D, j2) = ND x 28
+// columns in NT = 51 (ND = 29) or 27 (ND = 15) tiles of 16, K = frames.  LDS holds [frame][band] chunks of a and of b (ND - 1 frames more),
+// row means removed, zeros outside the segment (a) and outside [0, na) (b): with the column index col = (D - D0) * 28 + j2 the B operand
+// b_j2[s + k + D] of frame s + k is the double at (s + k) * 28 + col of the b chunk - ONE ds_read_b64 per lane and MFMA, no window to
+// rotate - and the two A fragments of a k-step stay in registers for every column tile of the wave.  grid (NX, nseg, B), block 256: the
+// 4 NX waves share the column tiles (6 or 7 each, 2 x 7 x 4 accumulators).  The vector-FMA kernel this replaces (one band pair and ND
+// lags per thread on a rotating register window) kept 784 of 1 024 lanes busy and held 23 TFLOP/s.
+// Chunks are double-buffered: the raw values of chunk c + 1 are requested before the MFMAs of chunk c and stored (minus the row means)
+// into the other buffer after them, one barrier per chunk.
+#define SLM_CH 32                  // frames per LDS chunk (8 k-steps)
+#define SLM_TPW 7                  // column tiles per wave, at most
+template <int ND> struct SiibLagGrid {
+    static constexpr int NT = (SB_J * ND + 15) / 16;                     // column tiles
+    static constexpr int NX = (NT + 4 * SLM_TPW - 1) / (4 * SLM_TPW);    // workgroups that share them
+};
 template <int SIGA, int SIGB, int D0, int ND>
-__global__ __launch_bounds__(256, (ND > 15 ? 2 : 4)) void siib_lag_kernel(SiibWs ws, int pair) {
-    constexpr int CH = (SL_CH / ND) * ND;                    // frames per LDS chunk: whole window periods
-    __shared__ double sa[CH][SB_J], sb[CH + ND - 1][SB_J];
-    const int b = blockIdx.z, tid = threadIdx.x, p = blockIdx.x * 256 + tid;
+__global__ __launch_bounds__(256, 2) void siib_lag_kernel(SiibWs ws, int pair) {
+    constexpr int CHP = (SL_CH / ND) * ND;                   // segment lengths are whole multiples of this (the chunk of the kernel replaced)
+    constexpr int NT = SiibLagGrid<ND>::NT, NS = 4 * SiibLagGrid<ND>::NX;
+    constexpr int FB = SLM_CH + ND - 1;                      // frames of b a chunk needs
+    constexpr int NA_E = SLM_CH * SB_J, NB_E = FB * SB_J;
+    // + 4 / + one zero row: what rows 28 .. 31 of the second A tile and the columns >= 28 ND of the last B tile read (never stored)
+    static_assert((SLM_CH - 1) * SB_J + NT * 16 <= (FB + 1) * SB_J, "padding columns of the last tile leave the b chunk");
+    static_assert(NT >= SLM_TPW && (NT + NS - 1) / NS <= SLM_TPW, "a wave owns more column tiles than it multiplies");
+    __shared__ double sa[2][NA_E + 4], sb[2][NB_E + SB_J], rmean[2][SB_J];
+    const int b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+    // a wave owns the tiles [own0, own1) (6 or 7) and always multiplies SLM_TPW tiles from t0 on: the loop has no guards, a wave
+    // with 6 repeats a neighbour's tile and does not store it
+    const int slot = blockIdx.x * 4 + (tid >> 6), own0 = slot * NT / NS, own1 = (slot + 1) * NT / NS, t0 = min(own0, NT - SLM_TPW);
     const int na = ws.info[4 * b + 2];
-    const int j1 = min(p, SB_J * SB_J - 1) / SB_J, j2 = min(p, SB_J * SB_J - 1) % SB_J;
-    const int per = ((na + SL_NSEG - 1) / SL_NSEG + CH - 1) / CH * CH;                   // frames per segment: whole chunks
+    const int per = ((na + SL_NSEG - 1) / SL_NSEG + CHP - 1) / CHP * CHP;                // frames per segment
     const int spg = SL_NSEG / ws.nseg;                                                   // segments this workgroup walks, one after the other
     const double* A = ws.XL + ((size_t)b * 2 + SIGA) * SB_J * ws.NA;
     const double* Bm = ws.XL + ((size_t)b * 2 + SIGB) * SB_J * ws.NA;
     const double* ra = ws.rowstat + ((size_t)b * 2 + SIGA) * SB_J * 2;
     const double* rb = ws.rowstat + ((size_t)b * 2 + SIGB) * SB_J * 2;
-    double acc[ND], w[ND];
-    // Staging, software-pipelined (third session of round 3): a chunk's multiply-adds take 3 us, its staging loop - two dependent
-    // global loads per element, 16 rounds - took 10 (PMC: the waves of this kernel waited 55 % of their time at two workgroups per
-    // CU).  The raw values of chunk c + 1 are requested into registers before the multiply-adds of chunk c and stored (minus the row
-    // means, which sit in LDS) after them: one barrier pair per chunk as before, the load latency under the arithmetic.
-    __shared__ double rmean[2][SB_J];
     if (tid < 2 * SB_J) rmean[tid / SB_J][tid % SB_J] = (tid < SB_J ? ra : rb)[2 * (tid % SB_J) + 1];
-    constexpr int NEA = (CH * SB_J + 255) / 256, NEB = ((CH + ND - 1) * SB_J + 255) / 256;
+    if (tid < 2 * 4) sa[tid >> 2][NA_E + (tid & 3)] = 0.0;
+    if (tid >= 64 && tid < 64 + 2 * SB_J) sb[(tid - 64) / SB_J][NB_E + (tid - 64) % SB_J] = 0.0;
+    __syncthreads();
+    constexpr int NEA = (NA_E + 255) / 256, NEB = (NB_E + 255) / 256;
     double pa[NEA], pb[NEB];
-    auto fetch = [&](int c0) {                               // thread -> (frame, band), coalesced along frames per band row
+    auto fetch = [&](int c0, int s1) {                       // thread -> (frame, band), coalesced along frames per band row
 #pragma unroll
         for (int i = 0; i < NEA; ++i) {
-            const int e = tid + 256 * i, j = e / CH, r = e - j * CH, sidx = c0 + r;
-            pa[i] = (e < CH * SB_J && sidx < na) ? A[(size_t)j * ws.NA + sidx] : 0.0;
+            const int e = tid + 256 * i, j = e / SLM_CH, r = e - j * SLM_CH, sidx = c0 + r;
+            pa[i] = (e < NA_E && sidx < s1) ? A[(size_t)j * ws.NA + sidx] : 0.0;
         }
 #pragma unroll
         for (int i = 0; i < NEB; ++i) {
-            const int e = tid + 256 * i, j = e / (CH + ND - 1), r = e - j * (CH + ND - 1), sidx = c0 + D0 + r;
-            pb[i] = (e < (CH + ND - 1) * SB_J && sidx >= 0 && sidx < na) ? Bm[(size_t)j * ws.NA + sidx] : 0.0;
+            const int e = tid + 256 * i, j = e / FB, r = e - j * FB, sidx = c0 + D0 + r;
+            pb[i] = (e < NB_E && sidx >= 0 && sidx < na) ? Bm[(size_t)j * ws.NA + sidx] : 0.0;
         }
     };
-    auto commit = [&](int c0) {                              // a[c0 .. c0 + CH) and b[c0 + D0 .. c0 + CH + D0 + ND - 1), zeros outside [0, na)
+    auto commit = [&](int buf, int c0, int s1) {             // a[c0 .. c0 + CH) of the segment and b[c0 + D0 .. c0 + D0 + FB), zeros outside
 #pragma unroll
         for (int i = 0; i < NEA; ++i) {
-            const int e = tid + 256 * i, j = e / CH, r = e - j * CH, sidx = c0 + r;
-            if (e < CH * SB_J) sa[r][j] = (sidx < na) ? pa[i] - rmean[0][j] : 0.0;
+            const int e = tid + 256 * i, j = e / SLM_CH, r = e - j * SLM_CH, sidx = c0 + r;
+            if (e < NA_E) sa[buf][r * SB_J + j] = (sidx < s1) ? pa[i] - rmean[0][j] : 0.0;
         }
 #pragma unroll
         for (int i = 0; i < NEB; ++i) {
-            const int e = tid + 256 * i, j = e / (CH + ND - 1), r = e - j * (CH + ND - 1), sidx = c0 + D0 + r;
-            if (e < (CH + ND - 1) * SB_J) sb[r][j] = (sidx >= 0 && sidx < na) ? pb[i] - rmean[1][j] : 0.0;
+            const int e = tid + 256 * i, j = e / FB, r = e - j * FB, sidx = c0 + D0 + r;
+            if (e < NB_E) sb[buf][r * SB_J + j] = (sidx >= 0 && sidx < na) ? pb[i] - rmean[1][j] : 0.0;
         }
     };
-    // (only the 29-lag instantiation is pipelined: the 15-lag ones run four workgroups per CU at 98 registers and hide the staging behind
-    //  each other - with the prefetch registers they drop to three and take 540 instead of 455 us)
-    constexpr bool PIPE = ND > 15;
     for (int seg = blockIdx.y * spg; seg < (int)(blockIdx.y + 1) * spg; ++seg) {
-    const int s0 = seg * per, s1 = min(na, s0 + per);
+        const int s0 = seg * per, s1 = min(na, s0 + per);
+        f64x4 acc[SLM_TPW][2];
 #pragma unroll
-    for (int d = 0; d < ND; ++d) { acc[d] = 0.0; w[d] = 0.0; }
-    if (PIPE && s0 < s1) fetch(s0);
-    for (int c0 = s0; c0 < s1; c0 += CH) {
-        __syncthreads();                                    // the previous chunk's reads of sa / sb are done (and rmean is visible)
-        if constexpr (PIPE) commit(c0);
-        else {                                              // element by element: a[c0 .. c0 + CH) and b[c0 + D0 .. c0 + CH + D0 + ND - 1)
-            for (int e = tid; e < CH * SB_J; e += 256) {
-                const int j = e / CH, r = e - j * CH, sidx = c0 + r;
-                sa[r][j] = (sidx < na) ? A[(size_t)j * ws.NA + sidx] - rmean[0][j] : 0.0;
-            }
-            for (int e = tid; e < (CH + ND - 1) * SB_J; e += 256) {
-                const int j = e / (CH + ND - 1), r = e - j * (CH + ND - 1), sidx = c0 + D0 + r;
-                sb[r][j] = (sidx >= 0 && sidx < na) ? Bm[(size_t)j * ws.NA + sidx] - rmean[1][j] : 0.0;
-            }
-        }
+        for (int i = 0; i < SLM_TPW; ++i) { acc[i][0] = (f64x4){0.0, 0.0, 0.0, 0.0}; acc[i][1] = (f64x4){0.0, 0.0, 0.0, 0.0}; }
+        if (s0 < s1) { fetch(s0, s1); commit(0, s0, s1); }
         __syncthreads();
-        if (PIPE && c0 + CH < s1) fetch(c0 + CH);
-        if (c0 == s0) {                                     // window = b[s0 + D0 .. s0 + D0 + ND - 2] in slots 0 .. ND - 2
+        for (int c0 = s0, buf = 0; c0 < s1; c0 += SLM_CH, buf ^= 1) {
+            const bool more = c0 + SLM_CH < s1;
+            if (more) fetch(c0 + SLM_CH, s1);
+            const double* fa = &sa[buf][lk * SB_J + li];
+            const double* fb = &sb[buf][lk * SB_J + t0 * 16 + li];
+#pragma unroll 4
+            for (int kk = 0; kk < SLM_CH / 4; ++kk) {        // frames c0 + 4 kk + lk: k ascends, a segment is summed in frame order
+                const double a0 = fa[4 * kk * SB_J], a1 = fa[4 * kk * SB_J + 16];
 #pragma unroll
-            for (int q = 0; q < ND - 1; ++q) w[q] = sb[q][j2];
+                for (int i = 0; i < SLM_TPW; ++i) {
+                    const double bv = fb[4 * kk * SB_J + 16 * i];
+                    acc[i][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, bv, acc[i][0], 0, 0, 0);
+                    acc[i][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, bv, acc[i][1], 0, 0, 0);
+                }
+            }
+            if (more) commit(buf ^ 1, c0 + SLM_CH, s1);
+            __syncthreads();                                 // the next chunk is whole, and this one's reads are done
         }
-#pragma unroll 1
-        for (int r0 = 0; r0 < CH; r0 += ND) {
+        double* out = ws.lagp + ((((size_t)b * 3 + pair) * SL_NSEG + seg) * SL_ND + (D0 + 14)) * (SB_J * SB_J);   // slot D + 14 of the 29 lag slots
 #pragma unroll
-            for (int u = 0; u < ND; ++u) {
-                const double a = sa[r0 + u][j1];
-                w[(u + ND - 1) % ND] = sb[r0 + u + ND - 1][j2];
+        for (int i = 0; i < SLM_TPW; ++i) {
+            const int col = (t0 + i) * 16 + li, d = col / SB_J, j2 = col - d * SB_J;
+            if (t0 + i >= own0 && t0 + i < own1 && d < ND) {
 #pragma unroll
-                for (int d = 0; d < ND; ++d) acc[d] = fma(a, w[(u + d) % ND], acc[d]);
+                for (int h = 0; h < 2; ++h)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int j1 = 16 * h + lk + 4 * q;
+                        if (j1 < SB_J) out[(size_t)d * (SB_J * SB_J) + j1 * SB_J + j2] = acc[i][h][q];
+                    }
             }
         }
-    }
-    if (p < SB_J * SB_J) {                                   // slot D + 14 of the 29 lag slots
-        double* out = ws.lagp + ((((size_t)b * 3 + pair) * SL_NSEG + seg) * SL_ND + (D0 + 14)) * (SB_J * SB_J) + p;
-#pragma unroll
-        for (int d = 0; d < ND; ++d) out[(size_t)d * (SB_J * SB_J)] = acc[d];
-    }
     }
 }
 
@@ -1440,14 +1450,14 @@ extern "C" int nele_metric_siib_var(const float* x, const float* y, const int* l
         NELE_AB_ONLY(NELE_ONCE_PER_DEVICE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(siib_stack_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));)
         if (siib_lag_path()) {
             hipLaunchKernelGGL(siib_mu_kernel, dim3(B, nsig), dim3(256), 0, s, ws, sig0);
-            const dim3 lg(4, ws.nseg, B);
+            const dim3 lg(SiibLagGrid<15>::NX, ws.nseg, B), lgx(SiibLagGrid<29>::NX, ws.nseg, B);
             if (sx) {
                 hipLaunchKernelGGL((siib_lag_kernel<0, 0, 0, 15>), lg, dim3(256), 0, s, ws, 0);
                 hipLaunchKernelGGL(siib_assemble_kernel<0>, dim3(15, B), dim3(256), 0, s, ws);
             }
             if (sy) {
                 hipLaunchKernelGGL((siib_lag_kernel<1, 1, 0, 15>), lg, dim3(256), 0, s, ws, 1);
-                hipLaunchKernelGGL((siib_lag_kernel<0, 1, -14, 29>), lg, dim3(256), 0, s, ws, 2);
+                hipLaunchKernelGGL((siib_lag_kernel<0, 1, -14, 29>), lgx, dim3(256), 0, s, ws, 2);
                 hipLaunchKernelGGL(siib_assemble_kernel<1>, dim3(15, B), dim3(256), 0, s, ws);
             }
         } else {
