@@ -11,7 +11,8 @@ batch 1 with wav files on disk as the hand-off between G, the metrics and D), th
 normalisation stays per utterance, and gradients are averaged across ranks with one flat RCCL
 all-reduce per model per optimiser step when torch.distributed is initialised.
 """
-import ctypes
+import collections
+import dataclasses
 import os
 import random
 
@@ -142,10 +143,131 @@ class _MetricForkCtx:
         return False
 
 
+class _FeatureCache:
+    """run_epoch with the clean-signal cache on: a batch's features (STFT / band energies of the clean file, IMCRA noise track of its noise
+    file: both files are fixed per utterance, train_nele.py:119, dataloader.py:30-42) are kept too, keyed by the batch's composition.
+    Least recently used first out, at most an eighth of the clean-signal cache's budget: a loop that re-draws its batches every epoch (fit:
+    the reference shuffles its file list, train_nele.py:118) never sees a batch twice and must not crowd the per-utterance states out."""
+
+    def __init__(self, clean_cache):
+        self.clean_cache = clean_cache
+        self.entries = collections.OrderedDict()    # key -> (features, bytes)
+        self.bytes = 0
+        self.seen = collections.OrderedDict()       # keys seen once (no tensors)
+
+    def __len__(self):
+        return len(self.entries)
+
+    def get(self, key):
+        hit = self.entries.get(key)
+        if hit is None:
+            return None
+        self.entries.move_to_end(key)
+        return hit[0]
+
+    def put(self, key, feats):
+        nb = sum(t.numel() * t.element_size() for t in feats.values() if torch.is_tensor(t))
+        cap = self.clean_cache.budget // 8
+        first = key not in self.seen                # admitted on its SECOND sighting: a composition that never comes back (re-drawn
+        self.seen[key] = True                       # batches) is not kept at all
+        self.seen.move_to_end(key)
+        while len(self.seen) > 4096:
+            self.seen.popitem(last=False)
+        if nb <= cap and not first:
+            while self.entries and self.bytes + nb > cap:
+                _, old = self.entries.popitem(last=False)
+                self.bytes -= old[1]
+            self.entries[key] = (feats, nb)
+            self.bytes += nb
+
+
+def _own_storage(item):
+    return tuple(None if t is None else t.clone() for t in item)
+
+
+class _PreEnhancedItems(dict):
+    """run_epoch with the clean-signal cache on: utterance key -> D item (input, targets, quality targets | None) of the utterance's
+    pre-enhanced ('DRC') example (:318-340; audio_util.py:267-321).  Its files are fixed, so its D input and its true targets are the same
+    in every epoch the utterance is drawn: they are kept after the first time (the reference recomputes read_batch_*_DRC every epoch), in
+    device memory charged to the clean-signal cache's budget."""
+
+    def __init__(self, clean_cache):
+        super().__init__()
+        self.clean_cache = clean_cache
+
+    def lookup(self, keys):
+        """-> (items by row, None where unknown; the unknown rows), or (None, None) when nothing is known: the ordinary path for the
+        whole batch."""
+        items = [self.get(k) for k in keys]
+        miss = [r for r, it in enumerate(items) if it is None]
+        return (None, None) if len(miss) == len(keys) else (items, miss)
+
+    def store(self, key, item):
+        """Keep a copy of ``item`` (own storage: not a view of its batch) if the key is new and the budget allows -> the copy, or None."""
+        nb = item[0].numel() * 4 + 64
+        if key in self or self.clean_cache.used + nb > self.clean_cache.budget:
+            return None
+        self[key] = item = _own_storage(item)
+        self.clean_cache.used += nb
+        return item
+
+
+@dataclasses.dataclass(eq=False)
+class _PendingBatch:
+    """A training batch behind its generator pass (run_epoch, :279-340): D inputs made, metric targets enqueued on the metric streams,
+    quality targets being scored on the host - nothing waited for until resolve()."""
+    targets: object             # _PendingTargets of the generated example; of (generated, pre-enhanced) when ``din_drc`` is there
+    din: object
+    qua: object                 # quality targets [B, 2], a Future of them (_quality_async) or None; ``drc_qua`` likewise
+    frames: object
+    frames_host: object
+    din_drc: object = None      # the pre-enhanced examples of the whole batch (none of them was known)
+    drc_qua: object = None
+    drc_keys: object = None     # the rows' utterance keys when newly scored pre-enhanced items are to be kept
+    drc_items: object = None    # the known pre-enhanced items by row; None at the rows ``miss``, scored as a batch of their own:
+    miss: object = None
+    miss_targets: object = None
+    miss_din: object = None
+
+    def resolve(self, tr):
+        """Wait for the targets -> the batch's D items: the generated examples', then the pre-enhanced ones'."""
+        rq = lambda q: torch.from_numpy(q.result()).to(tr.device) if hasattr(q, 'result') else q
+        qua, drc_qua = rq(self.qua), rq(self.drc_qua)
+        tgt = self.targets.result()
+        if self.din_drc is not None:
+            tgt, tgt_d = tgt
+        items = tr._items(self.din, tgt, qua, self.frames, self.frames_host)
+        if self.din_drc is not None:
+            items_d = tr._items(self.din_drc, tgt_d, drc_qua, self.frames, self.frames_host)
+            if self.drc_keys is not None:                              # first time these utterances' pre-enhanced examples are scored
+                for k, it in zip(self.drc_keys, items_d):
+                    tr._drc_cache.store(k, it)
+            return items + items_d
+        if self.drc_items is None:
+            return items
+        if self.miss:
+            miss, fh = self.miss, self.frames_host
+            fr = None if self.frames is None else ([fh[r] for r in miss] if fh is not None else [int(v) for v in self.frames[miss].tolist()])
+            new = tr._items(self.miss_din, self.miss_targets.result(), None if drc_qua is None else drc_qua[miss],
+                            None if fr is None else self.frames, fr)
+            for r, it in zip(miss, new):
+                self.drc_items[r] = tr._drc_cache.store(self.drc_keys[r], it) or _own_storage(it)
+        return items + self.drc_items
+
+
 class GanTrainer:
-    # fit(multienh='ssdrc') sets it on the instance: a batch without 'drc' then gets ssdrc.ssdrc(clean) as its pre-enhanced example.  A class
-    # attribute, so that a trainer assembled without the constructor (the epoch tests' doubles) has the default too.
-    multienh = None
+    # Defaults of what the constructor, enable_clean_cache() or fit() set on the instance - class attributes, so that a trainer assembled
+    # without the constructor (the epoch tests' doubles) has them too.
+    multienh = None                 # fit(multienh='ssdrc'): a batch without 'drc' then gets ssdrc.ssdrc(clean) as its pre-enhanced example
+    room = None
+    quality_scorer = None
+    target_lag = 3                  # run_epoch: batches whose metric targets may be in flight behind the sample-generation loop
+    clean_cache = None              # metrics.CleanStateCache (enable_clean_cache): clean-signal halves of SIIB / HASPI kept across epochs
+    cache_len_quantum = 16384       # metric inputs are padded to multiples of this many samples while the cache is on (_canon)
+    _feat_cache = None              # _FeatureCache, _PreEnhancedItems (enable_clean_cache; in use while ``clean_cache`` is not None)
+    _drc_cache = None
+    _write_pool = None              # write_samples(wait=False): the background writer and what it has been handed
+    _writes = None
 
     def __init__(self, target_metric=TargetMetric, device='cuda', lr_g=5e-4, lr_d=2.5e-4, use_quality=False, pcm16=True, seed=666,
                  haspi_dither=None, dither_seed=0, quality_scorer=None, norm='utterance', room=None):
@@ -229,8 +351,6 @@ class GanTrainer:
         # hides under them.  One rank: no collective, nothing is deferred.
         self.overlap_allreduce = True
         self._pending_d = None
-        self.target_lag = 3                          # run_epoch: batches whose metric targets may be in flight behind the sample-generation loop
-        self.clean_cache = None                      # metrics.CleanStateCache (enable_clean_cache): clean-signal halves of SIIB / HASPI kept across epochs
         for m in (self.G, self.D, self.D_Qua):
             if m is not None:
                 ndist.broadcast_module_(m, 0)
@@ -396,23 +516,17 @@ class GanTrainer:
         if budget_bytes is None:
             budget_bytes = torch.cuda.mem_get_info(self.device)[0] // 4
         self.clean_cache = mt.CleanStateCache(budget_bytes)
-        self.cache_len_quantum = 16384               # metric inputs are padded to multiples of this many samples while the cache is on (_canon)
-        import collections
-        self._feat_cache = collections.OrderedDict() # run_epoch: features of a batch of (clean, noise) files, keyed by the batch's keys (LRU)
-        self._feat_bytes = 0
-        self._feat_seen = collections.OrderedDict()  # batch keys seen once (no tensors): a batch's features are kept from its second sighting on
-        self._drc_cache = {}                         # run_epoch: D item (input, targets[, quality targets]) of an utterance's pre-enhanced example
+        self.cache_len_quantum = 16384
+        self._feat_cache = _FeatureCache(self.clean_cache)
+        self._drc_cache = _PreEnhancedItems(self.clean_cache)
         return self.clean_cache
-
-    def _dither_tag(self):
-        return None if self.haspi_dither is None else (self.haspi_dither, self.dither_seed)
 
     def _canon(self, x, ys, lengths):
         """Metric inputs of a batch in the cache's canonical geometry: rows zero-padded to the next multiple of ``cache_len_quantum`` samples
         and explicit per-row lengths.  A cached clean-signal state is laid out for one padded length; a loop that re-draws its batches every
         epoch (fit) pads every batch to its own longest file, so the same utterance would otherwise be looked up under ever new lengths.  The
         scores do not depend on the padding (everything behind a row's own end is zeros and never read; tests/test_varlen_gpu.py)."""
-        q = int(getattr(self, 'cache_len_quantum', 16384))
+        q = int(self.cache_len_quantum)
         B, L = x.shape
         Lc = (L + q - 1) // q * q
         if lengths is None:
@@ -425,22 +539,26 @@ class GanTrainer:
             return o
         return pad(x), [pad(y_) for y_ in ys], lengths
 
+    def _split_metric(self, m, x, which, lengths, utt_ids, keys):
+        """SIIB's or HASPI's split form on clean batch ``x`` with its clean-signal half done - from the cache when there is one and every
+        utterance of the batch is in it.  -> (degraded, note): degraded(y) -> (raw, mapped) of one degraded version, in the split
+        object's workspace until the next call; note() then folds that call's status into accumulator ``which``."""
+        if m == 'siib':
+            sp = mt.SiibSplit(x, lengths=lengths, owner=self._ws)
+            sp.clean_part(cache=self.clean_cache, keys=keys)
+            return sp.degraded_part, lambda: self._note_status(which, siib_info=sp.info)
+        hp = mt.HaspiSplit(x, lengths=lengths, owner=self._ws)
+        dz = self._dither(x, utt_ids)
+        hp.clean_part(dither=dz, cache=self.clean_cache, keys=keys, dither_tag=None if self.haspi_dither is None else (self.haspi_dither, self.dither_seed))
+        return (lambda y: hp.degraded_part(y, dither=dz)), lambda: self._note_status(which, haspi_info=hp.info)
+
     def _metric(self, m, x, y, which, lengths=None, utt_ids=None, keys=None):
         if self.clean_cache is not None and keys is not None and m in ('siib', 'haspi'):
-            # split form: the clean-signal half comes from the cache when every utterance of the batch is in it (bit-identical to the
-            # one-call form: phase 0 runs exactly phases 3 and 4 back to back)
-            if m == 'siib':
-                sp = mt.SiibSplit(x, lengths=lengths, owner=self._ws)
-                sp.clean_part(cache=self.clean_cache, keys=keys)
-                raw, mapped = sp.degraded_part(y)
-                self._note_status(which, siib_info=sp.info)
-            else:
-                hp = mt.HaspiSplit(x, lengths=lengths, owner=self._ws)
-                dz = self._dither(x, utt_ids)
-                hp.clean_part(dither=dz, cache=self.clean_cache, keys=keys, dither_tag=self._dither_tag())
-                raw, mapped = hp.degraded_part(y, dither=dz)
-                self._note_status(which, haspi_info=hp.info)
-            return raw, mapped
+            # split form: bit-identical to the one-call form (phase 0 runs exactly phases 3 and 4 back to back)
+            degraded, note = self._split_metric(m, x, which, lengths, utt_ids, keys)
+            res = degraded(y)
+            note()
+            return res
         if m == 'siib':
             raw, mapped, info = mt.batch_siib(x, y, return_info=True, lengths=lengths)
             self._note_status(which, siib_info=info)
@@ -481,6 +599,12 @@ class GanTrainer:
         elif lengths is not None:
             lengths = torch.clamp(lengths, max=L)
         return self.room.apply(clean_wav[:, :L], enh_wav[:, :L], noise_wav[:, :L], rir_ids, lengths)
+
+    def _drc_lengths(self, clean_wav, drc_wav, lengths, drc_lengths):
+        """Samples of every row that the comparison with the pre-enhanced example sees: min(clean, pre-enhanced), at most the two batches'
+        common width (audio_util.py:134-137); a side that brings no lengths counts with its full width."""
+        full = lambda t, w: torch.full((w.shape[0],), w.shape[1], dtype=torch.int32, device=self.device) if t is None else au._i32(t, self.device)
+        return torch.clamp(torch.minimum(full(drc_lengths, drc_wav), full(lengths, clean_wav)), max=min(clean_wav.shape[1], drc_wav.shape[1]))
 
     def true_metrics(self, clean_wav, enh_wav, noise_wav, norm=True, lengths=None, resynth=True, utt_ids=None, defer=False, keys=None,
                      rir_ids=None):
@@ -530,21 +654,19 @@ class GanTrainer:
         signal is cut to each comparison's own length before it is normalised, so the two share a clean-signal state only through the
         cache, whose keys tell them apart)."""
         lengths = au._i32(lengths, self.device)
-        if self.room is not None and rir_ids is not None:
-            full_ = lambda t, w: torch.full((w.shape[0],), w.shape[1], dtype=torch.int32, device=self.device) if t is None else au._i32(t, self.device)
-            ml_d_ = torch.clamp(torch.minimum(full_(drc_lengths, drc_wav), full_(lengths, clean_wav)), max=min(clean_wav.shape[1], drc_wav.shape[1]))
-            kd_ = None if keys is None else [('drc', k_) for k_ in keys]
-            pa = self.true_metrics(clean_wav, enh_wav, noise_wav, norm=norm, lengths=lengths, utt_ids=utt_ids, defer=defer, keys=keys, rir_ids=rir_ids)
-            pb = self.true_metrics(clean_wav, drc_wav, noise_wav, norm=norm, lengths=ml_d_, resynth=False, utt_ids=utt_ids, defer=defer, keys=kd_,
-                                   rir_ids=rir_ids)
+
+        def two_calls(ml_d, **room):
+            # (the pre-enhanced comparison sees the clean file cut to another length: its clean-signal state is cached under its own key)
+            kd = None if keys is None else [('drc', k_) for k_ in keys]
+            pa = self.true_metrics(clean_wav, enh_wav, noise_wav, norm=norm, lengths=lengths, utt_ids=utt_ids, defer=defer, keys=keys, **room)
+            pb = self.true_metrics(clean_wav, drc_wav, noise_wav, norm=norm, lengths=ml_d, resynth=False, utt_ids=utt_ids, defer=defer, keys=kd, **room)
             return _PendingTargets([], lambda: (pa.result(), pb.result())) if defer else (pa, pb)
+        if self.room is not None and rir_ids is not None:
+            return two_calls(self._drc_lengths(clean_wav, drc_wav, lengths, drc_lengths), rir_ids=rir_ids)
         L = min(clean_wav.shape[1], enh_wav.shape[1])
         Ld = min(clean_wav.shape[1], drc_wav.shape[1])
         ml_e = self.enhanced_lengths(lengths)
-        ml_d = None
-        if drc_lengths is not None or lengths is not None:
-            full = lambda t, w: torch.full((w.shape[0],), w.shape[1], dtype=torch.int32, device=self.device) if t is None else au._i32(t, self.device)
-            ml_d = torch.clamp(torch.minimum(full(drc_lengths, drc_wav), full(lengths, clean_wav)), max=Ld)
+        ml_d = self._drc_lengths(clean_wav, drc_wav, lengths, drc_lengths) if (drc_lengths is not None or lengths is not None) else None
         if ml_e is not None and ml_d is not None and lengths_host is not None and (drc_lengths_host is not None or drc_lengths is None):
             # the same comparison on the host copies of the lengths a loader hands over (dataio.FileBatches): no device read-back, which
             # would stall the thread that enqueues the GPU work once per batch
@@ -553,49 +675,32 @@ class GanTrainer:
             eq = bool(np.array_equal(256 * (lh // 256), np.minimum(np.minimum(dh, lh), Ld)))
         else:
             eq = (ml_e is None and ml_d is None) or (ml_e is not None and ml_d is not None and bool(torch.equal(ml_e, ml_d)))
-        same = (L == Ld) and eq
-        if not same:
-            # (the pre-enhanced comparison sees the clean file cut to another length: its clean-signal state is cached under its own key)
-            kd = None if keys is None else [('drc', k_) for k_ in keys]
-            if defer:
-                pa = self.true_metrics(clean_wav, enh_wav, noise_wav, norm=norm, lengths=lengths, utt_ids=utt_ids, defer=True, keys=keys)
-                pb = self.true_metrics(clean_wav, drc_wav, noise_wav, norm=norm, lengths=ml_d, resynth=False, utt_ids=utt_ids, defer=True, keys=kd)
-                return _PendingTargets([], lambda: (pa.result(), pb.result()))
-            return (self.true_metrics(clean_wav, enh_wav, noise_wav, norm=norm, lengths=lengths, utt_ids=utt_ids, keys=keys),
-                    self.true_metrics(clean_wav, drc_wav, noise_wav, norm=norm, lengths=ml_d, resynth=False, utt_ids=utt_ids, keys=kd))
+        if not (L == Ld and eq):
+            return two_calls(ml_d)
         x = clean_wav[:, :L].contiguous()
         ys = [(enh_wav[:, :L] + noise_wav[:, :L]).contiguous(), (drc_wav[:, :L] + noise_wav[:, :L]).contiguous()]
         if self.clean_cache is not None and keys is not None:
             x, ys, ml_e = self._canon(x, ys, ml_e)
             ml_d = ml_e
-        pick = (lambda r, m_: m_) if norm else (lambda r, m_: r)
         cols = [{}, {}]
         fork = self._metric_fork([x] + ys + [ml_e, ml_d])
         for m in self.metrics:
             with fork.on(m) as which:
-                if m == 'siib':
-                    sp = mt.SiibSplit(x, lengths=ml_e, owner=self._ws)
-                    sp.clean_part(cache=self.clean_cache, keys=keys)
+                if m in ('siib', 'haspi'):
+                    degraded, note = self._split_metric(m, x, which, ml_e, utt_ids, keys)
                     for k, y in enumerate(ys):
-                        raw, mapped = sp.degraded_part(y)
-                        cols[k][m] = fork.out(pick(raw, mapped).clone())
-                        self._note_status(which, siib_info=sp.info)
-                elif m == 'haspi':
-                    hp = mt.HaspiSplit(x, lengths=ml_e, owner=self._ws)
-                    dz = self._dither(x, utt_ids)
-                    hp.clean_part(dither=dz, cache=self.clean_cache, keys=keys, dither_tag=self._dither_tag())
-                    for k, y in enumerate(ys):
-                        raw, mapped = hp.degraded_part(y, dither=dz)
-                        cols[k][m] = fork.out(pick(raw, mapped).clone())
-                        self._note_status(which, haspi_info=hp.info)
+                        raw, mapped = degraded(y)
+                        cols[k][m] = fork.out((mapped if norm else raw).clone())       # (out of the workspace the next call writes)
+                        note()
                 else:
                     for k, y in enumerate(ys):
                         raw, mapped = mt.batch_estoi(x, y, lengths=ml_e)
-                        cols[k][m] = fork.out(pick(raw, mapped))
+                        cols[k][m] = fork.out(mapped if norm else raw)
+        build = lambda: tuple(torch.stack([c[m] for m in self.metrics], dim=1) for c in cols)
         if defer:
-            return _PendingTargets([fork], lambda: tuple(torch.stack([c[m] for m in self.metrics], dim=1) for c in cols))
+            return _PendingTargets([fork], build)
         fork.join()
-        return tuple(torch.stack([c[m] for m in self.metrics], dim=1) for c in cols)
+        return build()
 
     # ---------------------------------------------------------------- D-step (train_nele.py:349-367)
     def d_inputs(self, enh_wav, noise_band, clean_band, lengths=None, resynth=True):
@@ -1178,262 +1283,218 @@ class GanTrainer:
         its three training passes and the mean true targets of those samples (``target_mean``) - see tools/learn_curve.py.
         Returns a dict of what happened (losses, validation means, counts)."""
         out = {'gan_epoch': int(gan_epoch), 'g_steps': 0, 'g_loss': None, 'valid': None, 'samples': 0}
-        feats = [None] * len(train_batches)
-        dp = self.world > 1
-
-        def fts(b):
-            # with the clean-signal cache on, a batch's features (STFT / band energies of the clean file, IMCRA noise track of its noise
-            # file: both files are fixed per utterance, train_nele.py:119, dataloader.py:30-42) are kept too, keyed by the batch's keys
-            kw_ = ckw(b)
-            fc = getattr(self, '_feat_cache', None)
-            k_ = None
-            if kw_ and kw_['keys'] is not None and fc is not None:
-                k_ = (tuple(kw_['keys']), tuple(b['clean'].shape), b.get('noise_key'))     # (mixed noise: another batch of features every epoch)
-                hit = fc.get(k_)
-                if hit is not None:
-                    fc.move_to_end(k_)
-                    return hit[0]
-            f_ = self.features(b['clean'], b['noise'], b.get('lengths'))
-            if k_ is not None:
-                # least-recently-used, at most an eighth of the cache's budget: a loop that re-draws its batches every epoch (fit: the
-                # reference shuffles its file list, train_nele.py:118) never sees a batch twice and must not crowd the per-utterance states out
-                nb_ = sum(t.numel() * t.element_size() for t in f_.values() if torch.is_tensor(t))
-                cap_ = self.clean_cache.budget // 8
-                seen_ = self._feat_seen
-                first_ = k_ not in seen_                                # admitted on its SECOND sighting: a composition that never comes back
-                seen_[k_] = True                                        # (re-drawn batches) is not kept at all
-                seen_.move_to_end(k_)
-                while len(seen_) > 4096:
-                    seen_.popitem(last=False)
-                if nb_ <= cap_ and not first_:
-                    while fc and self._feat_bytes + nb_ > cap_:
-                        _, old_ = fc.popitem(last=False)
-                        self._feat_bytes -= old_[1]
-                    fc[k_] = (f_, nb_)
-                    self._feat_bytes += nb_
-            return f_
-
-        def hkw(b):                                                     # host copies of the lengths, when the loader has them (test doubles take none)
-            return ({'lengths_host': b['lengths_host'], 'drc_lengths_host': b.get('drc_lengths_host')}
-                    if (b.get('lengths_host') is not None and (b.get('drc_lengths_host') is not None or b.get('drc_lengths') is None)) else {})
-
-        def ckw(b):                                                     # utterance keys travel only when the clean-signal cache is on
-            return {'keys': b.get('keys', b.get('names'))} if getattr(self, 'clean_cache', None) is not None else {}
-
-        def rkw(b, rows=None):                                          # the rows' RIRs (batch key 'rir': host int32 [B]) travel when the trainer has a room
-            if getattr(self, 'room', None) is None or b.get('rir') is None:
-                return {}
-            r_ = np.asarray(b['rir'].cpu() if torch.is_tensor(b['rir']) else b['rir'], dtype=np.int32)
-            return {'rir_ids': r_ if rows is None else r_[rows]}
-
+        feats = [None] * len(train_batches)                             # the G-steps' features serve the sample generation too
         if gan_epoch >= 2:                                              # :122
-            tot = None
-            n_g = len(train_batches)
-            if dp:                                                      # ranks may hold different batch counts: same number of all-reduces
-                n_g = ndist.allreduce_max_int(n_g, self.device)
-            for i in range(n_g):
-                if i < len(train_batches):
-                    b = train_batches[i]
-                    f = feats[i] = fts(b)
-                    lg = self.g_step(f['clean_band'], f['noise_band'], f.get('frames'), weight=b['clean'].shape[0] if dp else None)
-                    tot = lg if tot is None else tot + lg
-                else:
-                    self.g_step(None, None, weight=0)
-                out['g_steps'] += 1
-            out['g_loss'] = tot / max(1, len(train_batches)) if tot is not None else None
-        raw, vq = [], []
-        scorer = getattr(self, 'quality_scorer', None)
-
-        def nsamp(b, wav, resynth=True, other=None):
-            # samples of every row the quality programs compare: the file the reference would have written (256 * (L // 256) samples of a
-            # generated example), or min(clean, pre-enhanced) for a pre-enhanced one
-            lh = b.get('lengths_host')
-            if lh is None:
-                lh = b['lengths'].tolist() if b.get('lengths') is not None else [b['clean'].shape[1]] * b['clean'].shape[0]
-            ns_ = [int(v) for v in lh]
-            if other is not None:
-                ns_ = [min(a_, int(o_)) for a_, o_ in zip(ns_, other)]
-            if resynth:
-                ns_ = [256 * (v // 256) for v in ns_]
-            return [min(v, wav.shape[1]) for v in ns_]
-
-        for b in valid_batches:                                         # :159-222
-            f = fts(b)
-            enh = self.generate(f['clean_band'], f['noise_band'], f['clean_spec'], frames=f.get('frames'))
-            if scorer is not None:                                      # :216-222 (norm=False: the raw scores of the learning curve)
-                vq.append(self._quality_async(b['clean'], enh, nsamp(b, enh), mapped=False))
-            if sample_dir is not None and 'names' in b:                 # :190-198 (the reference keeps the first 20 for listening)
-                self.write_samples(enh, b['names'], sample_dir + '/Test_epoch' + str(gan_epoch), gan_epoch,
-                                   lengths=b.get('lengths_host', b.get('lengths')), wait=False)
-            raw.append(self.true_metrics(b['clean'], enh, b['noise'], norm=False, lengths=b.get('lengths'), utt_ids=b.get('ids'), defer=True, **ckw(b),
-                                         **rkw(b)))
-        raw = [p.result() for p in raw]                                 # (a batch's metrics ran under the next batch's generator)
-        if raw or (dp and valid_batches is not None):
-            n_m = len(self.metrics)
-            acc = torch.zeros(2 * n_m + 1 + 3, dtype=torch.float64, device=self.device)
-            if vq:                                                      # [.., sum PESQ, sum ViSQOL, utterances scored]
-                q_ = np.concatenate([p.result() for p in vq], axis=0).astype(np.float64)
-                acc[2 * n_m + 1:] = torch.tensor([q_[:, 0].sum(), q_[:, 1].sum(), float(q_.shape[0])], dtype=torch.float64)
-            if raw:
-                r = torch.cat(raw, dim=0).double()
-                acc[:n_m] = r.sum(dim=0)
-                acc[n_m] = r.shape[0]
-                # the same scores through the reference's logistic maps (intel.py:52-55,102-106,116-118): what D is trained to predict
-                # and G is trained to push to 1 - not part of the reference's log line, reported beside it (out['valid_mapped'])
-                for i, m in enumerate(self.metrics):
-                    k_, x0_ = _MAPS[m]
-                    acc[n_m + 1 + i] = (1.0 / (1.0 + torch.exp(-k_ * (r[:, i] - x0_)))).sum()
-            if dp:                                                      # the learning curve is the mean over ALL validation utterances
-                import torch.distributed as tdist
-                tdist.all_reduce(acc)
-            if float(acc[n_m]) > 0:
-                r = (acc[:n_m] / acc[n_m]).cpu().numpy()
-                col = {m: float(r[i]) for i, m in enumerate(self.metrics)}
-                out['valid'] = col
-                rm = (acc[n_m + 1:2 * n_m + 1] / acc[n_m]).cpu().numpy()
-                out['valid_mapped'] = {m: float(rm[i]) for i, m in enumerate(self.metrics)}
-                if float(acc[2 * n_m + 3]) > 0:                         # Test_PESQ / Test_VISQOL (:217-222)
-                    col['pesq'] = float(acc[2 * n_m + 1] / acc[2 * n_m + 3])
-                    col['visqol'] = float(acc[2 * n_m + 2] / acc[2 * n_m + 3])
-                line = self.validation_log_line(col.get('siib', 0.0), col.get('haspi', 0.0), col.get('estoi', 0.0), gan_epoch)
-                if log_path is not None and ndist.rank() == 0:
-                    with open(log_path, 'a') as fh:                     # :224-225
-                        fh.write(line)
+            out['g_steps'], out['g_loss'] = self._g_steps(train_batches, feats)
+        out.update(self._validate(gan_epoch, valid_batches, sample_dir, log_path))
         if chkpt_path is not None and ndist.rank() == 0:
             self.save_checkpoint(chkpt_path)                            # :272-277
-        samples, pending, resolved = [], [], 0
-        out['sample_files'] = []
-
-        def rq(q):                                                      # quality targets scored on the host meanwhile (_quality_async)
-            return torch.from_numpy(q.result()).to(self.device) if hasattr(q, 'result') else q
-
-        def resolve(item):
-            pend, din, qua, frames, din_d, drc_qua, fh, drc_items, store_keys, part = item
-            qua, drc_qua = rq(qua), rq(drc_qua)
-            tgt = pend.result()
-            if din_d is not None:
-                tgt, tgt_d = tgt
-            samples.extend(self._items(din, tgt, qua, frames, fh))
-            if din_d is not None:
-                items_d = self._items(din_d, tgt_d, drc_qua, frames, fh)
-                samples.extend(items_d)
-                if store_keys is not None:                              # first time these utterances' pre-enhanced examples are scored: keep them
-                    for k_, it in zip(store_keys, items_d):
-                        nb_ = it[0].numel() * 4 + 64
-                        if k_ not in self._drc_cache and self.clean_cache.used + nb_ <= self.clean_cache.budget:
-                            self._drc_cache[k_] = tuple(None if t is None else t.clone() for t in it)   # (own storage: not a view of the batch)
-                            self.clean_cache.used += nb_
-            elif drc_items is not None:
-                if part is not None:                                    # the batch's new pre-enhanced examples, computed as a batch of their own
-                    pend_sub, din_sub, miss, dkeys, frames_b, fh_b, qua_b = part
-                    qua_b = drc_qua                                     # (resolved above when it was a future)
-                    tgt_sub = pend_sub.result()
-                    fr_sub = None if frames_b is None else ([fh_b[r_] for r_ in miss] if fh_b is not None else [int(v) for v in frames_b[miss].tolist()])
-                    new_items = self._items(din_sub, tgt_sub, None if qua_b is None else qua_b[miss], None if fr_sub is None else frames_b, fr_sub)
-                    for r_, it in zip(miss, new_items):
-                        it = tuple(None if t is None else t.clone() for t in it)
-                        drc_items[r_] = it
-                        nb_ = it[0].numel() * 4 + 64
-                        if self.clean_cache.used + nb_ <= self.clean_cache.budget:
-                            self._drc_cache[dkeys[r_]] = it
-                            self.clean_cache.used += nb_
-                samples.extend(drc_items)
-        for i, b in enumerate(train_batches):                           # :279-340
-            f = feats[i] if feats[i] is not None else fts(b)
-            lens, frames = b.get('lengths'), f.get('frames')
-            enh = self.generate(f['clean_band'], f['noise_band'], f['clean_spec'], frames=frames)
-            if sample_dir is not None and 'names' in b:
-                out['sample_files'] += self.write_samples(enh, b['names'], sample_dir + '/For_discriminator_training', gan_epoch,
-                                                          lengths=b.get('lengths_host', lens), wait=False)
-            dl = b.get('drc_lengths', lens)
-            lazy = self.multienh == 'ssdrc' and b.get('drc') is None   # the pre-enhanced example is made here, when it is needed
-            # The pre-enhanced ('DRC') example of an utterance (:318-340; audio_util.py:267-321) never changes: its files are fixed, so its D
-            # input and its true targets are the same in every epoch the utterance is drawn.  With the clean-signal cache on they are kept
-            # per utterance key after the first time (the reference recomputes read_batch_*_DRC every epoch); a batch whose utterances are
-            # all known skips the DRC file's STFT and its three metric calls altogether.
-            dkeys = ckw(b).get('keys') if (b.get('drc') is not None or lazy) else None
-            if dkeys is not None and rkw(b):                            # a pre-enhanced example's targets are those of (utterance, RIR)
-                dkeys = self._room_keys(dkeys, rkw(b)['rir_ids'])
-            dcache = getattr(self, '_drc_cache', None)
-            if b.get('noise_key') is not None:                          # mixed noise: an utterance's noise changes with the epoch, and its pre-enhanced
-                dcache = None                                           # example's D input (noise band) and targets with it - nothing of them is kept
-            drc_items, miss = None, None
-            if dkeys is not None and dcache is not None:
-                drc_items = [dcache.get(k_) for k_ in dkeys]
-                miss = [r_ for r_, it in enumerate(drc_items) if it is None]
-                if len(miss) == len(dkeys):
-                    drc_items, miss = None, None                         # nothing known: the ordinary path for the whole batch
-            pend_sub = din_sub = None
-            if lazy and (drc_items is None or miss):
-                # SSDRC of the clean rows as a PCM_16 file of it reads back (ssdrc.py): bit-identical to the folder route; utterances whose
-                # pre-enhanced D items are all cached need none
-                from . import ssdrc as _ssdrc
-                b = dict(b, drc=_ssdrc.ssdrc(b['clean'], lens, pcm16=True), drc_lengths=lens, drc_lengths_host=b.get('lengths_host'))
-            if b.get('drc') is not None and drc_items is None:
-                # generated + pre-enhanced example of the same utterances: one pass over the clean signal for both when they are compared over
-                # the same samples (audio_util.py:134-137)
-                pend = self.true_metrics_pair(b['clean'], enh, b['drc'], b['noise'], lengths=lens, drc_lengths=dl, utt_ids=b.get('ids'), defer=True,
-                                              **ckw(b), **hkw(b), **rkw(b))
-            else:
-                pend = self.true_metrics(b['clean'], enh, b['noise'], lengths=lens, utt_ids=b.get('ids'), defer=True, **ckw(b), **rkw(b))
-                if miss:
-                    # some pre-enhanced examples of this batch are new (a loop that re-draws its batches every epoch): their targets and D
-                    # inputs as a batch of their own - true_metrics on (clean, pre-enhanced + noise) over min(clean, pre-enhanced) samples is
-                    # what true_metrics_pair computes for them (audio_util.py:267-321), and every kernel is batch-invariant
-                    idx = torch.tensor(miss, dtype=torch.long).to(self.device, non_blocking=True)
-                    sub = lambda t: None if t is None else t.index_select(0, idx)
-                    Ld_ = min(b['clean'].shape[1], b['drc'].shape[1])
-                    ml_d = None
-                    if dl is not None or lens is not None:
-                        full_ = lambda t, w: torch.full((w.shape[0],), w.shape[1], dtype=torch.int32, device=self.device) if t is None else au._i32(t, self.device)
-                        ml_d = torch.clamp(torch.minimum(full_(dl, b['drc']), full_(lens, b['clean'])), max=Ld_)
-                    pend_sub = self.true_metrics(sub(b['clean']), sub(b['drc']), sub(b['noise']), lengths=sub(ml_d), resynth=False,
-                                                 utt_ids=sub(b.get('ids')), defer=True, keys=[('drc', dkeys[r_]) for r_ in miss],
-                                                 **rkw(b, miss))
-                    din_sub = self.d_inputs(sub(b['drc']), sub(f['noise_band']), sub(f['clean_band']),
-                                            sub(au._i32(dl, self.device)) if dl is not None else None, resynth=False)
-            # the targets are not waited for here: this batch's metric kernels (three streams, SIIB's a latency chain through the
-            # eigensolver) run under the next batch's generator and feature kernels; everything is resolved behind the loop
-            din = self.d_inputs(enh, f['noise_band'], f['clean_band'], lens)
-            din_d = None
-            if b.get('drc') is not None and drc_items is None:
-                din_d = self.d_inputs(b['drc'], f['noise_band'], f['clean_band'], au._i32(dl, self.device) if dl is not None else None, resynth=False)
-            lh = b.get('lengths_host')
-            fh_ = None if lh is None else [1 + int(v) // 256 for v in lh]
-            qua, drc_qua = b.get('qua'), b.get('drc_qua')
-            if scorer is not None and self.D_Qua is not None:          # :323-324, 336-337: PESQ / ViSQOL of the examples D_Qua is trained on
-                if qua is None:
-                    qua = self._quality_async(b['clean'], enh, nsamp(b, enh))
-                if drc_qua is None and b.get('drc') is not None and (drc_items is None or miss):
-                    dlh = b.get('drc_lengths_host')
-                    if dlh is None:
-                        dlh = dl.tolist() if torch.is_tensor(dl) else (dl if dl is not None else [b['drc'].shape[1]] * b['drc'].shape[0])
-                    drc_qua = self._quality_async(b['clean'], b['drc'], nsamp(b, b['drc'], resynth=False, other=dlh),
-                                                  rows=None if drc_items is None else miss)
-            pending.append((pend, din, qua, frames, din_d, drc_qua, fh_,
-                            drc_items, dkeys if (dcache is not None and drc_items is None) else None,
-                            None if not miss else (pend_sub, din_sub, miss, dkeys, frames, fh_, drc_qua)))
-            # bounded lag: the targets of batch i - target_lag are resolved now, so that at most target_lag batches keep their metric inputs
-            # (x, y, lengths: 2 - 3 x B x L x 4 bytes each) alive and the main stream cannot run arbitrarily far ahead of the metric streams
-            while len(pending) - resolved > getattr(self, 'target_lag', 3):
-                resolve(pending[resolved])
-                resolved += 1
-        while resolved < len(pending):
-            resolve(pending[resolved])
-            resolved += 1
+        # (``held``: the batches' resolved records; what their metric forks keep alive is released when the epoch returns, not before D trains)
+        samples, out['sample_files'], held = self._generate_samples(gan_epoch, train_batches, feats, sample_dir)
         out['samples'] = len(samples)
-        d0 = self.step_d
-        if d_eval:                                                      # D's error on this epoch's samples before it has trained on them
-            out['d_mse_fresh'] = self.d_mse(samples, d_batch)
-            out['target_mean'] = torch.stack([s_[1] for s_ in samples]).double().mean(dim=0).tolist() if samples else None
-        self.d_epoch(samples, batch=d_batch)                            # :342-426
-        out['d_steps'] = self.step_d - d0
-        if d_eval:
-            out['d_mse_fit'] = self.d_mse(samples, d_batch)
+        out.update(self._train_d(samples, d_batch, d_eval))             # :342-426
         self.flush_writes()                                             # the epoch's sample files are on disk when it returns
         if check:
             out['status'] = self.check_status()
         return out
+
+    def _batch_kw(self, b):
+        """What travels with a batch's metric calls only when it is there (the stages' test doubles accept none of it): the utterance
+        keys with the clean-signal cache on, the rows' RIRs (batch key 'rir': host int32 [B]) when the trainer has a room."""
+        kw = {'keys': b.get('keys', b.get('names'))} if self.clean_cache is not None else {}
+        if self.room is not None and b.get('rir') is not None:
+            kw['rir_ids'] = np.asarray(b['rir'].cpu() if torch.is_tensor(b['rir']) else b['rir'], dtype=np.int32)
+        return kw
+
+    @staticmethod
+    def _compared_samples(b, wav, resynth=True, other=None):
+        """Samples of every row the quality programs compare: the file the reference would have written (256 * (L // 256) samples of a
+        generated example), or min(clean, pre-enhanced) for a pre-enhanced one (``other``: its lengths)."""
+        lh = b.get('lengths_host')
+        if lh is None:
+            lh = b['lengths'].tolist() if b.get('lengths') is not None else [b['clean'].shape[1]] * b['clean'].shape[0]
+        ns = [int(v) for v in lh]
+        if other is not None:
+            ns = [min(a_, int(o_)) for a_, o_ in zip(ns, other)]
+        if resynth:
+            ns = [256 * (v // 256) for v in ns]
+        return [min(v, wav.shape[1]) for v in ns]
+
+    def _batch_features(self, b):
+        """features() of a batch - out of the feature cache when the batch brings keys and has been seen before (_FeatureCache)"""
+        keys, key = self._batch_kw(b).get('keys'), None
+        if keys is not None and self._feat_cache is not None:
+            key = (tuple(keys), tuple(b['clean'].shape), b.get('noise_key'))       # (mixed noise: another batch of features every epoch)
+            f = self._feat_cache.get(key)
+            if f is not None:
+                return f
+        f = self.features(b['clean'], b['noise'], b.get('lengths'))
+        if key is not None:
+            self._feat_cache.put(key, f)
+        return f
+
+    def _g_steps(self, train_batches, feats):
+        """:122-156 over the epoch's batches; their features are left in ``feats``.  -> (steps, mean loss)"""
+        dp = self.world > 1
+        tot = None
+        n_g = len(train_batches)
+        if dp:                                                          # ranks may hold different batch counts: same number of all-reduces
+            n_g = ndist.allreduce_max_int(n_g, self.device)
+        for i in range(n_g):
+            if i < len(train_batches):
+                b = train_batches[i]
+                f = feats[i] = self._batch_features(b)
+                lg = self.g_step(f['clean_band'], f['noise_band'], f.get('frames'), weight=b['clean'].shape[0] if dp else None)
+                tot = lg if tot is None else tot + lg
+            else:
+                self.g_step(None, None, weight=0)
+        return n_g, (tot / max(1, len(train_batches)) if tot is not None else None)
+
+    def _validate(self, gan_epoch, valid_batches, sample_dir, log_path):
+        """:159-225: enhance the validation batches, raw metric means over all ranks, the learning-curve line.  -> what it adds to the
+        epoch's result: {'valid', 'valid_mapped'}, or nothing without validation utterances."""
+        raw, vq = [], []
+        for b in valid_batches:                                         # :159-222
+            f = self._batch_features(b)
+            enh = self.generate(f['clean_band'], f['noise_band'], f['clean_spec'], frames=f.get('frames'))
+            if self.quality_scorer is not None:                         # :216-222 (norm=False: the raw scores of the learning curve)
+                vq.append(self._quality_async(b['clean'], enh, self._compared_samples(b, enh), mapped=False))
+            if sample_dir is not None and 'names' in b:                 # :190-198 (the reference keeps the first 20 for listening)
+                self.write_samples(enh, b['names'], sample_dir + '/Test_epoch' + str(gan_epoch), gan_epoch,
+                                   lengths=b.get('lengths_host', b.get('lengths')), wait=False)
+            raw.append(self.true_metrics(b['clean'], enh, b['noise'], norm=False, lengths=b.get('lengths'), utt_ids=b.get('ids'), defer=True,
+                                         **self._batch_kw(b)))
+        raw = [p.result() for p in raw]                                 # (a batch's metrics ran under the next batch's generator)
+        dp = self.world > 1
+        if not (raw or (dp and valid_batches is not None)):
+            return {}
+        n_m = len(self.metrics)
+        acc = torch.zeros(2 * n_m + 1 + 3, dtype=torch.float64, device=self.device)
+        if vq:                                                          # [.., sum PESQ, sum ViSQOL, utterances scored]
+            q_ = np.concatenate([p.result() for p in vq], axis=0).astype(np.float64)
+            acc[2 * n_m + 1:] = torch.tensor([q_[:, 0].sum(), q_[:, 1].sum(), float(q_.shape[0])], dtype=torch.float64)
+        if raw:
+            r = torch.cat(raw, dim=0).double()
+            acc[:n_m] = r.sum(dim=0)
+            acc[n_m] = r.shape[0]
+            # the same scores through the reference's logistic maps (intel.py:52-55,102-106,116-118): what D is trained to predict
+            # and G is trained to push to 1 - not part of the reference's log line, reported beside it ('valid_mapped')
+            for i, m in enumerate(self.metrics):
+                k_, x0_ = _MAPS[m]
+                acc[n_m + 1 + i] = (1.0 / (1.0 + torch.exp(-k_ * (r[:, i] - x0_)))).sum()
+        if dp:                                                          # the learning curve is the mean over ALL validation utterances
+            import torch.distributed as tdist
+            tdist.all_reduce(acc)
+        if not float(acc[n_m]) > 0:
+            return {}
+        r = (acc[:n_m] / acc[n_m]).cpu().numpy()
+        col = {m: float(r[i]) for i, m in enumerate(self.metrics)}
+        rm = (acc[n_m + 1:2 * n_m + 1] / acc[n_m]).cpu().numpy()
+        if float(acc[2 * n_m + 3]) > 0:                                 # Test_PESQ / Test_VISQOL (:217-222)
+            col['pesq'] = float(acc[2 * n_m + 1] / acc[2 * n_m + 3])
+            col['visqol'] = float(acc[2 * n_m + 2] / acc[2 * n_m + 3])
+        line = self.validation_log_line(col.get('siib', 0.0), col.get('haspi', 0.0), col.get('estoi', 0.0), gan_epoch)
+        if log_path is not None and ndist.rank() == 0:
+            with open(log_path, 'a') as fh:                             # :224-225
+                fh.write(line)
+        return {'valid': col, 'valid_mapped': {m: float(rm[i]) for i, m in enumerate(self.metrics)}}
+
+    def _generate_samples(self, gan_epoch, train_batches, feats, sample_dir):
+        """:279-340: the D training samples of the epoch's utterances with their true targets.  -> (D items, sample files written, the
+        batches' _PendingBatch records)."""
+        samples, files, pending = [], [], []
+        for i, b in enumerate(train_batches):
+            f = feats[i] if feats[i] is not None else self._batch_features(b)
+            enh = self.generate(f['clean_band'], f['noise_band'], f['clean_spec'], frames=f.get('frames'))
+            if sample_dir is not None and 'names' in b:
+                files += self.write_samples(enh, b['names'], sample_dir + '/For_discriminator_training', gan_epoch,
+                                            lengths=b.get('lengths_host', b.get('lengths')), wait=False)
+            # the targets are not waited for here: this batch's metric kernels (three streams, SIIB's a latency chain through the
+            # eigensolver) run under the next batch's generator and feature kernels
+            pending.append(self._enqueue_targets(b, f, enh))
+            # bounded lag: the targets of batch i - target_lag are resolved now, so that the main stream cannot run arbitrarily far ahead of
+            # the metric streams
+            if len(pending) > self.target_lag:
+                samples.extend(pending[-1 - self.target_lag].resolve(self))
+        for p in pending[max(0, len(pending) - self.target_lag):]:
+            samples.extend(p.resolve(self))
+        return samples, files, pending
+
+    def _enqueue_targets(self, b, f, enh):
+        """The true targets (:318-340) and D inputs of a training batch whose generated examples are ``enh``, enqueued and not waited
+        for.  -> _PendingBatch"""
+        lens, frames = b.get('lengths'), f.get('frames')
+        dl = b.get('drc_lengths', lens)
+        lazy = self.multienh == 'ssdrc' and b.get('drc') is None   # the pre-enhanced example is made here, when it is needed
+        kw = self._batch_kw(b)
+        # With the clean-signal cache on, the pre-enhanced examples' D items are kept per utterance key (_PreEnhancedItems); a batch whose
+        # utterances are all known skips the DRC file's STFT and its three metric calls altogether.
+        dkeys = kw.get('keys') if (b.get('drc') is not None or lazy) else None
+        if dkeys is not None and 'rir_ids' in kw:                       # a pre-enhanced example's targets are those of (utterance, RIR)
+            dkeys = self._room_keys(dkeys, kw['rir_ids'])
+        # mixed noise: an utterance's noise changes with the epoch, and its pre-enhanced example's D input (noise band) and targets with
+        # it - nothing of them is kept
+        dcache = self._drc_cache if b.get('noise_key') is None else None
+        drc_items, miss = dcache.lookup(dkeys) if (dkeys is not None and dcache is not None) else (None, None)
+        if lazy and (drc_items is None or miss):
+            # SSDRC of the clean rows as a PCM_16 file of it reads back (ssdrc.py): bit-identical to the folder route; utterances whose
+            # pre-enhanced D items are all cached need none
+            from . import ssdrc as _ssdrc
+            b = dict(b, drc=_ssdrc.ssdrc(b['clean'], lens, pcm16=True), drc_lengths=lens, drc_lengths_host=b.get('lengths_host'))
+        whole = b.get('drc') is not None and drc_items is None          # the pre-enhanced example of every row is scored with this batch
+        lh = b.get('lengths_host')
+        p = _PendingBatch(None, None, b.get('qua'), frames, None if lh is None else [1 + int(v) // 256 for v in lh], drc_qua=b.get('drc_qua'),
+                          drc_keys=dkeys if dcache is not None else None, drc_items=drc_items, miss=miss)
+        if whole:
+            # generated + pre-enhanced example of the same utterances: one pass over the clean signal for both when they are compared over
+            # the same samples (audio_util.py:134-137); the host copies of the lengths travel when the loader has them
+            hkw = ({'lengths_host': lh, 'drc_lengths_host': b.get('drc_lengths_host')}
+                   if (lh is not None and (b.get('drc_lengths_host') is not None or b.get('drc_lengths') is None)) else {})
+            p.targets = self.true_metrics_pair(b['clean'], enh, b['drc'], b['noise'], lengths=lens, drc_lengths=dl, utt_ids=b.get('ids'), defer=True,
+                                               **kw, **hkw)
+        else:
+            p.targets = self.true_metrics(b['clean'], enh, b['noise'], lengths=lens, utt_ids=b.get('ids'), defer=True, **kw)
+            if miss:
+                p.miss_targets, p.miss_din = self._enqueue_missing(b, f, miss, dkeys, lens, dl, kw)
+        p.din = self.d_inputs(enh, f['noise_band'], f['clean_band'], lens)
+        if whole:
+            p.din_drc = self.d_inputs(b['drc'], f['noise_band'], f['clean_band'], au._i32(dl, self.device) if dl is not None else None, resynth=False)
+        if self.quality_scorer is not None and self.D_Qua is not None:  # :323-324, 336-337: PESQ / ViSQOL of the examples D_Qua is trained on
+            if p.qua is None:
+                p.qua = self._quality_async(b['clean'], enh, self._compared_samples(b, enh))
+            if p.drc_qua is None and b.get('drc') is not None and (drc_items is None or miss):
+                dlh = b.get('drc_lengths_host')
+                if dlh is None:
+                    dlh = dl.tolist() if torch.is_tensor(dl) else (dl if dl is not None else [b['drc'].shape[1]] * b['drc'].shape[0])
+                p.drc_qua = self._quality_async(b['clean'], b['drc'], self._compared_samples(b, b['drc'], resynth=False, other=dlh),
+                                                rows=None if drc_items is None else miss)
+        return p
+
+    def _enqueue_missing(self, b, f, miss, dkeys, lens, dl, kw):
+        """Some pre-enhanced examples of this batch are new (a loop that re-draws its batches every epoch): their targets and D inputs as a
+        batch of their own - true_metrics on (clean, pre-enhanced + noise) over min(clean, pre-enhanced) samples is what true_metrics_pair
+        computes for them (audio_util.py:267-321), and every kernel is batch-invariant.  -> (deferred targets, D input) of rows ``miss``"""
+        idx = torch.tensor(miss, dtype=torch.long).to(self.device, non_blocking=True)
+        sub = lambda t: None if t is None else t.index_select(0, idx)
+        ml_d = self._drc_lengths(b['clean'], b['drc'], lens, dl) if (dl is not None or lens is not None) else None
+        pend = self.true_metrics(sub(b['clean']), sub(b['drc']), sub(b['noise']), lengths=sub(ml_d), resynth=False, utt_ids=sub(b.get('ids')),
+                                 defer=True, keys=[('drc', dkeys[r_]) for r_ in miss], **({'rir_ids': kw['rir_ids'][miss]} if 'rir_ids' in kw else {}))
+        din = self.d_inputs(sub(b['drc']), sub(f['noise_band']), sub(f['clean_band']), sub(au._i32(dl, self.device)) if dl is not None else None,
+                            resynth=False)
+        return pend, din
+
+    def _train_d(self, samples, d_batch, d_eval):
+        """:342-426 on the epoch's samples.  -> what it adds to the epoch's result"""
+        res = {}
+        d0 = self.step_d
+        if d_eval:                                                      # D's error on this epoch's samples before it has trained on them
+            res['d_mse_fresh'] = self.d_mse(samples, d_batch)
+            res['target_mean'] = torch.stack([s_[1] for s_ in samples]).double().mean(dim=0).tolist() if samples else None
+        self.d_epoch(samples, batch=d_batch)
+        res['d_steps'] = self.step_d - d0
+        if d_eval:
+            res['d_mse_fit'] = self.d_mse(samples, d_batch)
+        return res
 
     # ---------------------------------------------------------------- the script's outer loop (train_nele.py:28-120, 272-277, 426-428)
     def fit(self, train_clean_files, train_noise_path, valid_clean_files=(), valid_noise_path=None, train_enh_path=None, epochs=GAN_epoch,
@@ -1562,7 +1623,7 @@ class GanTrainer:
             if wait:
                 job()
             else:
-                if getattr(self, '_write_pool', None) is None:
+                if self._write_pool is None:
                     import concurrent.futures as cf
                     self._write_pool, self._writes = cf.ThreadPoolExecutor(max_workers=1), []
                 self._writes.append(self._write_pool.submit(job))
@@ -1574,7 +1635,7 @@ class GanTrainer:
 
     def flush_writes(self):
         """Wait for the sample files handed to the background writer (write_samples(wait=False)); re-raises a writer's error."""
-        pend, self._writes = getattr(self, '_writes', None) or [], []
+        pend, self._writes = self._writes or [], []
         for f in pend:
             f.result()
 
@@ -1602,7 +1663,7 @@ class GanTrainer:
             sd['quality-model'] = self.D_Qua.state_dict()
         if self.norm != 'utterance':                 # (utterance-mode checkpoints stay what they were: the reference's two entries)
             sd['enhance-norm'] = self.norm
-        if getattr(self, 'room', None) is not None:  # the listener's room the targets were taken in: names, tau and a hash of the samples
+        if self.room is not None:                    # the listener's room the targets were taken in: names, tau and a hash of the samples
             sd['room'] = self.room.bank.record()
         torch.save(sd, path)
 
@@ -1620,7 +1681,7 @@ class GanTrainer:
         if recorded != self.norm and not allow_norm_mismatch:
             raise ValueError("load_checkpoint: %s was trained with norm=%r, this trainer runs norm=%r (allow_norm_mismatch=True loads it anyway)"
                              % (path, recorded, self.norm))
-        mine = self.room.bank.record() if getattr(self, 'room', None) is not None else None
+        mine = self.room.bank.record() if self.room is not None else None
         self.loaded_room = ck.get('room')
         if self.loaded_room != mine:
             import warnings

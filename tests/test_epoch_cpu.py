@@ -493,3 +493,148 @@ def test_deferred_d_update_equals_the_synchronous_one_world2():
         assert out[r]['sync'][1] == [(1, 1), (2, 2), (3, 3)]
         assert out[r]['defer'][1] == [(0, 0), (1, 1), (1, 1), (2, 2), (2, 2), (3, 3)]
     np.testing.assert_array_equal(out[0]['defer'][0], out[1]['defer'][0])
+
+
+# ------------------------------------------------------------------------------------------ the epoch's two caches: call order and policy
+class _Resolved:                                           # what a deferred metric call returns
+    def __init__(self, v):
+        self.v = v
+
+    def result(self):
+        return self.v
+
+
+def _recording_cache_trainer(log, budget=1 << 30, T=30):
+    """_recording_trainer with the clean-signal cache on; true_metrics / true_metrics_pair / d_inputs also record their row count, the
+    utterance keys and ``resynth``: ('metrics', rows, keys, resynth), ('pair', rows, keys), ('d_inputs', rows, resynth)."""
+    tr = _recording_trainer(log)
+    tr.enable_clean_cache(budget)
+    tup = lambda keys: None if keys is None else tuple(keys)
+
+    def features(c, n, lengths=None):
+        log.append('features')
+        return {'clean_band': torch.zeros(c.shape[0], T, 64), 'noise_band': torch.zeros(c.shape[0], T, 64), 'clean_spec': None}
+
+    def true_metrics(c, e, n, norm=True, lengths=None, resynth=True, utt_ids=None, defer=False, keys=None):
+        log.append(('metrics' if norm else 'metrics_raw', c.shape[0], tup(keys), resynth))
+        v = torch.full((c.shape[0], 2), 0.25)
+        return _Resolved(v) if defer else v
+
+    def true_metrics_pair(c, e, d, n, norm=True, lengths=None, drc_lengths=None, utt_ids=None, defer=False, keys=None):
+        log.append(('pair', c.shape[0], tup(keys)))
+        v = torch.full((c.shape[0], 2), 0.25), torch.full((c.shape[0], 2), 0.5)
+        return _Resolved(v) if defer else v
+
+    def d_inputs(e, nb, cb, lengths=None, resynth=True):
+        log.append(('d_inputs', e.shape[0], resynth))
+        return torch.zeros(e.shape[0], 64, T, 4)
+
+    tr.features, tr.true_metrics, tr.true_metrics_pair, tr.d_inputs = features, true_metrics, true_metrics_pair, d_inputs
+    return tr
+
+
+def _feat_state(tr):
+    """(entries, bytes, keys seen) of the trainer's feature cache"""
+    return len(tr._feat_cache), tr._feat_cache.bytes, len(tr._feat_cache.seen)
+
+
+def _b(*names, L=256 * 29, drc=True, **extra):
+    b = {'clean': torch.zeros(len(names), L), 'noise': torch.zeros(len(names), L), 'names': list(names)}
+    if drc:
+        b['drc'] = torch.zeros(len(names), L)
+    b.update(extra)
+    return b
+
+
+def _epoch(tr, log, gan_epoch, batches):
+    del log[:]
+    out = tr.run_epoch(gan_epoch, batches)
+    return list(log), out
+
+
+def test_epochs_that_redraw_their_batches_score_each_pre_enhanced_example_once():
+    """The pre-enhanced example of an utterance is scored the first time the utterance is drawn and kept per utterance key; a batch
+    that mixes known and new utterances scores the new rows as a batch of their own, BEHIND the generated batch's metric call and
+    before its D input; a batch's features are kept from its second sighting on."""
+    log = []
+    tr = _recording_cache_trainer(log)
+    seq, out = _epoch(tr, log, 1, [_b('u0', 'u1'), _b('u2', 'u3')])
+    assert seq == ['features', 'generate', ('pair', 2, ('u0', 'u1')), ('d_inputs', 2, True), ('d_inputs', 2, False),
+                   'features', 'generate', ('pair', 2, ('u2', 'u3')), ('d_inputs', 2, True), ('d_inputs', 2, False),
+                   'd_epoch:8']
+    assert sorted(tr._drc_cache) == ['u0', 'u1', 'u2', 'u3'] and out['samples'] == 8
+
+    redrawn = [_b('u0', 'u2'), _b('u1', 'u4')]
+    seq, out = _epoch(tr, log, 2, redrawn)
+    known = ['generate', ('metrics', 2, ('u0', 'u2'), True), ('d_inputs', 2, True)]      # no pair call, no pre-enhanced d_inputs
+    assert seq == ['features', 'g_step', 'features', 'g_step'] + known + [
+        'generate', ('metrics', 2, ('u1', 'u4'), True), ('metrics', 1, (('drc', 'u4'),), False), ('d_inputs', 1, False), ('d_inputs', 2, True),
+        'd_epoch:8']
+    assert sorted(tr._drc_cache) == ['u0', 'u1', 'u2', 'u3', 'u4'] and len(tr._drc_cache) == 5
+    assert tr.clean_cache.used == 153920 == 5 * (64 * 30 * 4 * 4 + 64)
+    assert _feat_state(tr)[:2] == (0, 0)                                                 # first sighting of these two compositions
+
+    all_known = known + ['generate', ('metrics', 2, ('u1', 'u4'), True), ('d_inputs', 2, True), 'd_epoch:8']
+    seq, out = _epoch(tr, log, 3, redrawn)
+    assert seq == ['features', 'g_step', 'features', 'g_step'] + all_known               # second sighting: computed once more, admitted now
+    assert _feat_state(tr)[:2] == (2, 61440) and tr.clean_cache.used == 153920
+
+    seq, out = _epoch(tr, log, 4, redrawn)
+    assert seq == ['g_step', 'g_step'] + all_known and out['samples'] == 8
+    # the kept D items are the pre-enhanced examples' (the pair double's second targets), one per utterance, with storage of their own
+    assert all(it[0].shape == (64, 30, 4) and it[2] is None for it in tr._drc_cache.values())
+    assert [float(tr._drc_cache[k][1][0]) for k in ('u0', 'u1', 'u2', 'u3', 'u4')] == [0.5] * 4 + [0.25]   # (u4: true_metrics' double)
+
+
+def test_a_budget_too_small_keeps_nothing_and_recomputes_every_epoch():
+    log = []
+    tr = _recording_cache_trainer(log, budget=1000)
+    for gan_epoch in (1, 2, 3):
+        seq, out = _epoch(tr, log, gan_epoch, [_b('u0', 'u1')])
+    assert seq == ['features', 'g_step', 'generate', ('pair', 2, ('u0', 'u1')), ('d_inputs', 2, True), ('d_inputs', 2, False), 'd_epoch:4']
+    assert len(tr._drc_cache) == 0 and _feat_state(tr)[:2] == (0, 0) and tr.clean_cache.used == 0
+
+
+def test_feature_cache_policy():
+    """A batch's features are kept from its SECOND sighting on, never when they exceed an eighth of the budget, least recently used first
+    out, a hit refreshes; the list of compositions seen once is bounded; the key is (keys, clean shape, noise_key)."""
+    log = []
+    entry = 2 * 2 * 30 * 64 * 4                                                          # clean_band + noise_band of a two-row batch
+    tr = _recording_cache_trainer(log, budget=8 * (2 * entry + 8000))                    # room for two such batches, not for three
+
+    def computed(b):                                                                     # one validation batch: was features() called?
+        seq, _ = _epoch_valid(tr, log, b)
+        assert seq[-2:] == ['generate', ('metrics_raw', b['clean'].shape[0], tuple(b['names']), True)]
+        return seq[:-2] == ['features']
+
+    A, B, C = _b('a0', 'a1', drc=False), _b('b0', 'b1', drc=False), _b('c0', 'c1', drc=False)
+    assert computed(A) and _feat_state(tr) == (0, 0, 1)                                  # first sighting: not stored
+    assert computed(A) and _feat_state(tr) == (1, entry, 1)                              # second: stored
+    assert not computed(A)
+    assert computed(B) and computed(B) and _feat_state(tr) == (2, 2 * entry, 2)
+    big = _b('d0', 'd1', 'd2', 'd3', 'd4', 'd5', drc=False)                              # 3 entries' worth: above budget // 8
+    assert computed(big) and computed(big) and computed(big) and _feat_state(tr) == (2, 2 * entry, 3)
+    assert not computed(A)                                                               # a hit: A is now the most recently used
+    assert computed(C) and computed(C) and _feat_state(tr) == (2, 2 * entry, 4)          # B made room
+    assert not computed(A) and not computed(C) and computed(B)                           # (B, seen before, is back at once: A made room)
+    # (keys, clean shape, noise_key): the same names at another padded length or under another noise mix are other features
+    assert not computed(C) and computed(_b('c0', 'c1', drc=False, L=256 * 30)) and computed(_b('c0', 'c1', drc=False, noise_key='mix1'))
+    # evicted until the new one fits: a four-row batch needs the room of both two-row entries
+    n0 = _feat_state(tr)[0]
+    wide = _b('e0', 'e1', 'e2', 'e3', drc=False)
+    assert n0 == 2 and computed(wide) and computed(wide) and _feat_state(tr)[:2] == (1, 2 * entry) and not computed(wide)
+
+
+def _epoch_valid(tr, log, b):
+    del log[:]
+    out = tr.run_epoch(1, [], valid_batches=[b], check=False)
+    assert log[-1] == 'd_epoch:0'
+    return log[:-1], out
+
+
+def test_feature_cache_seen_list_is_bounded():
+    log = []
+    tr = _recording_cache_trainer(log, T=1)
+    for k in range(0, 4200, 600):
+        tr.run_epoch(1, [], valid_batches=[_b('s%d' % i, L=256, drc=False) for i in range(k, k + 600)], check=False)
+    assert _feat_state(tr) == (0, 0, 4096)
