@@ -725,6 +725,31 @@ int nele_ssdrc_shape(const float* x, const int* lengths, int B, int Lmax, const 
 int nele_ssdrc_compress(const double* s, const int* lengths, int B, int Lmax, const nele_ssdrc_params* params, double* y, double* ehat,
                         void* ws, void* stream);
 
+/* ---- rational-ratio polyphase FIR resampler (csrc/resample.hip) ---------------------------------------------------------------------
+ * Audio at any sample rate to the rate the rest of the library works at (the reference asserts 16 kHz - dataloader.py:34-37 - so this
+ * is an addition, not a parity item).  scipy.signal.resample_poly's convention, specified in DESIGN.md section 12: up / down =
+ * sr_out / sr_in in lowest terms, half = zeros max(up, down), the 2 half + 1 taps h = up firwin(2 half + 1, 1 / max(up, down),
+ * window = ('kaiser', beta)) in float64.  A row x[0 .. L) (zeros outside) gives n_out = ceil(L up / down) samples
+ *     y[n] = (float)(gain sum_{k < K} hp[p][k] x[q - k]),   c = n down + half (64-bit), p = c mod up, q = c div up,
+ * hp[p][k] = h[p + k up] (zero where p + k up > 2 half), K = ceil((2 half + 1) / up), the sum in float64 with k ascending.
+ * Supported: 1 <= up, down <= 1024, down <= 16 up, up <= 16 down, 1 <= zeros <= 64, 0 <= beta <= 20, gain finite, lengths and Lmax_out
+ * up to 2^30, R <= 65535; anything else is -1 before any GPU call.  up = down = 1 copies (times gain).
+ * nele_resample_out_len / _taps_count / _taps / _tile are host functions that make no HIP call.  nele_resample_taps writes
+ * nele_resample_taps_count doubles to out_host: layout 0 h[0 .. 2 half], layout 1 the table hp[up][K] (what nele_resample_var takes,
+ * uploaded by the caller).  nele_resample_tile: outputs per workgroup (a row's tiles start at its multiples).
+ * nele_resample_var: x rows of x_stride floats, y rows of y_stride >= Lmax_out floats; lengths_in / lengths_out device [rows], indexed by
+ * row (lengths_in is required; values are clamped to 0 .. min(x_stride, 2^30)); row_ids device [R]: the rows to process, NULL = rows
+ * 0 .. R - 1.  For a processed row y[row][n_out .. Lmax_out) = 0 exactly and lengths_out[row] = n_out; nothing is written at or behind
+ * Lmax_out (n_out > Lmax_out is the caller's error).  Other rows are neither read nor written.  K must be the K of (up, down, zeros) for
+ * a zeros in 1 .. 64.  A row's output bits do not depend on R, Lmax_out, row_ids or the other rows.  No allocation, no workspace. */
+#define NELE_RESAMPLE_MAX_SAMPLES (1 << 30)
+long long nele_resample_out_len(long long n_in, int up, int down);
+long long nele_resample_taps_count(int up, int down, int zeros, int layout);
+int nele_resample_taps(int up, int down, int zeros, double beta, int layout, double* out_host);
+int nele_resample_tile(void);
+int nele_resample_var(const float* x, long long x_stride, const int* lengths_in, const int* row_ids, int R, int Lmax_out, int up, int down,
+                      int K, const double* hp_dev, double gain, float* y, long long y_stride, int* lengths_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

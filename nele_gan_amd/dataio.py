@@ -99,9 +99,13 @@ def read_wav_into(path, out_row):
     return n, fmt[2]
 
 
-def load(path, sr=None):
-    """librosa.load(path, sr=...) as the reference uses it: native rate only (every call site asserts 16 kHz)."""
+def load(path, sr=None, resample=False):
+    """librosa.load(path, sr=...) as the reference uses it: native rate only (every call site asserts 16 kHz).  ``resample=True``: a file
+    at another rate than ``sr`` comes back resampled to it on the GPU (resample.py, quality 'high') instead of raising."""
     x, file_sr = read_wav(path)
+    if sr is not None and sr != file_sr and resample:
+        from .resample import resample_host
+        return resample_host(x, file_sr, sr), sr
     if sr is not None and sr != file_sr:
         raise ValueError('%s: sample rate %d, expected %d (resampling on load is not part of the path)' % (path, file_sr, sr))
     return x, file_sr

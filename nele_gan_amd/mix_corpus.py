@@ -67,12 +67,13 @@ def main(argv=None):
     ap.add_argument('--epoch', type=int, default=0, help='which of the per-epoch draws to write (0: what validation without noise files uses)')
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--multienh', choices=('ssdrc',), default=None, help='also write MultiEnh/: the SSDRC of every clean file (ssdrc.py)')
+    ap.add_argument('--resample', action='store_true', help='resample pool files that are not at 16 kHz on the GPU instead of stopping on them')
     a = ap.parse_args(argv)
     clean = sorted(dataio.get_filepaths(a.clean))
     pool = sorted(dataio.get_filepaths(a.noise_pool))
     if not clean or not pool:
         ap.error('no wav file under %s' % (a.clean if not clean else a.noise_pool))
-    mixer = mixing.NoiseMixer(pool, snrs_db=[float(v) for v in a.snr.split(',')] if a.snr else synth.SNRS_DB, level=a.snr_level, seed=a.seed)
+    mixer = mixing.NoiseMixer(pool, snrs_db=[float(v) for v in a.snr.split(',')] if a.snr else synth.SNRS_DB, level=a.snr_level, seed=a.seed, resample=a.resample)
     rows = mix_corpus(clean, mixer, a.out, epoch=a.epoch, batch=a.batch, multienh=a.multienh)
     bad, clip = sum(1 for r in rows if r[6] != 0), sum(1 for r in rows if r[8] != 0)
     print('%d noise files under %s/Noise (%d not mixed: zero speech level or silent noise segment; %d with clipped samples - see mix_manifest.csv)'

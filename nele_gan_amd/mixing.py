@@ -23,9 +23,11 @@ def draw_words(seed, key, epoch, n=3):
 
 
 class NoiseMixer:
-    def __init__(self, pool, snrs_db=synth.SNRS_DB, level='asl', seed=0, device='cuda'):
+    def __init__(self, pool, snrs_db=synth.SNRS_DB, level='asl', seed=0, device='cuda', resample=False):
         """pool: a list of wav paths (16 kHz; read once, kept on the device as [N][Ln] float32 rows with their lengths) or a tensor / array
-        [N, Ln] (every row Ln samples) or a pair (rows [N, Ln], lengths [N]).  snrs_db: the SNRs drawn from.  level: 'asl' or 'rms'."""
+        [N, Ln] (every row Ln samples) or a pair (rows [N, Ln], lengths [N]).  snrs_db: the SNRs drawn from.  level: 'asl' or 'rms'.
+        resample=True: pool files at other rates are resampled to 16 kHz on the GPU (resample.py) before the rows and the pool hash are
+        formed, so tag() describes what is mixed; the default raises on them."""
         if level not in ('asl', 'rms'):
             raise ValueError("NoiseMixer: level must be 'asl' or 'rms'")
         self.level, self.seed, self.device = level, int(seed), device
@@ -38,7 +40,10 @@ class NoiseMixer:
             sig = []
             for p in pool:
                 x, sr = dataio.load(p)
-                if sr != 16000:
+                if sr != 16000 and resample and len(x):
+                    from .resample import resample_host
+                    x = resample_host(x, sr, 16000, device=device)
+                elif sr != 16000:
                     raise ValueError("NoiseMixer: %s has sample rate %d, expected 16000" % (p, sr))
                 if len(x) == 0:
                     raise ValueError("NoiseMixer: %s is empty" % p)

@@ -1,0 +1,263 @@
+"""Audio at any sample rate to the rate the package works at: a rational-ratio polyphase FIR resampler on the GPU (csrc/resample.hip; the
+operation is fixed by DESIGN.md section 12 - scipy.signal.resample_poly's convention with a Kaiser-windowed sinc).  The reference loads
+files at their own rate and asserts 16 kHz (dataloader.py:34-37): this is an addition to it, not a parity item.
+
+    Resampler(sr_in, sr_out=16000, quality='high').apply(wav, lengths) -> (y, lengths_out)        device tensors [B, L]
+    resample(wav, lengths, sr_in, sr_out=16000, quality='high')        -> (y, lengths_out)        sr_in: an int, or one per row
+    python -m nele_gan_amd.resample --in DIR --out DIR [--sr 16000] [--quality high|scipy] [--batch 64]
+                                                                       every .wav under DIR as PCM_16 at --sr, same relative path,
+                                                                       and DIR/resample_manifest.csv
+
+``quality``: 'high' = (zeros 32, Kaiser beta 12.0): stop band at most -119 dB from 1.15 x the new Nyquist frequency, pass-band ripple below
+0.001 dB up to 0.85 x; 'scipy' = (10, 5.0): resample_poly's own default (-43 dB); or a (zeros, beta) pair.  The taps are designed on the
+host by the library (nele_resample_taps: no GPU needed).  A row's output bits do not depend on the batch it is in.
+"""
+import ctypes
+import math
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import c_double, c_int, c_longlong, c_void_p, call, ptr, stream
+
+QUALITIES = {'high': (32, 12.0), 'scipy': (10, 5.0)}
+MAX_SAMPLES = 1 << 30                                      # NELE_RESAMPLE_MAX_SAMPLES (include/nele_hip.h)
+MANIFEST_COLUMNS = ('name', 'sr_in', 'samples_in', 'samples_out', 'peak', 'clipped_samples')
+
+_lib._SIGS.update({
+    'nele_resample_out_len': [c_longlong, c_int, c_int],
+    'nele_resample_taps_count': [c_int, c_int, c_int, c_int],
+    'nele_resample_taps': [c_int, c_int, c_int, c_double, c_int, c_void_p],
+    'nele_resample_tile': [],
+    'nele_resample_var': [c_void_p, c_longlong, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_double, c_void_p, c_longlong,
+                          c_void_p, c_void_p],
+})
+for _n in ('nele_resample_taps', 'nele_resample_tile', 'nele_resample_var'):
+    _lib.declare(_n, _lib._SIGS[_n])
+for _n in ('nele_resample_out_len', 'nele_resample_taps_count'):
+    getattr(_lib.lib, _n).argtypes = _lib._SIGS[_n]
+    getattr(_lib.lib, _n).restype = c_longlong
+
+TILE = int(_lib.lib.nele_resample_tile())                  # outputs per workgroup of the kernel (tests put lengths around it)
+
+
+def ratio(sr_in, sr_out):
+    """-> (up, down) = sr_out / sr_in in lowest terms"""
+    sr_in, sr_out = int(sr_in), int(sr_out)
+    if sr_in < 1 or sr_out < 1:
+        raise ValueError("resample: sample rates must be positive (got %d -> %d)" % (sr_in, sr_out))
+    g = math.gcd(sr_in, sr_out)
+    return sr_out // g, sr_in // g
+
+
+def quality_params(quality):
+    """'high' | 'scipy' | (zeros, beta) -> (zeros, beta)"""
+    if isinstance(quality, str):
+        if quality not in QUALITIES:
+            raise ValueError("resample: quality must be one of %s or a (zeros, beta) pair" % sorted(QUALITIES))
+        return QUALITIES[quality]
+    zeros, beta = quality
+    return int(zeros), float(beta)
+
+
+def out_len(n_in, up, down):
+    """ceil(n_in up / down): scipy.signal.resample_poly's output length (nele_resample_out_len)"""
+    n = int(_lib.lib.nele_resample_out_len(int(n_in), int(up), int(down)))
+    if n < 0:
+        _lib.check(-1, 'nele_resample_out_len')
+    return n
+
+
+def taps(up, down, zeros=32, beta=12.0, layout=0):
+    """The filter as the library designs it on the host (nele_resample_taps), float64: layout 0 the taps h[0 .. 2 half] in natural order,
+    layout 1 the polyphase table hp[up][K]."""
+    n = int(_lib.lib.nele_resample_taps_count(int(up), int(down), int(zeros), int(layout)))
+    if n < 0:
+        _lib.check(-1, 'nele_resample_taps_count')
+    out = np.empty(n, dtype=np.float64)
+    call('nele_resample_taps', int(up), int(down), int(zeros), float(beta), int(layout), c_void_p(out.ctypes.data))
+    return out.reshape(int(up), -1) if layout == 1 else out
+
+
+def _host_lengths(lengths, B):
+    if isinstance(lengths, torch.Tensor):
+        lengths = lengths.detach().cpu().numpy()
+    h = np.ascontiguousarray(np.asarray(lengths).reshape(-1), dtype=np.int64)
+    if h.shape != (B,):
+        raise ValueError("resample: lengths must hold one entry per row (%d), got %d" % (B, h.size))
+    return h
+
+
+class Resampler:
+    """One rate pair and one filter: the table is designed and uploaded once."""
+
+    def __init__(self, sr_in, sr_out=16000, quality='high', device='cuda'):
+        self.sr_in, self.sr_out = int(sr_in), int(sr_out)
+        self.up, self.down = ratio(sr_in, sr_out)
+        self.zeros, self.beta = quality_params(quality)
+        table = taps(self.up, self.down, self.zeros, self.beta, layout=1)          # raises ValueError outside the supported ratios
+        self.K = int(table.shape[1])
+        self.device = torch.device(device)
+        self.table = torch.from_numpy(table).to(self.device)
+
+    def out_len(self, n):
+        return out_len(n, self.up, self.down)
+
+    def apply(self, wav, lengths, row_ids=None, out=None, gain=1.0):
+        """wav float32 [B, Lmax] on the device, lengths [B] (host or device) -> (y float32 [B, Lmax_out], lengths_out int32 [B]) with exact
+        zeros behind each row's output length.  row_ids: the rows to process (others are neither read nor written; None: all).
+        out: a (y, lengths_out) pair to write into - y [B, >= the longest output] float32, lengths_out [B] int32, both on the device."""
+        if wav.dim() != 2 or wav.dtype != torch.float32 or wav.shape[0] == 0 or wav.shape[1] == 0:
+            raise ValueError("resample: wav must be a float32 [B, Lmax] tensor, not empty")
+        x = ptr(wav)                                         # raises on a host tensor: there is no CPU path
+        B, L = wav.shape
+        host = _host_lengths(lengths, B)
+        if (host < 0).any() or (host > L).any():
+            raise ValueError("resample: lengths must lie in 0 .. %d" % L)
+        if L > MAX_SAMPLES:
+            raise ValueError("resample: rows of more than 2^30 samples are not supported")
+        rows = np.arange(B) if row_ids is None else np.asarray(row_ids.cpu() if isinstance(row_ids, torch.Tensor) else row_ids, dtype=np.int64).reshape(-1)
+        if rows.size == 0 or (rows < 0).any() or (rows >= B).any():
+            raise ValueError("resample: row_ids must name rows 0 .. %d" % (B - 1))
+        need = max(1, max(self.out_len(int(host[r])) for r in rows))
+        dev = wav.device
+        if out is None:
+            y = torch.empty((B, need), dtype=torch.float32, device=dev) if row_ids is None else torch.zeros((B, need), dtype=torch.float32, device=dev)
+            n_out = torch.zeros((B,), dtype=torch.int32, device=dev)
+        else:
+            y, n_out = out
+            if y.dim() != 2 or y.dtype != torch.float32 or y.shape[0] != B or y.shape[1] < need or y.device != dev:
+                raise ValueError("resample: out[0] must be float32 [%d, >= %d] on %s" % (B, need, dev))
+            if n_out.dtype != torch.int32 or n_out.shape != (B,) or n_out.device != dev:
+                raise ValueError("resample: out[1] must be int32 [%d] on %s" % (B, dev))
+        ln = lengths if (isinstance(lengths, torch.Tensor) and lengths.dtype == torch.int32 and lengths.device == dev and lengths.is_contiguous()) \
+            else torch.from_numpy(host.astype(np.int32)).to(dev)
+        ids = None if row_ids is None else torch.from_numpy(rows.astype(np.int32)).to(dev)
+        table = self.table if self.table.device == dev else self.table.to(dev)
+        call('nele_resample_var', x, L, ptr(ln), ptr(ids), int(rows.size), int(y.shape[1]), self.up, self.down, self.K, ptr(table), float(gain),
+             ptr(y), int(y.shape[1]), ptr(n_out), stream())
+        return y, n_out
+
+
+_CACHE = {}
+
+
+def resampler(sr_in, sr_out=16000, quality='high', device='cuda'):
+    """The Resampler of (sr_in, sr_out, quality, device), built once per process."""
+    key = (int(sr_in), int(sr_out), quality if isinstance(quality, str) else tuple(quality), str(torch.device(device)))
+    r = _CACHE.get(key)
+    if r is None:
+        r = _CACHE[key] = Resampler(sr_in, sr_out, quality, device)
+    return r
+
+
+def resample(wav, lengths, sr_in, sr_out=16000, quality='high', gain=1.0):
+    """wav float32 [B, Lmax] on the device, lengths [B]; sr_in an int or one int per row -> (y [B, max n_out], lengths_out int32 [B]).
+    Rows with different rates are grouped: one kernel call per distinct rate on the rows it names; rows already at sr_out are copied."""
+    if not isinstance(wav, torch.Tensor) or not wav.is_cuda:
+        raise ValueError("nele_gan_amd: expected a tensor on the GPU (got %s)" % (wav.device if isinstance(wav, torch.Tensor) else type(wav).__name__))
+    if np.ndim(sr_in) == 0:
+        return resampler(int(sr_in), sr_out, quality, wav.device).apply(wav, lengths, gain=gain)
+    B = wav.shape[0]
+    rates = np.asarray(sr_in, dtype=np.int64).reshape(-1)
+    if rates.shape != (B,):
+        raise ValueError("resample: sr_in must be an int or hold one rate per row (%d)" % B)
+    host = _host_lengths(lengths, B)
+    groups = {int(r): np.nonzero(rates == r)[0] for r in sorted(set(rates.tolist()))}
+    res = {r: resampler(r, sr_out, quality, wav.device) for r in groups}
+    need = max(1, max(res[int(r)].out_len(int(n)) for r, n in zip(rates, host)))
+    y = torch.empty((B, need), dtype=torch.float32, device=wav.device)           # every row is named by one of the calls
+    n_out = torch.empty((B,), dtype=torch.int32, device=wav.device)
+    ln = torch.from_numpy(host.astype(np.int32)).to(wav.device)
+    for r, rows in groups.items():
+        res[r].apply(wav, ln, row_ids=rows, out=(y, n_out), gain=gain)
+    return y, n_out
+
+
+def resample_host(x, sr_in, sr_out=16000, quality='high', gain=1.0, device='cuda'):
+    """One host signal (1-D float32 array) through the device resampler -> float32 array of out_len samples."""
+    x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
+    if len(x) == 0 or int(sr_in) == int(sr_out) and gain == 1.0:
+        return x
+    y, n = resampler(sr_in, sr_out, quality, device).apply(torch.from_numpy(x).to(device).unsqueeze(0), [len(x)], gain=gain)
+    return y[0, :int(n[0])].cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------------ a folder of files at any rate
+def _convert_batch(items, sr_in, sr_out, quality, out_dir, device, workers):
+    """items: [(relative name, float32 signal)] at sr_in -> PCM_16 files under out_dir and their manifest rows.  Samples PCM_16 cannot
+    hold are saturated in the file and counted."""
+    from . import dataio
+    from .ssdrc import pcm16_codes
+    lens = np.asarray([len(x) for _, x in items], dtype=np.int32)
+    rows = np.zeros((len(items), max(1, int(lens.max()))), dtype=np.float32)
+    for k, (_, x) in enumerate(items):
+        rows[k, :len(x)] = x
+    y, n_out = resample(torch.from_numpy(rows).to(device), lens, int(sr_in), sr_out, quality)
+    codes = pcm16_codes(y)
+    clipped = (torch.abs(y) * 32767.0 > 32767.5).sum(dim=1).cpu().numpy()
+    peak = torch.abs(y).amax(dim=1).cpu().numpy()
+    n_host = n_out.cpu().numpy().astype(np.int32)
+    paths = [os.path.join(out_dir, nm) for nm, _ in items]
+    for p in paths:
+        dataio.creatdir(os.path.dirname(p))
+    dataio.write_wav_batch_pcm16(paths, np.ascontiguousarray(codes.to(torch.int16).cpu().numpy()), n_host, sr=int(sr_out), threads=workers)
+    return [(nm, int(sr_in), int(lens[k]), int(n_host[k]), '%.9g' % float(peak[k]), int(clipped[k])) for k, (nm, _) in enumerate(items)]
+
+
+def write_manifest(out_dir, rows):
+    import csv
+    with open(os.path.join(out_dir, 'resample_manifest.csv'), 'w', newline='') as fh:
+        w = csv.writer(fh, lineterminator='\n')
+        w.writerow(MANIFEST_COLUMNS)
+        w.writerows(rows)
+
+
+def resample_corpus(in_dir, out_dir, sr=16000, quality='high', batch=64, workers=8, device='cuda'):
+    """Every .wav under in_dir (any RIFF flavour dataio.read_wav reads, mixed to mono) as PCM_16 at ``sr`` under the same relative path
+    in out_dir, and out_dir/resample_manifest.csv -> manifest rows (sorted by name).  Files are batched by their rate; files already at
+    ``sr`` are rewritten as PCM_16 without filtering."""
+    from . import dataio
+    files = sorted(dataio.get_filepaths(in_dir))
+    dataio.creatdir(out_dir)
+    pending, rows = {}, []
+    for f in files:
+        x, file_sr = dataio.read_wav(f)
+        group = pending.setdefault(int(file_sr), [])
+        group.append((os.path.relpath(f, in_dir), x))
+        if len(group) >= batch:
+            rows += _convert_batch(group, file_sr, sr, quality, out_dir, device, workers)
+            pending[int(file_sr)] = []
+    for file_sr, group in sorted(pending.items()):
+        if group:
+            rows += _convert_batch(group, file_sr, sr, quality, out_dir, device, workers)
+    rows.sort(key=lambda r: r[0])
+    write_manifest(out_dir, rows)
+    return rows
+
+
+def main(argv=None):
+    import argparse
+    from . import dataio
+    ap = argparse.ArgumentParser(prog='python -m nele_gan_amd.resample', description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--in', dest='src', required=True, help='folder of wav files at any sample rate')
+    ap.add_argument('--out', required=True, help='folder the converted files and resample_manifest.csv are written under')
+    ap.add_argument('--sr', type=int, default=16000, help='the rate to convert to')
+    ap.add_argument('--quality', choices=sorted(QUALITIES), default='high')
+    ap.add_argument('--batch', type=int, default=64, help='files of one rate per kernel call')
+    a = ap.parse_args(argv)
+    if a.batch < 1 or a.sr < 1:
+        ap.error('--batch and --sr must be positive')
+    if not dataio.get_filepaths(a.src):
+        ap.error('no wav file under %s' % a.src)
+    rows = resample_corpus(a.src, a.out, sr=a.sr, quality=a.quality, batch=a.batch)
+    print('%d files at %d Hz under %s (%d resampled, %d with clipped samples - see resample_manifest.csv)'
+          % (len(rows), a.sr, a.out.rstrip('/'), sum(1 for r in rows if r[1] != a.sr), sum(1 for r in rows if r[5] != 0)))
+    return 0
+
+
+if __name__ == '__main__':
+    import sys
+    sys.exit(main())

@@ -49,16 +49,21 @@ def rir_name_of(file_name):
 
 
 class RirBank:
-    def __init__(self, rirs, tau=32, resolver=None, device='cuda'):
+    def __init__(self, rirs, tau=32, resolver=None, device='cuda', resample=False):
         """rirs: dict name -> 1-D array, or a folder of 16 kHz wav files (name = file name without '.wav').  resolver(file_name) -> RIR
-        name or None replaces the '#' convention of ``ids``."""
+        name or None replaces the '#' convention of ``ids``.  resample=True: a folder's files at other rates are resampled to 16 kHz on
+        the GPU (resample.py) with gain sr_in / sr_out - a sampled impulse response carries the sampling period, so this keeps the
+        filter's gain; argmax and tau then work on the 16 kHz response.  The default raises on them."""
         if isinstance(rirs, (str, os.PathLike)):
             from . import dataio
             found = {}
             for f in sorted(os.listdir(rirs)):
                 if f.lower().endswith('.wav'):
                     x, sr = dataio.read_wav(os.path.join(rirs, f))
-                    if sr != fs:
+                    if sr != fs and resample:
+                        from .resample import resample_host
+                        x = resample_host(x, sr, fs, gain=sr / float(fs), device=device)
+                    elif sr != fs:
                         raise ValueError('%s: %d Hz, expected %d' % (f, sr, fs))
                     found[f[:-4]] = x
             rirs = found

@@ -1724,6 +1724,7 @@ def main(argv=None):
     ap.add_argument('--mix-seed', type=int, default=0)
     ap.add_argument('--rir', default=None, help="folder of 16 kHz room impulse responses: targets are taken in the room a file's name gives ('<utt>#<rir>#...wav'; "
                                                 "no such RIR: anechoic)")
+    ap.add_argument('--resample', action='store_true', help='resample --noise-pool files and --rir responses that are not at 16 kHz on the GPU instead of stopping on them')
     ap.add_argument('--multienh', choices=('folder', 'ssdrc'), default='folder', help="pre-enhanced examples: the files under Train/MultiEnh (when the folder exists), "
                                                                                        "or 'ssdrc': SSDRC of the clean files computed on the GPU (Train/MultiEnh is not read)")
     from . import quality as _q
@@ -1745,7 +1746,7 @@ def main(argv=None):
     bank = None
     if a.rir:
         from . import room as _room
-        bank = _room.RirBank(a.rir, device='cuda:%d' % local)
+        bank = _room.RirBank(a.rir, device='cuda:%d' % local, resample=a.resample)
     tr = GanTrainer(a.metrics, device='cuda:%d' % local, use_quality=a.quality, quality_scorer=scorer, norm=a.norm, room=bank)
     for m_ in (tr.G, tr.D, tr.D_Qua):
         if m_ is not None:
@@ -1774,7 +1775,7 @@ def main(argv=None):
         if not pool:
             ap.error('--noise-pool: no wav file under ' + a.noise_pool)
         mixer = mixing.NoiseMixer(pool, snrs_db=[float(v) for v in a.snr.split(',')] if a.snr else synth.SNRS_DB, level=a.snr_level, seed=a.mix_seed,
-                                  device='cuda:%d' % local)
+                                  device='cuda:%d' % local, resample=a.resample)
     valid_noise = root + '/Test/Noise/'
     if mixer is not None and not os.path.isdir(valid_noise):
         valid_noise = None                                               # mixed once (epoch 0)
