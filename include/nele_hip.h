@@ -599,6 +599,22 @@ int nele_metric_haspi_quality(const float* x, const float* y, const int* lengths
 int nele_metric_haspi_quality_hl(const float* x, const float* y, const int* lengths, int B, int L, int fs_in, int noise,
                                  unsigned long long seed, double alpha, const double* hl6_host, int itype, void* workspace,
                                  long long workspace_bytes, double* out, int* info, void* stream);
+/* pyhaspi2.py:32-74 hasqi_v2(x, fs, y, fs, HL) alone, as a batched training target split by data dependence like nele_metric_haspi_var:
+ * phase 3 = everything that needs the reference x only (ear model with the BM switch :1155-1250, group-delay shifts :1098-1131, IHC
+ * pass 2 + BM motion, eb_EnvSmooth :674-703 and eb_BMcovary's mean squares :550-657 of x, segment loudness, lag-correlation table),
+ * phase 4 = the chain of y, the cross-covariance against the kept state and the scores (eb_melcor :706-751, eb_AveCovary2 :160-220,
+ * eb_aveSL :1135-1152, eb_SpectDiff :222-251, :69-71); phase 0 = both.  Phase 4 may be repeated after one phase 3.  The HASPI-v1-only
+ * stages (eb_3LevelCovary, the logistic) are not run.  hl6_host: audiogram (host, 6 doubles) or NULL, heard by both signals (itype 2).
+ * noise: 0 none; 1 eb_BMaddnoise (:1091-1095) keyed by (seed, row of the batch) as nele_metric_haspi_quality; 2 keyed by (seed,
+ * utt_ids[b], signal, channel, sample) - a pure function of the utterance id (utt_ids [B] int64, device), like nele_haspi_dither_rows.
+ * The noise of x is added in phase 3 and is part of the kept state.  out [B][7] float64 = {Combined, Nonlin, Linear, CepCorr, BMsync5,
+ * Dloud, Dslope}; info [B][4] as nele_metric_haspi_quality (status bit 1 also for a digitally silent y); status bits 1 / 2 make the
+ * row NaN.  nele_metric_hasqi_clean_sections: what phase 3 leaves, in the form of nele_metric_haspi_clean_sections (12 sections). */
+long long nele_metric_hasqi_workspace_bytes(int B, int L, int fs_in);
+int nele_metric_hasqi_clean_sections(int B, int L, int fs_in, long long* out, int max_sections);
+int nele_metric_hasqi_var(const float* x, const float* y, const int* lengths, int B, int L, int fs_in, const double* hl6_host,
+                          int noise, unsigned long long seed, const long long* utt_ids, void* workspace, long long workspace_bytes,
+                          double* out, int* info, int phase, void* stream);
 
 /* ---- evaluation path (csrc/reverb.hip) ---------------------------------------------------------------------- */
 

@@ -8,6 +8,8 @@
 //   q4  hq_loud_kernel     segment loudness (band average of 10^(dB/20), back in dB) for the silence gates of eb_melcor / the covariance stages
 //   q5  hq_final_kernel    eb_melcor (:706-751), eb_3LevelCovary (:416-547), eb_AveCovary2 (:160-220), eb_aveSL (:1135-1152), eb_SpectDiff
 //                          (:222-251) and the two score formulas, one block per utterance
+// hasqi_v2 alone, split into a reference half and a processed half for use as a training target (nele_metric_hasqi_var, phases 3 / 4),
+// is at the end of this file: q2 / q3 in their MODE 1 / 2 forms, q5 without the HASPI-v1-only stages.
 // The BM motion that reaches eb_BMcovary is bm gain_c gain_SL gain_IHC (:997, :1087, :1076) with gain_SL = (sl + 1e-30) / (c + 1e-30) and
 // gain_IHC = (out + 1e-30) / (sl + 1e-30), c = gain_c |u| the compressed envelope: the product is (out + 1e-30) cos(phase) c / (c + 1e-30)
 // with cos(phase) = bm / |u|.  The filter-bank pass stores cos(phase) (float32, like the envelopes: see hp_env_t) and q1 multiplies it by
@@ -30,7 +32,8 @@ struct QualWs {
     int* qinfo;      // [B][4]            {segments above threshold (eb_melcor), status bits, above threshold (covariance), histogram bins}
     int nseg;        // of the longest row
     unsigned long long seed;
-    int noise;
+    int noise;       // 0 none, 1 keyed by (seed, row of the batch), 2 keyed by (seed, ids[b]): see nele_metric_hasqi_var
+    const long long* ids;   // [B] utterance ids (noise 2), else NULL
 };
 
 __device__ __forceinline__ int hq_nseg(int n24) { return 1 + n24 / HQ_NWIN + (n24 - HQ_NHALF) / HQ_NWIN; }
@@ -65,7 +68,13 @@ __global__ __launch_bounds__(256) void hq_ihc_bm_kernel(HaspiWs ws, QualWs q, in
     hp_env_t* e = ws.env + ((size_t)row * ws.n24p) * HP_NCH + ch;
     float* c = ws.cphi + ((size_t)row * ws.n24p) * HP_NCH + ch;
     const float gn = q.noise ? 1.7782794100389227e-4f : 0.f;          // 10^((-10 - 65) / 20)
-    const unsigned long long base = ((unsigned long long)row * HP_NCH + ch) * (unsigned long long)ws.n24p;
+    // noise 1: counter = position of the sample in the batch's [row][channel][sample] block; noise 2: a pure function of (seed, utterance
+    // id, signal, channel, sample), the same at any row of any batch (as nele_haspi_dither_rows is for the HASPI dither)
+    unsigned long long base = ((unsigned long long)row * HP_NCH + ch) * (unsigned long long)ws.n24p, key = q.seed;
+    if (q.noise == 2) {
+        key = hq_mix(q.seed ^ hq_mix((unsigned long long)q.ids[row >> 1]));
+        base = (unsigned long long)((row & 1) * HP_NCH + ch) << 32;
+    }
     for (int nb = n0; nb < n1; nb += GL_U) {
         float ev[GL_U], cv[GL_U];
 #pragma unroll
@@ -78,7 +87,7 @@ __global__ __launch_bounds__(256) void hq_ihc_bm_kernel(HaspiWs ws, QualWs q, in
             out = out < 0.0 ? 0.0 : out;
             ev[u] = (float)out;
             float bm = (float)((out + 1.0e-30) * (double)cv[u]);
-            if (q.noise) bm += gn * hq_gauss(q.seed, base + (unsigned long long)(nb + u));
+            if (q.noise) bm += gn * hq_gauss(key, base + (unsigned long long)(nb + u));
             cv[u] = bm;
         }
 #pragma unroll
@@ -119,6 +128,11 @@ __global__ void hq_corr_kernel(QualWs q) {
 // 2 LDS reads per 4 multiply-adds.
 #define HQ_XR (HQ_NWIN + 2 * HQ_MAXLAG + 4)
 #define HQ_TROWS 640                 // tile rows: 384 + the largest shift spread inside a group of 8 neighbouring bands that still uses the tile
+// MODE 0: all four arrays in one launch (the one-shot call, and phase 0 of nele_metric_hasqi_var).  The split of HASQI by data dependence:
+// MODE 1 = the reference side (smoothed envelope of x, msx: phase 3), MODE 2 = the processed side (smoothed envelope of y, msy) and the
+// lag loop, which stages the kept BM motion of x through the same shifted tile again (phase 4).  Every array goes through the same
+// statements in every mode, so each sum keeps its order.
+template <int MODE>
 __global__ __launch_bounds__(128) void hq_segment_kernel(HaspiWs ws, QualWs q) {
     __shared__ __attribute__((aligned(16))) float tile[HQ_TROWS][8];
     __shared__ float xs[HQ_XR][8];
@@ -139,7 +153,7 @@ __global__ __launch_bounds__(128) void hq_segment_kernel(HaspiWs ws, QualWs q) {
     const int base = st - smax;                              // first row of the tile (may be negative: zeros, as the reference prepends)
     const int rows = min(N + smax - smin, HQ_TROWS);
     const int roff = smax - sh;                              // the lane's segment starts at tile row roff
-    for (int r = k16; r < HQ_XR; r += 16) xs[r][c] = 0.f;
+    if (MODE != 1) for (int r = k16; r < HQ_XR; r += 16) xs[r][c] = 0.f;    // (the reference side needs the mean square only: no lag loop)
     double res[2] = {0.0, 0.0};
     double MSx = 0.0, MSy = 0.0;
     // the tile rows of array a + 1 are loaded into registers before array a is processed (one global round trip per array and workgroup was
@@ -155,8 +169,11 @@ __global__ __launch_bounds__(128) void hq_segment_kernel(HaspiWs ws, QualWs q) {
             pre[u] = (r < rows && m >= 0 && m < n24) ? *reinterpret_cast<const float4*>(src + (size_t)m * HP_NCH + 4 * (tid & 1)) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     };
-    gload(0);
-    for (int a = 0; a < 4; ++a) {                            // 0, 1: envelopes of x, y; 2, 3: BM motion of x, y
+    constexpr int NA = MODE == 0 ? 4 : (MODE == 1 ? 2 : 3);
+    auto arr = [](int i) { return MODE == 0 ? i : (MODE == 1 ? 2 * i : i + 1); };
+    gload(arr(0));
+    for (int i = 0; i < NA; ++i) {                           // 0, 1: envelopes of x, y; 2, 3: BM motion of x, y
+        const int a = arr(i);
         const float* src = srcof(a);
         __syncthreads();                                     // the previous array's readers are done with the tile
 #pragma unroll
@@ -164,7 +181,7 @@ __global__ __launch_bounds__(128) void hq_segment_kernel(HaspiWs ws, QualWs q) {
             const int r = (tid >> 1) + 64 * u;
             if (r < rows) *reinterpret_cast<float4*>(&tile[r][4 * (tid & 1)]) = pre[u];
         }
-        if (a + 1 < 4) gload(a + 1);
+        if (i + 1 < NA) gload(arr(i + 1));
         __syncthreads();
         double s = 0.0;
         if (a < 2) {
@@ -200,7 +217,7 @@ __global__ __launch_bounds__(128) void hq_segment_kernel(HaspiWs ws, QualWs q) {
                 const int r = roff + k, m = base + r;
                 const float v = r < HQ_TROWS ? tile[r][c] : ((m >= 0 && m < n24) ? src[(size_t)m * HP_NCH + c] : 0.f);
                 const float d = (float)((double)v * wtab[k] - mean);
-                dst[k * 8 + c] = d;
+                if (MODE != 1) dst[k * 8 + c] = d;
                 s2 += (double)d * (double)d;
             }
             part[k16][c][1] = s2;
@@ -210,6 +227,10 @@ __global__ __launch_bounds__(128) void hq_segment_kernel(HaspiWs ws, QualWs q) {
             for (int j = 0; j < 16; ++j) t += part[j][c][1];
             if (a == 2) MSx = t; else MSy = t;
         }
+    }
+    if (MODE == 1) {
+        if (k16 == 0) q.msx[((size_t)b * q.nseg + seg) * HP_NCH + ch] = 2.0 * (MSx * (1.0 / (N == HQ_NWIN ? 143.625 : 71.8125)));
+        return;
     }
     __syncthreads();
     double best = 0.0;
@@ -240,7 +261,8 @@ __global__ __launch_bounds__(128) void hq_segment_kernel(HaspiWs ws, QualWs q) {
         double cv = (MSx > 1.0e-30 && MSy > 1.0e-30) ? Mxy / sqrt(MSx * MSy) : 0.0;
         cv = fmin(fmax(cv, 0.0), 1.0);
         const size_t o = ((size_t)b * q.nseg + seg) * HP_NCH + ch;
-        q.cov[o] = cv; q.msx[o] = 2.0 * MSx; q.msy[o] = 2.0 * MSy;
+        q.cov[o] = cv; q.msy[o] = 2.0 * MSy;
+        if (MODE == 0) q.msx[o] = 2.0 * MSx;
     }
 }
 
@@ -270,11 +292,16 @@ __device__ __forceinline__ double hq_block_sum(double v, double* sh4) {
 // ---- q5: grid B, block 256.  out [B][HQ_NOUT] = {HASPI v1 Intel, CepCorr, cov3 low / mid / high, HASQI Combined, Nonlin, Linear, BMsync5,
 // Dloud, Dslope, avecov}.  Where the reference raises ('Signal below threshold', pyhaspi2.py:723-724, :427-428; eb_AveCovary2's (0, 0)
 // return makes hasqi_v2 fail at syncov[4]) the values are NaN and the status bits say which: 1 eb_melcor, 2 the covariance stages.
+// V1 = false: hasqi_v2 alone (nele_metric_hasqi_var): no loudness histogram, no three-level covariance, no logistic;
+// out [B][HS_NOUT] = {Combined, Nonlin, Linear, CepCorr, BMsync5, Dloud, Dslope}.  There a processed signal that is digitally silent
+// (rms 0: the reference divides by it, pyhaspi2.py:81-84, and returns NaN scores under numpy warnings) also sets status bit 1.
+#define HS_NOUT 7
+template <bool V1>
 __global__ __launch_bounds__(256) void hq_final_kernel(HaspiWs ws, QualWs q, double alpha, double* __restrict__ out) {
     __shared__ double cepm[HP_NCH][HP_NBASIS];
     __shared__ double sh4[4];
     __shared__ double accs[8][HP_NCH][8];
-    __shared__ int hist[HQ_MAXBINS];
+    __shared__ int hist[V1 ? HQ_MAXBINS : 1];                // the loudness histogram is eb_3LevelCovary's: hasqi_v2 alone holds no LDS for it
     __shared__ double edges[2];
     __shared__ double SL[2][HP_NCH];
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -361,39 +388,42 @@ __global__ __launch_bounds__(256) void hq_final_kernel(HaspiWs ws, QualWs q, dou
         status |= 2;
     } else {
         nbins = (int)ceil(((hi + 0.5) - lo) / 0.5);                     // len(np.arange(dBmin, dBmax + 0.5, 0.5))
-        if (nbins > HQ_MAXBINS) { status |= 4; nbins = HQ_MAXBINS; }
-        for (int i = tid; i < nbins; i += 256) hist[i] = 0;
-        __syncthreads();
-        // np.histogram over the mid-points between the bin centres lo + 0.5 i: bin i = [edge(i), edge(i + 1)), open at both ends
-        for (int seg = tid; seg < nseg; seg += 256) {
-            const double v = lc[seg];
-            if (!(v > thr)) continue;
-            int i = (int)floor((v - lo) / 0.5 + 0.5);
-            i = max(0, min(i, nbins - 1));
-            while (i < nbins - 1 && v >= ((lo + 0.5 * (double)i) + (lo + 0.5 * (double)(i + 1))) / 2.0) ++i;
-            while (i > 0 && v < ((lo + 0.5 * (double)(i - 1)) + (lo + 0.5 * (double)i)) / 2.0) --i;
-            atomicAdd(&hist[i], 1);
-        }
-        __syncthreads();
-        if (tid == 0) {                                                  // pyhaspi2.py:459-472
-            double e0 = 0.0, e1 = 0.0, cum = 0.0;
-            for (int n = 0; n < nbins; ++n) {
-                cum += (double)hist[n];
-                const double xc = cum / ncov;
-                if (xc < 0.333) e0 = lo + 0.5 * (double)n;
-                if (xc < 0.667) e1 = lo + 0.5 * (double)n;
+        double e0 = 0.0, e1 = 0.0;
+        if (V1) {                                                        // loudness thirds: eb_3LevelCovary only (pyhaspi2.py:440-472)
+            if (nbins > HQ_MAXBINS) { status |= 4; nbins = HQ_MAXBINS; }
+            for (int i = tid; i < nbins; i += 256) hist[i] = 0;
+            __syncthreads();
+            // np.histogram over the mid-points between the bin centres lo + 0.5 i: bin i = [edge(i), edge(i + 1)), open at both ends
+            for (int seg = tid; seg < nseg; seg += 256) {
+                const double v = lc[seg];
+                if (!(v > thr)) continue;
+                int i = (int)floor((v - lo) / 0.5 + 0.5);
+                i = max(0, min(i, nbins - 1));
+                while (i < nbins - 1 && v >= ((lo + 0.5 * (double)i) + (lo + 0.5 * (double)(i + 1))) / 2.0) ++i;
+                while (i > 0 && v < ((lo + 0.5 * (double)(i - 1)) + (lo + 0.5 * (double)i)) / 2.0) --i;
+                atomicAdd(&hist[i], 1);
             }
-            edges[0] = e0; edges[1] = e1;
+            __syncthreads();
+            if (tid == 0) {                                                  // pyhaspi2.py:459-472
+                double t0 = 0.0, t1 = 0.0, cum = 0.0;
+                for (int n = 0; n < nbins; ++n) {
+                    cum += (double)hist[n];
+                    const double xc = cum / ncov;
+                    if (xc < 0.333) t0 = lo + 0.5 * (double)n;
+                    if (xc < 0.667) t1 = lo + 0.5 * (double)n;
+                }
+                edges[0] = t0; edges[1] = t1;
+            }
+            __syncthreads();
+            e0 = edges[0]; e1 = edges[1];
         }
-        __syncthreads();
-        const double e0 = edges[0], e1 = edges[1];
         // per band: sums of weight * covariance and of the weights, by loudness third
         const int sg = tid >> 5, ch = tid & 31;
         double S[3] = {0, 0, 0}, W[3] = {0, 0, 0};
         for (int seg = sg; seg < nseg; seg += 8) {
             const double v = lc[seg];
             if (!(v > thr)) continue;
-            const int g = v < e0 ? 0 : (v < e1 ? 1 : 2);
+            const int g = !V1 ? 0 : (v < e0 ? 0 : (v < e1 ? 1 : 2));       // hasqi_v2 alone: one group (eb_AveCovary2 takes every cell)
             const size_t o = ((size_t)b * q.nseg + seg) * HP_NCH + ch;
             const bool w = sqrt(q.msx[o]) > thr;
             const double cv = q.cov[o];
@@ -480,6 +510,18 @@ __global__ __launch_bounds__(256) void hq_final_kernel(HaspiWs ws, QualWs q, dou
         Dloud = fmin(fmax(1.0 - dl / 2.5, 0.0), 1.0);
         Dslope = fmin(fmax(1.0 - dsl, 0.0), 1.0);
     }
+    if (!V1) {
+        if (!(ws.rinfo[(size_t)(2 * b + 1) * 4] > 0.f)) status |= 1;
+        if (tid == 0) {
+            const bool bad = (status & 3) != 0;
+            const double Nonlin = (CepCorr * CepCorr) * sync5, Linear = 0.579 * Dloud + 0.421 * Dslope;             // pyhaspi2.py:69-71
+            const double v[HS_NOUT] = {Nonlin * Linear, Nonlin, Linear, CepCorr, sync5, Dloud, Dslope};
+            for (int j = 0; j < HS_NOUT; ++j) out[(size_t)b * HS_NOUT + j] = bad ? NaN : v[j];
+            int* qi = q.qinfo + 4 * b;
+            qi[0] = n_mel; qi[1] = status; qi[2] = n_cov; qi[3] = nbins;
+        }
+        return;
+    }
     if (tid == 0) {
         double* o = out + (size_t)b * HQ_NOUT;
         const double arg = -9.047 + 14.816 * CepCorr + ((0.0 * cov3[0] + 0.0 * cov3[1]) + 4.616 * cov3[2]);     // pyhaspi2.py:147-150
@@ -553,7 +595,7 @@ static int haspi_quality_impl(const float* x, const float* y, const int* lengths
     QualWs q;
     quality_layout(B, L, fs_in, &ws, &q, (char*)workspace);
     ws.lens = lengths;
-    q.seed = seed; q.noise = noise;
+    q.seed = seed; q.noise = noise ? 1 : 0; q.ids = nullptr;
     hipStream_t s = as_stream(stream);
     hipLaunchKernelGGL(haspi_loss_kernel, dim3(1), dim3(64), 0, s, ws, hl);
     if (fs_in != 24000) haspi_build_window(ws, s);
@@ -561,10 +603,112 @@ static int haspi_quality_impl(const float* x, const float* y, const int* lengths
     const int rows = 2 * B;
     hipLaunchKernelGGL(hq_ihc_bm_kernel, dim3(((ws.n24p + GL_N - 1) / GL_N + 7) / 8, rows), dim3(256), 0, s, ws, q, 0, 2);
     hipLaunchKernelGGL(hq_corr_kernel, dim3(1), dim3(128), 0, s, q);
-    hipLaunchKernelGGL(hq_segment_kernel, dim3(q.nseg, 4, B), dim3(128), 0, s, ws, q);
+    hipLaunchKernelGGL(hq_segment_kernel<0>, dim3(q.nseg, 4, B), dim3(128), 0, s, ws, q);
     hipLaunchKernelGGL(hq_loud_kernel, dim3((q.nseg + 63) / 64, B), dim3(64), 0, s, ws, q);
-    hipLaunchKernelGGL(hq_final_kernel, dim3(B), dim3(256), 0, s, ws, q, alpha, out);
+    hipLaunchKernelGGL(hq_final_kernel<true>, dim3(B), dim3(256), 0, s, ws, q, alpha, out);
     if (info_out) (void)hipMemcpyAsync(info_out, q.qinfo, sizeof(int) * 4 * (size_t)B, hipMemcpyDeviceToDevice, s);
     NELE_CHECK_LAUNCH("nele_metric_haspi_quality");
+    return NELE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- HASQI v2 as a batched training target
+// hasqi_v2(x, fs, y, fs, HL) alone (pyhaspi2.py:32-74), split by data dependence like nele_metric_haspi_var:
+//   phase 3  everything that needs x only: ear model of the reference with the BM switch (eb_EarModel :1155-1250, signal 0), group-delay
+//            shifts (:1098-1131), IHC pass 2 + BM motion (+ eb_BMaddnoise :1091-1095 of signal 0), eb_EnvSmooth of x (:674-703), the
+//            reference-side mean squares of eb_BMcovary (:550-657), the segment loudness of the silence gates, the lag-correlation table
+//   phase 4  the chain of y, eb_EnvSmooth of y, the cross-covariance against the kept BM motion of x, eb_melcor (:706-751),
+//            eb_AveCovary2 (:160-220), eb_aveSL (:1135-1152), eb_SpectDiff (:222-251) and the score (:69-71)
+//   phase 0  phase 3 and phase 4 on the same workspace, as the one-shot call's launches: both signals per launch, one segment launch
+// Phase 4 may be repeated after one phase 3 (several processed versions of one reference).  The workspace is the one-shot call's.
+extern "C" long long nele_metric_hasqi_workspace_bytes(int B, int L, int fs_in) {
+    return (long long)quality_layout(B, L, fs_in, nullptr, nullptr, nullptr);
+}
+
+// What phase 3 leaves for phase 4, as {offset, stride, bytes} ranges (see nele_metric_haspi_clean_sections): the BM motion of x
+// (float32 [n24p][32], nearly all of it), its smoothed envelope, msx, the two segment-loudness rows, the shifts, the adjusted
+// bandwidths and the sum-of-squares partials of x that eb_aveSL reads, and the constant tables.  The per-sample envelope of x is not
+// part of it.  With noise 1 / 2 the noise of signal 0 is inside the kept BM motion.
+extern "C" int nele_metric_hasqi_clean_sections(int B, int L, int fs_in, long long* out, int max_sections) {
+    NELE_CHECK_ARG(B > 0 && out && max_sections >= 12, "nele_metric_hasqi_clean_sections: bad arguments (12 sections)");
+    NELE_CHECK_ARG(fs_in >= 1000 && fs_in <= 24000 && L >= 2400, "nele_metric_hasqi_clean_sections: bad signal geometry");
+    HaspiWs w;
+    QualWs q;
+    char* base = reinterpret_cast<char*>((uintptr_t)1 << 20);
+    quality_layout(B, L, fs_in, &w, &q, base);
+    int k = 0;
+    auto put = [&](const void* p, long long stride, long long bytes) {
+        out[3 * k] = (long long)(reinterpret_cast<const char*>(p) - base); out[3 * k + 1] = stride; out[3 * k + 2] = bytes; ++k;
+    };
+    const size_t ns = (size_t)q.nseg, nc = (size_t)w.nchunk;
+    put(w.win, 0, sizeof(double) * (HP_NWIN_AL + RS3_TAB));
+    put(w.pmat, 0, sizeof(double) * HP_NCH * 16);                                   // entry 0: the control bank (per channel only)
+    put(w.pihc, 0, sizeof(double) * 4);
+    put(q.corr, 0, sizeof(double) * 128);
+    put(w.bw, sizeof(double) * 2 * HP_NCH, sizeof(double) * HP_NCH);                // reference half of each [2][..] block, here and below
+    put(w.shift, sizeof(int) * HP_NCH, sizeof(int) * HP_NCH);
+    put(w.ssp, sizeof(double) * 2 * nc * HP_NCH, sizeof(double) * nc * HP_NCH);
+    put(w.sse, sizeof(double) * 2 * nc * HP_NCH, sizeof(double) * nc * HP_NCH);
+    put(w.cphi, sizeof(float) * 2 * (size_t)w.n24p * HP_NCH, sizeof(float) * (size_t)w.n24p * HP_NCH);
+    put(q.sm, sizeof(double) * 2 * ns * HP_NCH, sizeof(double) * ns * HP_NCH);
+    put(q.msx, sizeof(double) * ns * HP_NCH, sizeof(double) * ns * HP_NCH);
+    put(q.segl, sizeof(double) * 2 * ns, sizeof(double) * 2 * ns);
+    return k;
+}
+
+// x, y [B][L] float32 (reference, processed; x may be NULL in phase 4, y in phase 3); lengths [B] or NULL; hl6_host: audiogram (HOST
+// pointer, 6 doubles) or NULL = normal hearing, heard by both signals (itype 2 of
+// nele_metric_haspi_quality_hl, the only one hasqi_v2 uses: pyhaspi2.py:41-43);
+// noise: 0 none, 1 eb_BMaddnoise keyed by (seed, row of the batch) as nele_metric_haspi_quality does, 2 keyed by (seed, utt_ids[b],
+// signal, channel, sample): an utterance's score then does not depend on its row, its batch-mates or the rank that scores it.
+// utt_ids [B] int64 on the device (noise 2).  out [B][7] float64 = {Combined, Nonlin, Linear, CepCorr, BMsync5, Dloud, Dslope} (phases 0, 4),
+// info_out [B][4] int or NULL = {segments above threshold (eb_melcor), status, above threshold (covariance), loudness bins}; status
+// bit 1: eb_melcor's 'Signal below threshold' (pyhaspi2.py:723-724) or a digitally silent y, bit 2: eb_AveCovary2 has no segment
+// (hasqi_v2 fails at :54); either makes the row's seven values NaN.
+extern "C" int nele_metric_hasqi_var(const float* x, const float* y, const int* lengths, int B, int L, int fs_in, const double* hl6_host,
+                                     int noise, unsigned long long seed, const long long* utt_ids, void* workspace, long long workspace_bytes,
+                                     double* out, int* info_out, int phase, void* stream) {
+    NELE_CHECK_ARG(workspace && B > 0 && (phase == 0 || phase == 3 || phase == 4), "nele_metric_hasqi_var: bad arguments");
+    NELE_CHECK_ARG((x || phase == 4) && (y || phase == 3) && (out || phase == 3), "nele_metric_hasqi_var: missing signal / output for phase %d", phase);
+    NELE_CHECK_ARG(noise >= 0 && noise <= 2 && (noise != 2 || utt_ids), "nele_metric_hasqi_var: noise must be 0, 1 or 2 (2 needs utt_ids)");
+    HpHL hl;
+    { const int st_ = haspi_hl_table(hl6_host, 2, &hl); if (st_) return st_; }
+    NELE_CHECK_ARG(fs_in >= 1000 && fs_in <= 24000, "nele_metric_hasqi_var: fs must be in [1000, 24000] Hz (got %d; the reference has no downsampler)", fs_in);
+    if (L < 2400) return nele_set_error(NELE_ERR_SIGNAL, "nele_metric_hasqi_var: L=%d too short", L);
+    if (workspace_bytes < nele_metric_hasqi_workspace_bytes(B, L, fs_in))
+        return nele_set_error(NELE_ERR_WORKSPACE, "nele_metric_hasqi_var: workspace too small");
+    HaspiWs ws;
+    QualWs q;
+    quality_layout(B, L, fs_in, &ws, &q, (char*)workspace);
+    ws.lens = lengths;
+    q.seed = seed; q.noise = noise; q.ids = utt_ids;
+    hipStream_t s = as_stream(stream);
+    const dim3 igrid(((ws.n24p + GL_N - 1) / GL_N + 7) / 8, B), sgrid(q.nseg, 4, B), lgrid((q.nseg + 63) / 64, B);
+    hipLaunchKernelGGL(haspi_loss_kernel, dim3(1), dim3(64), 0, s, ws, hl);
+    if (phase != 4) {
+        if (fs_in != 24000) haspi_build_window(ws, s);
+        hipLaunchKernelGGL(hq_corr_kernel, dim3(1), dim3(128), 0, s, q);
+    }
+    if (phase == 0) {
+        // both signals through every launch together, and the segment kernel fused: the launch sequence of the one-shot call (every kernel
+        // works row by row, so a row's values are those of its own phase 3 / phase 4 launches: tests/test_hasqi_target_gpu.py, bit for bit)
+        haspi_chain(x, y, B, L, fs_in, ws, 0, 2, s, true);
+        hipLaunchKernelGGL(hq_ihc_bm_kernel, dim3(igrid.x, 2 * B), dim3(256), 0, s, ws, q, 0, 2);
+        hipLaunchKernelGGL(hq_segment_kernel<0>, sgrid, dim3(128), 0, s, ws, q);
+        hipLaunchKernelGGL(hq_loud_kernel, lgrid, dim3(64), 0, s, ws, q);
+    } else if (phase == 3) {
+        haspi_chain(x, y, B, L, fs_in, ws, 0, 1, s, true);
+        hipLaunchKernelGGL(hq_ihc_bm_kernel, igrid, dim3(256), 0, s, ws, q, 0, 1);
+        hipLaunchKernelGGL(hq_segment_kernel<1>, sgrid, dim3(128), 0, s, ws, q);
+        hipLaunchKernelGGL(hq_loud_kernel, lgrid, dim3(64), 0, s, ws, q);
+    } else {
+        haspi_chain(x, y, B, L, fs_in, ws, 1, 1, s, true);
+        hipLaunchKernelGGL(hq_ihc_bm_kernel, igrid, dim3(256), 0, s, ws, q, 1, 1);
+        hipLaunchKernelGGL(hq_segment_kernel<2>, sgrid, dim3(128), 0, s, ws, q);
+    }
+    if (phase != 3) {
+        hipLaunchKernelGGL((hq_final_kernel<false>), dim3(B), dim3(256), 0, s, ws, q, -1.0, out);
+        if (info_out) (void)hipMemcpyAsync(info_out, q.qinfo, sizeof(int) * 4 * (size_t)B, hipMemcpyDeviceToDevice, s);
+    }
+    NELE_CHECK_LAUNCH("nele_metric_hasqi_var");
     return NELE_OK;
 }

@@ -267,6 +267,41 @@ def score_enhanced(clean_path, noise_path, enhanced_names, groups=('Cafeteria', 
     return res
 
 
+def score_quality(clean_path, enhanced_names, groups=('Cafeteria', 'AirportAnnouncement'), batch=32, out=None):
+    """HASQI v2 (pyhaspi2.py:32-74) of (clean file, enhanced file) per noise group, both cut to the shorter one (what the reference's
+    PESQ / ViSQOL calls compare: no listener's noise): metrics.batch_hasqi over batches of ``batch`` files, with the reference's
+    basilar-membrane noise drawn per file (position in ``enhanced_names``).  The quality figure this build has without the two external
+    programs, and what a D_Qua trained with ``--quality-targets hasqi`` predicts two terms of.
+    -> {group: {'hasqi', 'nonlin', 'linear': mean over the files with a defined score, 'files': n}}; one report line per group."""
+    import sys
+    import numpy as np
+    import torch
+    from . import dataio
+    from . import metrics as mt
+    out = sys.stdout if out is None else out
+    res = {}
+    for g in (tuple(groups) if groups else ('',)):
+        names = [(i, x) for i, x in enumerate(enhanced_names) if g in x]
+        if not names:
+            continue
+        rows = []
+        for k in range(0, len(names), batch):
+            pairs = []
+            for _i, f in names[k:k + batch]:
+                c, e = dataio.load(clean_path + dataio.wave_name_of(f) + '.wav', sr=16000)[0], dataio.load(f, sr=16000)[0]
+                n = min(len(c), len(e))
+                pairs.append((c[:n], e[:n]))
+            (c, lens), (e, _) = (dataio.pad_batch([p_[j] for p_ in pairs]) for j in range(2))
+            rows.append(mt.batch_hasqi(c, e, 16000, lengths=torch.from_numpy(lens), noise='utterance', seed=0,
+                                       utt_ids=[i for i, _f in names[k:k + batch]])[:, :3].cpu().numpy())
+        rows = np.concatenate(rows)
+        ok = rows[~np.isnan(rows[:, 0])]
+        m = ok.mean(axis=0) if len(ok) else np.full(3, np.nan)
+        res[g] = {'hasqi': float(m[0]), 'nonlin': float(m[1]), 'linear': float(m[2]), 'files': int(len(ok))}
+        out.write('%s:\nHASQI is %.3f, Nonlin is %.3f, Linear is %.3f\n\n======\n' % (g, m[0], m[1], m[2]))
+    return res
+
+
 def score_rooms(clean_path, noise_path, enhanced_names, bank, batch=32, metrics=('siib', 'haspi', 'estoi'), out=None):
     """The scores of the enhanced files in the room each file's name gives (room.RirBank.ids: '<utt>#<rir>#...wav'; no such RIR:
     anechoic), eval_metrics.py:100-186 per utterance: eval_metrics.evaluate_rooms over batches of ``batch`` files.
@@ -343,6 +378,8 @@ def main(argv=None):
     ap.add_argument('--precision', choices=('bf16', 'bf16x3', 'f32'), default='bf16')
     ap.add_argument('--norm', choices=M.NORMS, default=None, help="energy normalisation (default: what the checkpoint records, else 'utterance'); 'prefix' = the causal form the real-time path emits")
     ap.add_argument('--score', action='store_true', help='SIIB / HASPI / ESTOI (PESQ / ViSQOL when registered) of the written files')
+    ap.add_argument('--score-quality', action='store_true', help='with --score: also HASQI v2 Combined / Nonlin / Linear of (clean, enhanced), computed on the GPU '
+                                                                 '(no external program)')
     ap.add_argument('--groups', default='Cafeteria,AirportAnnouncement', help='noise types (substrings of the file names) reported separately; empty = all files together')
     ap.add_argument('--rir', default=None, help="with --score: folder of 16 kHz room impulse responses; the files are also scored in the room their name gives "
                                                 "('<utt>#<rir>#...wav'), reported per RIR")
@@ -353,6 +390,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.baseline and not a.score:
         ap.error('--baseline needs --score')
+    if a.score_quality and not a.score:
+        ap.error('--score-quality needs --score')
     _q.backends_from_cli(a)
     e = Enhancer(a.chkpt, norm=a.norm)
     e.G.precision = a.precision
@@ -364,6 +403,8 @@ def main(argv=None):
         groups = tuple(g for g in a.groups.split(',') if g)
         bank = None
         score_enhanced(a.clean.rstrip('/') + '/', noise, out, groups=groups)
+        if a.score_quality:
+            score_quality(a.clean.rstrip('/') + '/', out, groups=groups, batch=a.batch)
         if a.rir:
             from . import room
             bank = room.RirBank(a.rir)

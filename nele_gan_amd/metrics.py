@@ -6,6 +6,7 @@ here: one batched launch over utterances resident in HBM).
     SIIB_Wrapper[_raw]_harvard(x, y, fs)    intel.py:57-100
     HASPI_Wrapper[_raw]_harvard(x, y, fs)   intel.py:108-114
     batch_estoi / batch_siib / batch_haspi (clean[B,L], degraded[B,L]) -> (raw[B], mapped[B])
+    batch_hasqi / HasqiSplit (reference[B,L], processed[B,L]) -> float64 [B,7]: hasqi_v2 (pyhaspi2.py:32-74) as a training target
 
 x is the clean reference, y the degraded signal (enhanced + noise, audio_util.py:139-141).
 """
@@ -53,6 +54,13 @@ _lib._SIGS['nele_metric_haspi_quality'] = _lib.lib.nele_metric_haspi_quality.arg
 declare('nele_metric_haspi_quality_hl', [_P, _P, _P, c_int, c_int, c_int, c_int, ctypes.c_ulonglong, ctypes.c_double, ctypes.POINTER(ctypes.c_double), c_int, _P,
                                          c_longlong, _P, _P, _P])
 _lib._SIGS['nele_metric_haspi_quality_hl'] = _lib.lib.nele_metric_haspi_quality_hl.argtypes
+_lib.lib.nele_metric_hasqi_workspace_bytes.argtypes = [c_int, c_int, c_int]
+_lib.lib.nele_metric_hasqi_workspace_bytes.restype = c_longlong
+_lib._SIGS['nele_metric_hasqi_workspace_bytes'] = _lib.lib.nele_metric_hasqi_workspace_bytes.argtypes
+declare('nele_metric_hasqi_var', [_P, _P, _P, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_double), c_int, ctypes.c_ulonglong, _P, _P, c_longlong, _P, _P, c_int, _P])
+_lib._SIGS['nele_metric_hasqi_var'] = _lib.lib.nele_metric_hasqi_var.argtypes
+declare('nele_metric_hasqi_clean_sections', [c_int, c_int, c_int, ctypes.POINTER(c_longlong), c_int])
+_lib._SIGS['nele_metric_hasqi_clean_sections'] = _lib.lib.nele_metric_hasqi_clean_sections.argtypes
 _lib.lib.nele_metric_haspi_nsub.argtypes = [c_int, c_int]
 _lib.lib.nele_metric_haspi_nsub.restype = c_int
 _lib._SIGS['nele_metric_haspi_nsub'] = _lib.lib.nele_metric_haspi_nsub.argtypes
@@ -126,6 +134,8 @@ class CleanStateCache:
         buf = (c_longlong * (3 * 24))()
         if kind == 'siib':
             n = _lib.lib.nele_metric_siib_clean_sections(int(B), int(L), buf, 24)
+        elif kind == 'hasqi':
+            n = _lib.lib.nele_metric_hasqi_clean_sections(int(B), int(L), int(fs), buf, 24)
         else:
             n = _lib.lib.nele_metric_haspi_clean_sections(int(B), int(L), int(fs), buf, 24)
         if n < 0:
@@ -580,6 +590,96 @@ def batch_haspi_quality(x, y, fs=16000, lengths=None, noise=True, seed=None, alp
         call('nele_metric_haspi_quality_hl', ptr(x), ptr(y), ptr(lengths), B, L, int(fs), int(bool(noise)), int(seed), float(alpha), hl, int(itype),
              ptr(ws), ws.numel(), ptr(out), ptr(info), stream())
     return (out, info) if return_info else out
+
+
+HASQI_FIELDS = ('Combined', 'Nonlin', 'Linear', 'CepCorr', 'BMsync5', 'Dloud', 'Dslope')
+QUALITY_TARGET_FIELDS = ('Nonlin', 'Linear')          # D_Qua's two targets when it is trained on HASQI (quality.HasqiScorer)
+_HASQI_NOISE = {False: 0, None: 0, 0: 0, True: 1, 1: 1, 'row': 1, 'utterance': 2, 2: 2}
+
+
+class HasqiSplit:
+    """HASQI v2 (pyhaspi2.py:32-74) of a batch, split by data dependence like HaspiSplit: clean_part() runs everything that needs the
+    reference x alone (its ear model with the basilar-membrane motion, group-delay shifts, smoothed envelope, mean squares, segment
+    loudness) and degraded_part(y) - any number of times - the chain of y, the cross-covariance and the scores: float64 [B, 7]
+    (HASQI_FIELDS; a new tensor per call), status in ``info`` [B, 4].
+    noise: False | True (eb_BMaddnoise keyed by (seed, row of the batch)) | 'utterance' (keyed by (seed, utt_ids[b]): an utterance is
+    scored alike at any row of any batch on any rank).  The noise of x is part of what clean_part() leaves.  HL: audiogram heard by both
+    signals.  Own workspace: the clean-signal state must survive until degraded_part()."""
+
+    def __init__(self, x, fs=16000, lengths=None, noise=False, seed=0, utt_ids=None, HL=None, owner=None, ws_kind='hasqi_split'):
+        self.x = x.contiguous().float()
+        self.fs = int(fs)
+        self.owner = owner
+        if noise not in _HASQI_NOISE:
+            raise ValueError("HASQI: noise must be False, True or 'utterance'")
+        self.noise, self.seed, self.HL = _HASQI_NOISE[noise], int(seed) & 0xFFFFFFFFFFFFFFFF, HL
+        self.hl = _hl6(HL)
+        B, L = self.x.shape
+        self.utt_ids = None
+        if self.noise == 2:
+            if utt_ids is None:
+                raise ValueError("HASQI: noise='utterance' needs utt_ids")
+            self.utt_ids = torch.as_tensor(utt_ids).to(device=self.x.device, dtype=torch.int64).contiguous()
+            if tuple(self.utt_ids.shape) != (B,):
+                raise ValueError('HASQI: utt_ids must hold one id per row')
+        self.lengths = _lens(lengths, self.x.device)
+        self.ws = _workspace(ws_kind, _lib.lib.nele_metric_hasqi_workspace_bytes(B, L, self.fs), self.x.device, cache=owner)
+        self.info = torch.zeros((B, 4), dtype=torch.int32, device=self.x.device)
+
+    def _call(self, y, phase, out=None):
+        B, L = self.x.shape
+        call('nele_metric_hasqi_var', ptr(self.x), ptr(y), ptr(self.lengths), B, L, self.fs, self.hl, self.noise, self.seed, ptr(self.utt_ids),
+             ptr(self.ws), self.ws.numel(), ptr(out), ptr(self.info), phase, stream())
+
+    def _geom(self):
+        B, L = self.x.shape
+        # a cached state is valid for the noise it holds: none, or the per-utterance one of this seed; row-keyed noise is never cached
+        return ('L', L, 'fs', self.fs, 'noise', (self.noise, self.seed) if self.noise else 0, 'HL', None if self.hl is None else tuple(self.hl))
+
+    def clean_part(self, cache=None, keys=None):
+        """cache / keys: as SiibSplit.clean_part (CleanStateCache kind 'hasqi')."""
+        if cache is None or keys is None or self.noise == 1:
+            self._call(None, 3)
+            return False
+        B, L = self.x.shape
+        geom = self._geom()
+        full = list(keys)
+        slots = cache.lookup('hasqi', geom, full)
+        if slots is not None:
+            cache.restore('hasqi', geom, self.ws, B, L, self.fs, slots)
+            return True
+        rows = cache.missing('hasqi', geom, full)
+        if rows is not None:                                      # (see SiibSplit.clean_part: the unknown utterances as a batch of their own)
+            sub = HasqiSplit(self.x[rows], fs=self.fs, lengths=None if self.lengths is None else self.lengths[rows], noise=self.noise, seed=self.seed,
+                             utt_ids=None if self.utt_ids is None else self.utt_ids[rows], HL=self.HL, owner=self.owner, ws_kind='hasqi_split_sub')
+            sub._call(None, 3)
+            if cache.store('hasqi', geom, sub.ws, len(rows), L, self.fs, [full[i] for i in rows]):
+                slots = cache.lookup('hasqi', geom, full, count=False)
+                if slots is not None:
+                    cache.partial += 1
+                    cache.restore('hasqi', geom, self.ws, B, L, self.fs, slots)
+                    return True
+        self._call(None, 3)
+        cache.store('hasqi', geom, self.ws, B, L, self.fs, full)
+        return False
+
+    def degraded_part(self, y):
+        assert y.shape == self.x.shape
+        self.y = y.contiguous().float()
+        out = torch.empty((self.x.shape[0], len(HASQI_FIELDS)), dtype=torch.float64, device=self.x.device)
+        self._call(self.y, 4, out)
+        return out
+
+
+def batch_hasqi(x, y, fs=16000, lengths=None, noise=False, seed=0, utt_ids=None, HL=None, return_info=False):
+    """reference x [B,L], processed y [B,L] -> float64 [B, 7] (HASQI_FIELDS): hasqi_v2 (pyhaspi2.py:32-74) alone, one launch chain
+    (phase 0 of nele_metric_hasqi_var).  noise / seed / utt_ids / HL: see HasqiSplit.  info [B,4] = (segments above threshold of
+    eb_melcor, status, of the covariance, loudness bins); status bits 1 / 2 (signal below threshold) make a row NaN."""
+    x, y, _ = _pair(x, y)
+    sp = HasqiSplit(x, fs=fs, lengths=lengths, noise=noise, seed=seed, utt_ids=utt_ids, HL=HL, ws_kind='hasqi')
+    out = torch.empty((x.shape[0], len(HASQI_FIELDS)), dtype=torch.float64, device=x.device)
+    sp._call(y, 0, out)
+    return (out, sp.info) if return_info else out
 
 
 def _quality_checked(x, fx, y, fy, alpha=-1.0, HL=None, itype=0):

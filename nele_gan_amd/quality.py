@@ -16,6 +16,11 @@ gets the reference's D_Qua training with two lines (INTEGRATION.md section 2b'''
 Nothing here runs on the GPU: both programs are host programs, as in the reference; the trainer calls ``Scorer`` on a background thread
 while the next batch's kernels are enqueued (train_nele.py:323-324, 336-337, 216-222 in ``run_epoch``).
 A call without a registered program raises - there is no stand-in score.
+
+``HasqiScorer`` is the alternative that needs neither program: D_Qua trained on the Nonlin and Linear terms of HASQI v2 (pyhaspi2.py:32-74),
+the one quality metric of the reference's own code base, computed on the GPU (metrics.HasqiSplit) and pinned to the reference's runs
+(tests/golden/haspi_quality.npz).  PESQ and ViSQOL stay unbuilt; a D_Qua trained on HASQI targets is a different model from the
+reference's, and its checkpoints say so ('quality-targets').
 """
 import concurrent.futures as cf
 import csv
@@ -287,3 +292,43 @@ class Scorer:
     def map(raw):
         raw = np.asarray(raw, dtype=np.float64)
         return np.stack([mapping_PESQ_harvard(raw[:, 0]), mapping_VISQOL(raw[:, 1])], axis=1)
+
+
+# ------------------------------------------------------------------------------------------------ HASQI targets on the device
+def utterance_ids(keys):
+    """One int64 id per utterance key (file name, path, tuple ...): the first 8 bytes of BLAKE2b of the key's repr - the same in every
+    process, epoch and rank, unlike hash().  What keys the per-utterance basilar-membrane noise of a batch that brings no 'ids'."""
+    import hashlib
+    return np.array([int.from_bytes(hashlib.blake2b(repr(k).encode('utf-8'), digest_size=8).digest(), 'little', signed=True) for k in keys], dtype=np.int64)
+
+
+class HasqiScorer:
+    """D_Qua's two targets from HASQI v2 of (clean, example) on the GPU: the Nonlin and Linear terms (metrics.QUALITY_TARGET_FIELDS,
+    pyhaspi2.py:69-71).  Both lie in [0, 1] with 1 = transparent, so they are the targets as they are - no logistic map - and the
+    G-step's all-ones target keeps its meaning.  Registers no program and never raises QualityBackendMissing.
+    noise: 'utterance' (eb_BMaddnoise keyed by (seed, utterance id): an utterance is scored alike in every epoch, at any row of any
+    batch, on any rank) | False | True (keyed by the row: position dependent, never cached).  HL: audiogram of the listener.
+    ``GanTrainer(use_quality=True, quality_scorer=HasqiScorer())`` enqueues the chain on one of its metric streams."""
+    on_device = True
+    target_kind = 'hasqi'
+
+    def __init__(self, noise='utterance', seed=0, HL=None):
+        if noise not in (False, True, 'utterance'):
+            raise ValueError("HasqiScorer: noise must be 'utterance', False or True")
+        self.noise, self.seed, self.HL = noise, int(seed), HL
+
+    def split(self, x, lengths=None, utt_ids=None, owner=None, fs_=fs):
+        """-> metrics.HasqiSplit of the clean batch x [B, L] with this scorer's noise and audiogram"""
+        from . import metrics as mt
+        return mt.HasqiSplit(x, fs=fs_, lengths=lengths, noise=self.noise, seed=self.seed, utt_ids=utt_ids if self.noise == 'utterance' else None,
+                             HL=self.HL, owner=owner)
+
+    def score(self, x, y, lengths=None, utt_ids=None, fs_=fs):
+        """float64 [B, 7] (metrics.HASQI_FIELDS) of (x, y): what the trainer's targets are columns 1:3 of"""
+        from . import metrics as mt
+        return mt.batch_hasqi(x, y, fs=fs_, lengths=lengths, noise=self.noise, seed=self.seed, utt_ids=utt_ids if self.noise == 'utterance' else None, HL=self.HL)
+
+    @staticmethod
+    def targets(out):
+        """[B, 7] scores -> D_Qua's targets float32 [B, 2] (NaN where the score is undefined: the guarded Adam step then skips)"""
+        return out[:, 1:3].float()

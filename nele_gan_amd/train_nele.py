@@ -118,6 +118,18 @@ class _PendingTargets:
         return self.value
 
 
+class _Lazy:
+    """result() of a function of other pending results, evaluated once"""
+
+    def __init__(self, fn):
+        self.fn, self.value = fn, None
+
+    def result(self):
+        if self.fn is not None:
+            self.value, self.fn = self.fn(), None
+        return self.value
+
+
 class _MetricForkCtx:
     def __init__(self, fork, m):
         self.fork, self.m, self.ctx = fork, m, None
@@ -231,7 +243,9 @@ class _PendingBatch:
 
     def resolve(self, tr):
         """Wait for the targets -> the batch's D items: the generated examples', then the pre-enhanced ones'."""
-        rq = lambda q: torch.from_numpy(q.result()).to(tr.device) if hasattr(q, 'result') else q
+        def rq(q):
+            q = q.result() if hasattr(q, 'result') else q          # a Future (host programs), a _Lazy (device scorer) or the targets themselves
+            return torch.from_numpy(q).to(tr.device) if isinstance(q, np.ndarray) else q
         qua, drc_qua = rq(self.qua), rq(self.drc_qua)
         tgt = self.targets.result()
         if self.din_drc is not None:
@@ -261,6 +275,9 @@ class GanTrainer:
     multienh = None                 # fit(multienh='ssdrc'): a batch without 'drc' then gets ssdrc.ssdrc(clean) as its pre-enhanced example
     room = None
     quality_scorer = None
+    # a device-side quality scorer's chain (quality.HasqiScorer) rides on the metric stream of this metric - 'estoi': the features / ESTOI
+    # stream, 'haspi': behind HASPI's degraded half (no stream of its own: DESIGN 4.1; both measured by tools/hasqi_time.py)
+    quality_stream = 'estoi'
     target_lag = 3                  # run_epoch: batches whose metric targets may be in flight behind the sample-generation loop
     clean_cache = None              # metrics.CleanStateCache (enable_clean_cache): clean-signal halves of SIIB / HASPI kept across epochs
     cache_len_quantum = 16384       # metric inputs are padded to multiples of this many samples while the cache is on (_canon)
@@ -279,7 +296,8 @@ class GanTrainer:
         sums over the whole utterance) or 'prefix' (sums over the frames up to each frame: the causal form realtime.RealtimeEnhancer
         emits) - and with it of canonical_step, run_epoch (training samples, validation pass, D items) and fit.  The
         pre-enhanced MultiEnh examples are files and are not renormalised.
-        quality_scorer: a ``quality.Scorer`` (PESQ / ViSQOL are external host programs, registered with quality.set_backends): with
+        quality_scorer: a ``quality.HasqiScorer`` (HASQI v2 Nonlin / Linear of (clean, example), computed on the device: nothing to
+        register) or a ``quality.Scorer`` (PESQ / ViSQOL are external host programs, registered with quality.set_backends): with
         ``use_quality`` run_epoch then scores the generated and the pre-enhanced examples for D_Qua's targets where the batches bring none
         ('qua' / 'drc_qua'), and the validation utterances for the learning curve (train_nele.py:216-222, 323-324, 336-337).
         haspi_dither: None = HASPI targets without the IHC firing jitter (deterministic); 'utterance' = the reference's semantics
@@ -340,7 +358,8 @@ class GanTrainer:
         self._queues_checked = False                 # _pipeline_queues has verified that the three pipelined streams sit on three hardware queues
         # metric status, accumulated on the device without a host synchronisation and read by check_status():
         # [SIIB undefined (too few active frames: pysiib raises), SIIB clamped (M / frame caps hit: truncated score),
-        #  HASPI below threshold (pyhaspi2.py:357-358 raises)] - one accumulator per stream that folds into it
+        #  HASPI below threshold (pyhaspi2.py:357-358 raises), eigensolver repairs, HASQI quality targets below threshold (pyhaspi2.py:723-724,
+        #  :54 raise)] - one accumulator per stream that folds into it
         self._status = {}
         self._ws = {}                                # metric workspaces of the split objects (multi-GB at B = 256): owned here, freed with the trainer
         self.world = ndist.world_size()
@@ -468,17 +487,19 @@ class GanTrainer:
         return enh_wav
 
     # ---------------------------------------------------------------- metric status (intel.py / pysiib / pyhaspi2.py raise; here: count)
-    def _note_status(self, which, siib_info=None, haspi_info=None):
+    def _note_status(self, which, siib_info=None, haspi_info=None, hasqi_info=None):
         """Fold a metric call's per-utterance status into the device-side counters of accumulator ``which`` on the current stream."""
         acc = self._status.get(which)
         if acc is None:
-            acc = self._status[which] = torch.zeros(4, dtype=torch.int64, device=self.device)
+            acc = self._status[which] = torch.zeros(5, dtype=torch.int64, device=self.device)
         if siib_info is not None:
             st = siib_info[:, 3]
             acc[0:2] += torch.stack((((st & 24) != 0).sum(), ((st & 7) != 0).sum()))
             acc[3:4] += ((st & 32) != 0).sum()       # covariances that went through the eigensolver's repair path (slower, not wrong)
         if haspi_info is not None:
             acc[2:3] += (haspi_info[:, 1] != 0).sum()
+        if hasqi_info is not None:
+            acc[4:5] += ((hasqi_info[:, 1] & 3) != 0).sum()
 
     def check_status(self, raise_on_error=True):
         """Synchronising read of everything the step masked or counted on the device: metric scores the reference would have raised on
@@ -490,7 +511,7 @@ class GanTrainer:
         for st_ in self._all_side_streams():         # the 'side' accumulators are updated on a side stream BEHIND the event the main stream waits on
             if cur is not None:
                 cur.wait_stream(st_)
-        tot = torch.zeros(4, dtype=torch.int64)
+        tot = torch.zeros(5, dtype=torch.int64)
         for acc in self._status.values():
             tot += acc.cpu()
         # eigh_repaired: SIIB covariances whose cluster tridiagonalisation gave up (its workgroups were not co-resident within the spin
@@ -498,9 +519,10 @@ class GanTrainer:
         # ~3 ms per matrix instead of 25 us: a non-zero count explains a slow step, it is not an error
         st = {'siib_undefined': int(tot[0]), 'siib_clamped': int(tot[1]), 'haspi_below_threshold': int(tot[2]), 'eigh_repaired': int(tot[3]),
               'skipped_g_steps': self.optimizer_g.skipped_steps(), 'skipped_d_steps': self.optimizer_d.skipped_steps(),
-              'skipped_dqua_steps': self.optimizer_dqua.skipped_steps() if self.optimizer_dqua is not None else 0}
-        if raise_on_error and any(st[k] for k in ('siib_undefined', 'haspi_below_threshold', 'skipped_g_steps', 'skipped_d_steps',
-                                                  'skipped_dqua_steps')):
+              'skipped_dqua_steps': self.optimizer_dqua.skipped_steps() if self.optimizer_dqua is not None else 0,
+              'hasqi_below_threshold': int(tot[4])}
+        if raise_on_error and any(st[k] for k in ('siib_undefined', 'haspi_below_threshold', 'hasqi_below_threshold', 'skipped_g_steps',
+                                                  'skipped_d_steps', 'skipped_dqua_steps')):
             raise RuntimeError("NELE-GAN step status: %s (undefined metric targets; the reference raises from pysiib / "
                                "pyhaspi2.py:357-358 on such utterances; the affected optimiser steps were skipped)" % st)
         return st
@@ -511,7 +533,9 @@ class GanTrainer:
         utterance in device memory and reuse them whenever the utterance is scored again: the reference draws the same <= 720 training
         files for 500 epochs (train_nele.py:35-38,119,318-340) and recomputes them each time.  Batches must carry ``keys`` (or ``names``):
         one hashable per utterance that stands for its clean waveform (with haspi_dither='utterance': also for its utterance id).
-        ~2.1 MB (SIIB) + ~6.5 MB (HASPI) per 4 s utterance.  budget_bytes: device-memory cap (default: a quarter of what is free now);
+        ~2.1 MB (SIIB) + ~6.5 MB (HASPI) per 4 s utterance, + ~12.6 MB per example length with a quality.HasqiScorer (the clean signal's
+        basilar-membrane motion; with its noise='utterance' the key must also stand for the utterance id, as for the dither: a batch
+        without 'ids' has them derived from the keys, quality.utterance_ids).  budget_bytes: device-memory cap (default: a quarter of what is free now);
         beyond it new utterances are recomputed every time.  Scores are bit-identical to recomputation (copies only)."""
         if budget_bytes is None:
             budget_bytes = torch.cuda.mem_get_info(self.device)[0] // 4
@@ -1257,6 +1281,55 @@ class GanTrainer:
             self._quality_pool = cf.ThreadPoolExecutor(max_workers=2)
         return self._quality_pool.submit(job)
 
+    def _quality_device(self, b, examples):
+        """HASQI v2 of (clean, example) for the examples of batch ``b`` on the device (quality.HasqiScorer): the example WITHOUT the
+        listener's noise - what PESQ / ViSQOL compare in the reference and what D_Qua's input [enhanced, clean] shows - over the samples
+        _compared_samples names.  examples: list of (wav [B, L'], resynth, other lengths | None, rows | None = all).  Examples that are
+        compared over the same clean samples share one clean half (metrics.HasqiSplit: clean_part() once, degraded_part() per example),
+        with enable_clean_cache() from the cache.  Enqueued on the metric stream ``quality_stream`` names and not waited for.
+        -> pending whose result() is the list of float64 [B, 7] scores (metrics.HASQI_FIELDS; rows not asked for are 0)."""
+        sc, clean = self.quality_scorer, b['clean']
+        B = clean.shape[0]
+        # The per-utterance noise follows the utterance id.  A batch that brings no 'ids' (dataio.FileBatches, fit) gets them from its
+        # utterance keys (quality.utterance_ids: a stable hash), so an utterance is scored alike at any row of any batch in any epoch on
+        # any rank, cached or not.  Without ids and keys the ids are the row numbers and nothing of such a batch is cached.
+        ids, names = b.get('ids'), b.get('keys', b.get('names'))
+        keys = self._batch_kw(b).get('keys')
+        if ids is None and names is not None:
+            from . import quality as _q
+            ids = _q.utterance_ids(names)
+        elif ids is None:
+            ids, keys = torch.arange(B, dtype=torch.int64), None
+        ids = torch.as_tensor(ids).to(device=self.device, dtype=torch.int64)
+        groups = {}
+        for j, (wav, resynth, other, rows) in enumerate(examples):
+            ns = self._compared_samples(b, wav, resynth, other)
+            sel = tuple(range(B)) if rows is None else tuple(int(r) for r in rows)
+            groups.setdefault((min(clean.shape[1], wav.shape[1]), tuple(ns[r] for r in sel), sel), []).append(j)
+        work, inputs = [], [ids]
+        for (L, ns, sel), js in groups.items():
+            idx = None if len(sel) == B else torch.tensor(sel, dtype=torch.long).to(self.device, non_blocking=True)
+            sub = (lambda t: t) if idx is None else (lambda t: t.index_select(0, idx))
+            x, ys = sub(clean)[:, :L].contiguous(), [sub(examples[j][0])[:, :L].contiguous() for j in js]
+            lens = torch.tensor(ns, dtype=torch.int32).to(self.device, non_blocking=True)
+            gkeys = None
+            if self.clean_cache is not None and keys is not None:
+                x, ys, lens = self._canon(x, ys, lens)
+                gkeys = [(keys[r], n) for r, n in zip(sel, ns)]         # the clean file cut to the samples compared
+            work.append((js, idx, x, ys, lens, sub(ids).contiguous(), gkeys))
+            inputs += [x, lens, work[-1][5]] + ys + ([] if idx is None else [idx])
+        outs = [None] * len(examples)
+        fork = self._metric_fork(inputs)
+        with fork.on(self.quality_stream) as which:
+            for (js, idx, x, ys, lens, gid, gkeys) in work:
+                sp = sc.split(x, lens, gid, owner=self._ws)
+                sp.clean_part(cache=self.clean_cache, keys=gkeys)
+                for j, y in zip(js, ys):
+                    o = sp.degraded_part(y)
+                    self._note_status(which, hasqi_info=sp.info)
+                    outs[j] = fork.out(o if idx is None else o.new_zeros((B, o.shape[1])).index_copy_(0, idx, o))
+        return _PendingTargets([fork], lambda: outs)
+
     def run_epoch(self, gan_epoch, train_batches, valid_batches=(), chkpt_path=None, sample_dir=None, log_path=None, d_batch=32,
                   check=True, d_eval=False):
         """One iteration of ``for gan_epoch in np.arange(1, GAN_epoch+1)`` (train_nele.py:110) in the reference's order.
@@ -1353,11 +1426,13 @@ class GanTrainer:
     def _validate(self, gan_epoch, valid_batches, sample_dir, log_path):
         """:159-225: enhance the validation batches, raw metric means over all ranks, the learning-curve line.  -> what it adds to the
         epoch's result: {'valid', 'valid_mapped'}, or nothing without validation utterances."""
-        raw, vq = [], []
+        raw, vq, vh = [], [], []
         for b in valid_batches:                                         # :159-222
             f = self._batch_features(b)
             enh = self.generate(f['clean_band'], f['noise_band'], f['clean_spec'], frames=f.get('frames'))
-            if self.quality_scorer is not None:                         # :216-222 (norm=False: the raw scores of the learning curve)
+            if getattr(self.quality_scorer, 'on_device', False):        # HASQI Combined / Nonlin / Linear of (clean, enhanced), raw
+                vh.append(self._quality_device(b, [(enh, True, None, None)]))
+            elif self.quality_scorer is not None:                       # :216-222 (norm=False: the raw scores of the learning curve)
                 vq.append(self._quality_async(b['clean'], enh, self._compared_samples(b, enh), mapped=False))
             if sample_dir is not None and 'names' in b:                 # :190-198 (the reference keeps the first 20 for listening)
                 self.write_samples(enh, b['names'], sample_dir + '/Test_epoch' + str(gan_epoch), gan_epoch,
@@ -1369,7 +1444,14 @@ class GanTrainer:
         if not (raw or (dp and valid_batches is not None)):
             return {}
         n_m = len(self.metrics)
-        acc = torch.zeros(2 * n_m + 1 + 3, dtype=torch.float64, device=self.device)
+        # (the length is the same on every rank, whatever its validation shard holds: it is all-reduced)
+        dev_q = bool(getattr(self.quality_scorer, 'on_device', False))
+        acc = torch.zeros(2 * n_m + 1 + 3 + (4 if dev_q else 0), dtype=torch.float64, device=self.device)
+        if vh:                                                          # [.., sum Combined, sum Nonlin, sum Linear, utterances with a defined score]
+            h = torch.cat([p.result()[0] for p in vh], dim=0)
+            ok = ~torch.isnan(h[:, 0])
+            acc[2 * n_m + 4:2 * n_m + 7] = torch.where(ok[:, None], h[:, :3], torch.zeros_like(h[:, :3])).sum(dim=0)
+            acc[2 * n_m + 7] = ok.sum()
         if vq:                                                          # [.., sum PESQ, sum ViSQOL, utterances scored]
             q_ = np.concatenate([p.result() for p in vq], axis=0).astype(np.float64)
             acc[2 * n_m + 1:] = torch.tensor([q_[:, 0].sum(), q_[:, 1].sum(), float(q_.shape[0])], dtype=torch.float64)
@@ -1393,7 +1475,10 @@ class GanTrainer:
         if float(acc[2 * n_m + 3]) > 0:                                 # Test_PESQ / Test_VISQOL (:217-222)
             col['pesq'] = float(acc[2 * n_m + 1] / acc[2 * n_m + 3])
             col['visqol'] = float(acc[2 * n_m + 2] / acc[2 * n_m + 3])
-        line = self.validation_log_line(col.get('siib', 0.0), col.get('haspi', 0.0), col.get('estoi', 0.0), gan_epoch)
+        if dev_q and float(acc[2 * n_m + 7]) > 0:
+            for i, k_ in enumerate(('hasqi', 'hasqi_nonlin', 'hasqi_linear')):
+                col[k_] = float(acc[2 * n_m + 4 + i] / acc[2 * n_m + 7])
+        line = self.validation_log_line(col.get('siib', 0.0), col.get('haspi', 0.0), col.get('estoi', 0.0), gan_epoch, hasqi=col.get('hasqi'))
         if log_path is not None and ndist.rank() == 0:
             with open(log_path, 'a') as fh:                             # :224-225
                 fh.write(line)
@@ -1459,13 +1544,28 @@ class GanTrainer:
         p.din = self.d_inputs(enh, f['noise_band'], f['clean_band'], lens)
         if whole:
             p.din_drc = self.d_inputs(b['drc'], f['noise_band'], f['clean_band'], au._i32(dl, self.device) if dl is not None else None, resynth=False)
-        if self.quality_scorer is not None and self.D_Qua is not None:  # :323-324, 336-337: PESQ / ViSQOL of the examples D_Qua is trained on
-            if p.qua is None:
-                p.qua = self._quality_async(b['clean'], enh, self._compared_samples(b, enh))
-            if p.drc_qua is None and b.get('drc') is not None and (drc_items is None or miss):
+        if self.quality_scorer is not None and self.D_Qua is not None:  # :323-324, 336-337: the quality scores of the examples D_Qua is trained on
+            want_drc = p.drc_qua is None and b.get('drc') is not None and (drc_items is None or miss)
+            if want_drc:
                 dlh = b.get('drc_lengths_host')
                 if dlh is None:
                     dlh = dl.tolist() if torch.is_tensor(dl) else (dl if dl is not None else [b['drc'].shape[1]] * b['drc'].shape[0])
+            if getattr(self.quality_scorer, 'on_device', False):
+                # HASQI targets on the device, behind this batch's metric targets on an existing metric stream; the generated and the
+                # pre-enhanced example share the clean half when they are compared over the same samples
+                sc, ex = self.quality_scorer, []
+                if p.qua is None:
+                    ex.append(('qua', (enh, True, None, None)))
+                if want_drc:
+                    ex.append(('drc_qua', (b['drc'], False, dlh, None if drc_items is None else miss)))
+                if ex:
+                    pend = self._quality_device(b, [e for _n, e in ex])
+                    for j, (name, _e) in enumerate(ex):
+                        setattr(p, name, _Lazy(lambda j=j: sc.targets(pend.result()[j])))
+                return p
+            if p.qua is None:
+                p.qua = self._quality_async(b['clean'], enh, self._compared_samples(b, enh))
+            if want_drc:
                 p.drc_qua = self._quality_async(b['clean'], b['drc'], self._compared_samples(b, b['drc'], resynth=False, other=dlh),
                                                 rows=None if drc_items is None else miss)
         return p
@@ -1650,10 +1750,11 @@ class GanTrainer:
         return dataio.List_concat(dataio.List_concat_5scores(*[list(map(float, c)) for c in five]), enhanced_names)
 
     @staticmethod
-    def validation_log_line(siib, haspi, estoi, gan_epoch):
-        """The learning-curve line of train_nele.py:224-225 (PESQ / ViSQOL are reported as 0 there too)."""
-        return 'SIIB is %.3f, HASPI is %.3f, ESTOI is %.3f, PESQ is %.3f, VISQOL is %.3f, EPOCH:%d \n' % (
-            float(np.mean(siib)), float(np.mean(haspi)), float(np.mean(estoi)), 0, 0, gan_epoch)
+    def validation_log_line(siib, haspi, estoi, gan_epoch, hasqi=None):
+        """The learning-curve line of train_nele.py:224-225 (PESQ / ViSQOL are reported as 0 there too).  hasqi: the raw HASQI v2
+        Combined score of a trainer whose quality targets are HASQI's (quality.HasqiScorer) - a field the reference's line does not have."""
+        return 'SIIB is %.3f, HASPI is %.3f, ESTOI is %.3f, PESQ is %.3f, VISQOL is %.3f, %sEPOCH:%d \n' % (
+            float(np.mean(siib)), float(np.mean(haspi)), float(np.mean(estoi)), 0, 0, '' if hasqi is None else 'HASQI is %.3f, ' % float(hasqi), gan_epoch)
 
     # ---------------------------------------------------------------- checkpoints (train_nele.py:272-277)
     def save_checkpoint(self, path):
@@ -1661,11 +1762,17 @@ class GanTrainer:
         sd = {'enhance-model': self.G.state_dict(), 'intel-model': self.D.state_dict()}
         if self.D_Qua is not None:
             sd['quality-model'] = self.D_Qua.state_dict()
+            if self._quality_target_kind() != 'programs':    # (PESQ / ViSQOL checkpoints stay what they were)
+                sd['quality-targets'] = self._quality_target_kind()
         if self.norm != 'utterance':                 # (utterance-mode checkpoints stay what they were: the reference's two entries)
             sd['enhance-norm'] = self.norm
         if self.room is not None:                    # the listener's room the targets were taken in: names, tau and a hash of the samples
             sd['room'] = self.room.bank.record()
         torch.save(sd, path)
+
+    def _quality_target_kind(self):
+        """What D_Qua's two targets are: 'programs' (mapped PESQ / ViSQOL, the reference's) or 'hasqi' (HASQI v2 Nonlin / Linear)"""
+        return getattr(self.quality_scorer, 'target_kind', 'programs')
 
     def flush(self):
         """Complete a deferred D update (overlap_allreduce: canonical_step leaves D's gradient all-reduce and Adam-D step pending until
@@ -1691,16 +1798,16 @@ class GanTrainer:
         if 'intel-model' in ck:
             self.D.load_state_dict(ck['intel-model'])
         if self.D_Qua is not None and 'quality-model' in ck:
+            kind = ck.get('quality-targets', 'programs')
+            if self.quality_scorer is not None and kind != self._quality_target_kind():
+                raise ValueError("load_checkpoint: the quality discriminator of %s was trained on %r targets, this trainer scores %r: the two are "
+                                 "different models" % (path, kind, self._quality_target_kind()))
             self.D_Qua.load_state_dict(ck['quality-model'])
 
 
-def main(argv=None):
-    """``python -m nele_gan_amd.train_nele --data ./toy_dataset`` = the reference's usage step 3 (`python train_nele.py`, README) with the
-    script's constants (train_nele.py:28-43, 49-70) as options instead of edits: <data>/Train/{Clean,Noise,MultiEnh}, <data>/Test/{Clean,Noise}
-    as in ./toy_dataset; checkpoints in --chkpt, samples and the learning-curve log under --output.  Under torchrun every rank takes its
-    shard of the epoch's draw (one process per GPU, RCCL)."""
+def build_parser():
+    """The options of ``python -m nele_gan_amd.train_nele`` (see main)."""
     import argparse
-    from . import dataio
     ap = argparse.ArgumentParser(prog='python -m nele_gan_amd.train_nele', description=main.__doc__)
     ap.add_argument('--data', required=True, help='corpus root with Train/Clean, Train/Noise, Train/MultiEnh (optional), Test/Clean, Test/Noise')
     ap.add_argument('--metrics', default=TargetMetric)
@@ -1717,7 +1824,11 @@ def main(argv=None):
     ap.add_argument('--resume', default=None, help='checkpoint to start from (train_nele.py:82-84)')
     ap.add_argument('--first-epoch', type=int, default=1)
     ap.add_argument('--no-cache', action='store_true', help='recompute the clean-signal halves of the metrics every epoch')
-    ap.add_argument('--quality', action='store_true', help='train Discriminator_Quality too (train_nele.py:150-152, 362-365): needs --pesq and --visqol - external programs')
+    ap.add_argument('--quality', action='store_true', help='train Discriminator_Quality too (train_nele.py:150-152, 362-365): needs --pesq and --visqol - external programs - '
+                                                           'or --quality-targets hasqi')
+    ap.add_argument('--quality-targets', choices=('programs', 'hasqi'), default='programs',
+                    help="what --quality trains D_Qua on: the reference's mapped PESQ / ViSQOL scores (external programs), or 'hasqi': the Nonlin and Linear terms of "
+                         "HASQI v2 of (clean, example), computed on the GPU - needs no program; a different model from the reference's")
     ap.add_argument('--noise-pool', default=None, help='folder of noise recordings: training noise is mixed from it afresh every epoch (Train/Noise is not read)')
     ap.add_argument('--snr', default=None, help='comma-separated SNRs in dB drawn from with --noise-pool (default: -11,-9,-7,-5,-3,-1)')
     ap.add_argument('--snr-level', choices=('asl', 'rms'), default='asl', help='speech level of the SNR: ITU-T P.56 active speech level, or long-term mean square')
@@ -1729,9 +1840,30 @@ def main(argv=None):
                                                                                        "or 'ssdrc': SSDRC of the clean files computed on the GPU (Train/MultiEnh is not read)")
     from . import quality as _q
     _q.add_cli_arguments(ap)
-    a = ap.parse_args(argv)
-    if a.quality and not _q.backends_from_cli(a):
+    return ap
+
+
+def quality_scorer_from_cli(ap, a):
+    """--quality [--quality-targets ...] -> the trainer's quality scorer, or None"""
+    from . import quality as _q
+    if not a.quality:
+        return None
+    if a.quality_targets == 'hasqi':
+        return _q.HasqiScorer()
+    if not _q.backends_from_cli(a):
         ap.error('--quality needs both programs: --pesq MODULE:FUNCTION and --visqol PROGRAM --visqol-model FILE (neither is part of this build)')
+    return _q.Scorer()
+
+
+def main(argv=None):
+    """``python -m nele_gan_amd.train_nele --data ./toy_dataset`` = the reference's usage step 3 (`python train_nele.py`, README) with the
+    script's constants (train_nele.py:28-43, 49-70) as options instead of edits: <data>/Train/{Clean,Noise,MultiEnh}, <data>/Test/{Clean,Noise}
+    as in ./toy_dataset; checkpoints in --chkpt, samples and the learning-curve log under --output.  Under torchrun every rank takes its
+    shard of the epoch's draw (one process per GPU, RCCL)."""
+    from . import dataio
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    scorer = quality_scorer_from_cli(ap, a)
     root = a.data.rstrip('/')
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
@@ -1739,10 +1871,6 @@ def main(argv=None):
         import torch.distributed as tdist
         torch.cuda.set_device(local)
         tdist.init_process_group('nccl', device_id=torch.device('cuda', local))
-    scorer = None
-    if a.quality:
-        from . import quality
-        scorer = quality.Scorer()
     bank = None
     if a.rir:
         from . import room as _room
