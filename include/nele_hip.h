@@ -766,6 +766,33 @@ int nele_resample_tile(void);
 int nele_resample_var(const float* x, long long x_stride, const int* lengths_in, const int* row_ids, int R, int Lmax_out, int up, int down,
                       int K, const double* hp_dev, double gain, float* y, long long y_stride, int* lengths_out, void* stream);
 
+/* ---- shoebox room impulse responses by the image-source method (csrc/roomsynth.hip) -------------------------------------------------
+ * The impulse response of a rectangular room as DESIGN.md section 13 defines it (neither the reference nor its corpus ships one: an
+ * addition, not a parity item).  rooms [R][16] float64 (device): sizes Lx Ly Lz (m), source sx sy sz, receiver mx my mz,
+ * beta[x][0] beta[x][1] beta[y][0] beta[y][1] beta[z][0] beta[z][1] (reflection factor of the wall at coordinate 0 / at L of the axis),
+ * slot 15 reserved (0).  taps [R] (device, clamped to 0 .. N).  For axis a, parity u in {0, 1} and integer l:
+ *     delta_a(u, l) = (1 - 2u) s_a + 2 l L_a - m_a,    g_a(u, l) = beta[a][0]^|l - u| beta[a][1]^|l|    (0^0 = 1);
+ * an image is a triple of (u, l): d = sqrt(sum delta_a^2), A = g_x g_y g_z / (4 pi d), tau = d fs / c, and for 0 <= n < taps[r]
+ *     out[r][n] = sum over the images with |n - tau| <= half_width of A sinc(n - tau) 0.5 (1 + cos(pi (n - tau) / half_width)).
+ * No reflection-order cap: the truncation is in time only.  float64 throughout.  out[r][n] = 0 exactly for taps[r] <= n < N.
+ * status [R] (device): 0 or NELE_RIR_* bits, and then the row is all zeros: a size that is not a finite number in
+ * NELE_RIR_MIN_SIZE_M .. NELE_RIR_MAX_SIZE_M (every non-positive size); a source or receiver not strictly inside the room, or the two
+ * closer together than 1 cm; a beta outside [0, 1].  A row's bits depend on its room and n alone: not on R, r, N, taps, the other
+ * rooms or the run (each tap is summed by one thread in a fixed enumeration order; no atomics).  Bad host arguments - a null rooms /
+ * taps / out / status, R outside 1 .. 65535, N <= 0, half_width outside 1 .. 4096, fs or c not finite and positive,
+ * (N + half_width) c / fs above NELE_RIR_MAX_DISTANCE_M - are -1 before any GPU call.  nele_rir_synth_workspace_bytes: the bytes
+ * `workspace` must hold (0 in this version: NULL is accepted; -1 on bad R / N).  nele_rir_synth_tile: taps per workgroup. */
+#define NELE_RIR_BAD_SIZE 1
+#define NELE_RIR_BAD_POSITION 2
+#define NELE_RIR_BAD_BETA 4
+#define NELE_RIR_MIN_SIZE_M 0.1
+#define NELE_RIR_MAX_SIZE_M 1000.0
+#define NELE_RIR_MAX_DISTANCE_M 10000.0
+long long nele_rir_synth_workspace_bytes(int R, int N);
+int nele_rir_synth_tile(void);
+int nele_rir_synth(const double* rooms, const int* taps, int R, int N, double fs, double c, int half_width, double* out, int* status,
+                   void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -385,9 +385,13 @@ def main(argv=None):
                                                 "('<utt>#<rir>#...wav'), reported per RIR")
     ap.add_argument('--baseline', action='append', choices=BASELINES, default=None,
                     help="with --score: also score a baseline beside the generator - 'ssdrc' (SSDRC of the clean files) or 'clean' (the unprocessed speech); may repeat")
+    from . import roomsynth as _rs
+    _rs.add_cli_arguments(ap)
     from . import quality as _q
     _q.add_cli_arguments(ap)
     a = ap.parse_args(argv)
+    if a.rooms_synth and not a.score:
+        ap.error('--rooms-synth needs --score')
     if a.baseline and not a.score:
         ap.error('--baseline needs --score')
     if a.score_quality and not a.score:
@@ -405,9 +409,12 @@ def main(argv=None):
         score_enhanced(a.clean.rstrip('/') + '/', noise, out, groups=groups)
         if a.score_quality:
             score_quality(a.clean.rstrip('/') + '/', out, groups=groups, batch=a.batch)
-        if a.rir:
+        if a.rooms_synth:
+            bank = _rs.bank_from_cli(ap, a)                              # (refuses --rir beside it)
+        elif a.rir:
             from . import room
             bank = room.RirBank(a.rir)
+        if bank is not None:
             score_rooms(a.clean.rstrip('/') + '/', noise, out, bank, batch=a.batch)
         for tag in a.baseline or ():
             score_baseline(tag, a.clean.rstrip('/') + '/', noise, files, a.output, groups=groups, bank=bank, batch=a.batch)

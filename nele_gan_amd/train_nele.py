@@ -1838,6 +1838,8 @@ def build_parser():
     ap.add_argument('--resample', action='store_true', help='resample --noise-pool files and --rir responses that are not at 16 kHz on the GPU instead of stopping on them')
     ap.add_argument('--multienh', choices=('folder', 'ssdrc'), default='folder', help="pre-enhanced examples: the files under Train/MultiEnh (when the folder exists), "
                                                                                        "or 'ssdrc': SSDRC of the clean files computed on the GPU (Train/MultiEnh is not read)")
+    from . import roomsynth as _rs
+    _rs.add_cli_arguments(ap)
     from . import quality as _q
     _q.add_cli_arguments(ap)
     return ap
@@ -1872,7 +1874,10 @@ def main(argv=None):
         torch.cuda.set_device(local)
         tdist.init_process_group('nccl', device_id=torch.device('cuda', local))
     bank = None
-    if a.rir:
+    if a.rooms_synth:
+        from . import roomsynth as _rs
+        bank = _rs.bank_from_cli(ap, a, device='cuda:%d' % local)          # (refuses --rir beside it)
+    elif a.rir:
         from . import room as _room
         bank = _room.RirBank(a.rir, device='cuda:%d' % local, resample=a.resample)
     tr = GanTrainer(a.metrics, device='cuda:%d' % local, use_quality=a.quality, quality_scorer=scorer, norm=a.norm, room=bank)
