@@ -793,6 +793,32 @@ int nele_rir_synth_tile(void);
 int nele_rir_synth(const double* rooms, const int* taps, int R, int N, double fs, double c, int half_width, double* out, int* status,
                    void* workspace, void* stream);
 
+/* ---- acoustic echo cancellation (csrc/aec.hip) -------------------------------------------------------------------------------------
+ * One partitioned-block frequency-domain adaptive filter per stream slot (overlap-save, gradient-constrained, error-regularised step;
+ * DESIGN.md section 14 is the arithmetic): 256-sample hops, 512-point float64 transforms, `partitions` = P blocks of echo tail
+ * (256 P samples), 1 .. 32, one value per state.  `state` (nele_aec_state_bytes(max_streams, partitions) bytes, 256-byte aligned)
+ * holds a header and one record of nele_aec_stream_record_bytes(partitions) bytes per slot; nele_aec_init lays it out and clears
+ * every slot, nele_aec_reset clears the slots with slots[b] != 0 (NULL = all).  The same (max_streams, partitions) in every call on
+ * one state: a kernel given another pair touches nothing.
+ * nele_aec_hop: mic / played [max_streams][nh * 256] float32, hop h of the call in columns [256 h, 256 h + 256); per hop
+ *   y = the filter's echo estimate from the last P hops of `played`, e = mic - y, residual = float32(e), echo = float32(y) (echo may
+ *   be NULL); S_e follows |E|^2 in every hop; the weights move by mu E conj(X_p) / (sum_p |X_p|^2 + gamma P S_e + delta), constrained,
+ *   in the slots with adapt[b] != 0 (NULL = all).  active [max_streams] (bytes, NULL = all): inactive slots are neither read nor
+ *   written and their output columns are left as they were.  0 < mu < 2, gamma >= 0, delta > 0.  A slot's outputs and state are the
+ *   same bits whatever nh per call, max_streams and the other slots are.
+ * nele_aec_echo_path: h [max_streams][partitions * 256] float64, h[256 p + n] = irfft512(W_p)[n]: the impulse-response estimate.
+ * Bad host arguments are -1 before any GPU call; the *_bytes functions return -1 on bad arguments. */
+#define NELE_AEC_SMOOTH 0.9            /* S_e <- NELE_AEC_SMOOTH S_e + (1 - NELE_AEC_SMOOTH) |E|^2 */
+#define NELE_AEC_MAX_PARTITIONS 32
+long long nele_aec_state_bytes(int max_streams, int partitions);
+long long nele_aec_stream_record_bytes(int partitions);
+int nele_aec_init(void* state, long long state_bytes, int max_streams, int partitions, void* stream);
+int nele_aec_reset(void* state, long long state_bytes, int max_streams, int partitions, const unsigned char* slots, void* stream);
+int nele_aec_hop(void* state, long long state_bytes, int max_streams, int partitions, const float* mic, const float* played,
+                 const unsigned char* active, const unsigned char* adapt, int nh, double mu, double gamma, double delta,
+                 float* residual, float* echo, void* stream);
+int nele_aec_echo_path(const void* state, long long state_bytes, int max_streams, int partitions, double* h, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,275 @@
+"""Acoustic echo cancellation for the real-time enhancer: the microphone at the listener's end hears the room's noise AND the loudspeaker
+playing the enhancer's own output; ``EchoCanceller`` takes the loudspeaker's part out of it, so that what reaches ``RealtimeEnhancer`` as
+`noise` is the noise.  One partitioned-block frequency-domain adaptive filter per stream slot (256-sample hops, 512-point float64
+transforms, P partitions = 256 P samples of echo tail) in libnele_hip.so (csrc/aec.hip, the ``nele_aec_*`` entry points; the arithmetic
+is DESIGN.md section 14).  This module owns memory and bookkeeping only; there is no arithmetic in torch.
+
+    aec = EchoCanceller(streams=256, partitions=8)
+    residual = aec.process(mic_hops, played_hops)              # [256, nh * 256] each -> mic minus the estimated echo of `played`
+    h = aec.echo_path()                                        # [256, 8 * 256] float64: the impulse responses estimated so far
+
+    loop = EchoCancellingEnhancer(RealtimeEnhancer(...), aec)  # closes the loop: what process() returns is what the loudspeaker plays
+    out = loop.process(clean_hops, mic_hops)                   # during the next call's capture
+
+    python -m nele_gan_amd.aec --mic mic.wav --played far.wav --out residual.wav [--partitions 8] [--echo-path h.npy]
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import c_double, c_int, c_longlong, c_void_p, call, ptr, stream
+
+HOP = 256
+MAX_PARTITIONS = 32
+
+_RESTYPES = {'nele_aec_state_bytes': c_longlong, 'nele_aec_stream_record_bytes': c_longlong, 'nele_aec_init': c_int, 'nele_aec_reset': c_int,
+             'nele_aec_hop': c_int, 'nele_aec_echo_path': c_int}
+_lib._SIGS.update({
+    'nele_aec_state_bytes': [c_int, c_int],
+    'nele_aec_stream_record_bytes': [c_int],
+    'nele_aec_init': [c_void_p, c_longlong, c_int, c_int, c_void_p],
+    'nele_aec_reset': [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p],
+    'nele_aec_hop': [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_double, c_void_p,
+                     c_void_p, c_void_p],
+    'nele_aec_echo_path': [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p],
+})
+for _n, _r in _RESTYPES.items():
+    getattr(_lib.lib, _n).argtypes = _lib._SIGS[_n]
+    getattr(_lib.lib, _n).restype = _r
+
+
+def _norm_dev(device):
+    d = torch.device(device)
+    return torch.device('cuda', torch.cuda.current_device()) if d.type == 'cuda' and d.index is None else d
+
+
+class EchoCanceller:
+    """B independent echo cancellers.  partitions: P in 1 .. 32, the echo tail the filter covers is 256 P samples (128 ms at P = 8);
+    mu (0 < mu < 2), gamma (>= 0), delta (> 0): the step of DESIGN.md section 14 - the weights move by
+    mu E conj(X_p) / (sum_p |X_p|^2 + gamma P S_e + delta), S_e the smoothed power of the residual."""
+
+    def __init__(self, streams, partitions=8, mu=0.5, gamma=4.0, delta=1e-2, device='cuda'):
+        self.S, self.P = int(streams), int(partitions)
+        if self.S < 1:
+            raise ValueError("EchoCanceller: streams must be >= 1")
+        if not 1 <= self.P <= MAX_PARTITIONS:
+            raise ValueError("EchoCanceller: partitions must be in 1 .. %d (got %d)" % (MAX_PARTITIONS, self.P))
+        self.mu, self.gamma, self.delta = float(mu), float(gamma), float(delta)
+        if not (0.0 < self.mu < 2.0) or not (self.gamma >= 0.0) or not (self.delta > 0.0):
+            raise ValueError("EchoCanceller: needs 0 < mu < 2, gamma >= 0 and delta > 0 (got %g, %g, %g)" % (self.mu, self.gamma, self.delta))
+        self.device = _norm_dev(device)
+        self.nbytes = int(_lib.lib.nele_aec_state_bytes(self.S, self.P))
+        self.state = torch.empty((self.nbytes,), dtype=torch.uint8, device=self.device)
+        self.hops = np.zeros(self.S, dtype=np.int64)
+        call('nele_aec_init', ptr(self.state), c_longlong(self.nbytes), self.S, self.P, stream())
+
+    # ---- helpers (as RealtimeEnhancer's)
+    def _mask(self, flags, name):
+        m = np.asarray(flags, dtype=bool).reshape(-1)
+        if m.shape[0] != self.S:
+            raise ValueError("EchoCanceller: %s must hold one flag per stream" % name)
+        return m
+
+    def _slots_mask(self, slots):
+        m = np.zeros(self.S, dtype=bool)
+        m[np.asarray(slots, dtype=np.int64).reshape(-1)] = True
+        return m
+
+    def _dev_bytes(self, mask):
+        return torch.from_numpy(mask.astype(np.uint8)).pin_memory().to(self.device, non_blocking=True)
+
+    def _dev_f32(self, x, shape, name):
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(np.asarray(x, dtype=np.float32))
+        if tuple(x.shape) != shape:
+            raise ValueError("EchoCanceller: %s must be %s (got %s)" % (name, shape, tuple(x.shape)))
+        if x.dtype != torch.float32:
+            raise ValueError("EchoCanceller: %s must be float32" % name)
+        if not x.is_cuda:
+            if not x.is_pinned():
+                x = x.pin_memory()
+            x = x.to(self.device, non_blocking=True)
+        return x.contiguous()
+
+    # ---- streaming
+    def process(self, mic, played, active=None, adapt=None, want_echo=False, out=None):
+        """mic, played [streams, nh * 256] float32 (host, pinned host or device) -> residual [streams, nh * 256] on the device: mic minus
+        the echo of `played` as estimated so far (with want_echo: (residual, echo)).  played: what the loudspeaker put out while mic was
+        captured, hop for hop; a constant extra delay is part of the echo path.  active / adapt: host bool sequences [streams] or None
+        (all): inactive slots are neither read nor changed and their output columns are left as they were; slots with adapt false
+        cancel with the filter they have and do not move it.  out (beyond RealtimeEnhancer's signature): a residual buffer, or
+        (residual, echo), on the device to write into - the way to keep an inactive slot's columns; without it the outputs are fresh
+        tensors and an inactive slot's columns undefined.  Never blocks the host."""
+        shape = tuple(np.shape(mic))
+        if len(shape) != 2 or shape[0] != self.S or shape[1] % HOP or shape[1] == 0:
+            raise ValueError("EchoCanceller.process: mic must be [%d, nh * 256]" % self.S)
+        nh = shape[1] // HOP
+        d = self._dev_f32(mic, shape, 'mic')
+        x = self._dev_f32(played, shape, 'played')
+        act = None if active is None else self._mask(active, 'active')
+        ada = None if adapt is None else self._dev_bytes(self._mask(adapt, 'adapt'))
+        res, echo = (out if isinstance(out, (tuple, list)) else (out, None)) if out is not None else (None, None)
+        res = torch.empty(shape, dtype=torch.float32, device=self.device) if res is None else res
+        echo = (torch.empty(shape, dtype=torch.float32, device=self.device) if echo is None else echo) if want_echo else None
+        for o in (res, echo):
+            if o is not None and (tuple(o.shape) != shape or o.dtype != torch.float32):
+                raise ValueError("EchoCanceller.process: out buffers must be float32 %s" % (shape,))
+        call('nele_aec_hop', ptr(self.state), c_longlong(self.nbytes), self.S, self.P, ptr(d), ptr(x), ptr(None if act is None else self._dev_bytes(act)),
+             ptr(ada), nh, self.mu, self.gamma, self.delta, ptr(res), ptr(echo), stream())
+        self.hops[slice(None) if act is None else act] += nh
+        return (res, echo) if want_echo else res
+
+    def echo_path(self, slots=None):
+        """-> float64 [len(slots), partitions * 256] on the device (all slots when None): h[256 p + n] = irfft512(W_p)[n], the impulse
+        response from `played` to `mic` as estimated so far (zeros after a reset)."""
+        h = torch.empty((self.S, self.P * HOP), dtype=torch.float64, device=self.device)
+        call('nele_aec_echo_path', ptr(self.state), c_longlong(self.nbytes), self.S, self.P, ptr(h), stream())
+        if slots is None:
+            return h
+        idx = torch.from_numpy(np.asarray(slots, dtype=np.int64).reshape(-1)).pin_memory().to(self.device, non_blocking=True)
+        return h.index_select(0, idx)
+
+    def reset(self, slots):
+        """Restart the given slots (zero weights, history and S_e); the other slots are not touched."""
+        m = self._slots_mask(slots)
+        call('nele_aec_reset', ptr(self.state), c_longlong(self.nbytes), self.S, self.P, ptr(self._dev_bytes(m)), stream())
+        self.hops[m] = 0
+
+
+class EchoCancellingEnhancer:
+    """``RealtimeEnhancer`` behind an ``EchoCanceller``, the loop closed: per call
+        residual = aec.process(mic, played);  out = rt.process(clean, residual);  played <- out (active slots)
+    with played = zeros before a slot's first call and after its reset.  The caller's promise: what process() returns is what the
+    loudspeaker plays during the NEXT call's capture (any constant extra delay is part of the echo path the canceller learns).  The
+    number of hops per call is fixed by the first call."""
+
+    def __init__(self, rt, aec):
+        if rt.S != aec.S:
+            raise ValueError("EchoCancellingEnhancer: the enhancer has %d streams, the canceller %d" % (rt.S, aec.S))
+        self.rt, self.aec, self.S = rt, aec, rt.S
+        self.played = None                                 # [S, nh * 256] on the canceller's device, from the first call on
+
+    def _played(self, width):
+        if self.played is None:
+            self.played = torch.zeros((self.S, width), dtype=torch.float32, device=self.aec.device)
+        elif self.played.shape[1] != width:
+            raise ValueError("EchoCancellingEnhancer: %d hops per call, this call brings %d (fixed for the object's life)"
+                             % (self.played.shape[1] // HOP, width // HOP))
+        return self.played
+
+    def _to_dev(self, t):
+        """host tensor -> the loop's device through pinned memory, without blocking the host (as RealtimeEnhancer's arguments)"""
+        dev = self.played.device
+        if t.device == dev or dev.type != 'cuda':
+            return t.to(dev)
+        return (t if t.is_pinned() else t.pin_memory()).to(dev, non_blocking=True)
+
+    def _rows(self, slots):
+        return self._to_dev(torch.from_numpy(np.asarray(slots, dtype=np.int64).reshape(-1)))
+
+    def process(self, clean, mic, active=None, debug=None):
+        """clean, mic [streams, nh * 256] float32 -> out [streams, nh * 256] (RealtimeEnhancer.process on the echo-cancelled mic).
+        The returned tensor is the caller's: the loop keeps its own copy of what was played.  debug: RealtimeEnhancer's RealtimeDebug."""
+        shape = tuple(np.shape(mic))
+        if len(shape) != 2 or shape[1] % HOP or shape[1] == 0:
+            raise ValueError("EchoCancellingEnhancer.process: mic must be [%d, nh * 256]" % self.S)
+        played = self._played(shape[1])
+        residual = self.aec.process(mic, played, active=active)
+        out = self.rt.process(clean, residual, active=active) if debug is None else self.rt.process(clean, residual, active=active, debug=debug)
+        if active is None:
+            played.copy_(out)                              # an owned buffer: later calls and reset() change it in place
+        else:
+            rows = self._rows(np.nonzero(np.asarray(active, dtype=bool).reshape(-1))[0])
+            played.index_copy_(0, rows, out.index_select(0, rows))
+        return out
+
+    def finish(self, slots, clean_tail, mic_tail, tail_lengths, debug=None):
+        """End the streams of ``slots`` (RealtimeEnhancer.finish): the tails [len(slots), <= 256] are padded to one hop, one canceller hop
+        runs on those slots (against the first hop of what they were last given to play) and the first tail_lengths[i] samples of its
+        residual are the noise tails of rt.finish."""
+        slots = np.asarray(slots, dtype=np.int64).reshape(-1)
+        mt = torch.as_tensor(mic_tail, dtype=torch.float32).reshape(len(slots), -1)
+        if mt.shape[1] > HOP:
+            raise ValueError("EchoCancellingEnhancer.finish: tails must be [len(slots), <= 256]")
+        played = self._played(HOP if self.played is None else self.played.shape[1])
+        rows = self._rows(slots)
+        mic = torch.zeros((self.S, HOP), dtype=torch.float32, device=played.device)
+        mic[:, :mt.shape[1]].index_copy_(0, rows, self._to_dev(mt))
+        act = np.zeros(self.S, dtype=bool)
+        act[slots] = True
+        residual = self.aec.process(mic, played[:, :HOP].contiguous(), active=act)
+        ct = torch.as_tensor(clean_tail, dtype=torch.float32).reshape(len(slots), -1)
+        if ct.shape[1] < HOP:
+            ct = torch.nn.functional.pad(ct, (0, HOP - ct.shape[1]))
+        kw = {} if debug is None else {'debug': debug}
+        return self.rt.finish(slots, self._to_dev(ct), residual.index_select(0, rows), tail_lengths, **kw)
+
+    def reset(self, slots):
+        """Restart the given slots in both objects; they play zeros until their next call."""
+        self.rt.reset(slots)
+        self.aec.reset(slots)
+        if self.played is not None:
+            slots = np.asarray(slots, dtype=np.int64).reshape(-1)
+            self.played.index_fill_(0, self._rows(slots), 0.0)
+
+
+# ------------------------------------------------------------------------------------------------------------------ command line
+def cancel_file(mic, played, partitions=8, mu=0.5, gamma=4.0, delta=1e-2, device='cuda'):
+    """mic, played: float32 arrays of one length L -> (residual [L] float32, echo path [partitions * 256] float64): the whole hops through
+    one EchoCanceller call, the last L % 256 samples zero-padded to one more hop and cut again."""
+    mic = np.ascontiguousarray(mic, dtype=np.float32).reshape(-1)
+    played = np.ascontiguousarray(played, dtype=np.float32).reshape(-1)
+    if mic.shape != played.shape or mic.size == 0:
+        raise ValueError("aec: --mic and --played must have one length (got %d and %d samples)" % (mic.size, played.size))
+    L = mic.size
+    nh = (L + HOP - 1) // HOP
+    d = np.zeros((1, nh * HOP), dtype=np.float32)
+    x = np.zeros((1, nh * HOP), dtype=np.float32)
+    d[0, :L], x[0, :L] = mic, played
+    aec = EchoCanceller(1, partitions=partitions, mu=mu, gamma=gamma, delta=delta, device=device)
+    res = aec.process(torch.from_numpy(d), torch.from_numpy(x))
+    h = aec.echo_path()
+    return res[0, :L].cpu().numpy(), h[0].cpu().numpy()
+
+
+def build_parser():
+    import argparse
+    ap = argparse.ArgumentParser(prog='python -m nele_gan_amd.aec', description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--mic', required=True, help='16 kHz PCM_16 wav: what the microphone captured')
+    ap.add_argument('--played', required=True, help='16 kHz PCM_16 wav of the same length: what the loudspeaker played meanwhile')
+    ap.add_argument('--out', required=True, help='the residual (mic minus the estimated echo), PCM_16')
+    ap.add_argument('--partitions', type=int, default=8, help='256-sample blocks of echo tail the filter covers, 1 .. 32')
+    ap.add_argument('--echo-path', default=None, metavar='NPY', help='write the final impulse-response estimate (float64 [partitions * 256])')
+    ap.add_argument('--mu', type=float, default=0.5)
+    ap.add_argument('--gamma', type=float, default=4.0)
+    ap.add_argument('--delta', type=float, default=1e-2)
+    return ap
+
+
+def main(argv=None):
+    from . import dataio
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    if not 1 <= a.partitions <= MAX_PARTITIONS:
+        ap.error('--partitions must be in 1 .. %d' % MAX_PARTITIONS)
+    if not (0.0 < a.mu < 2.0) or not (a.gamma >= 0.0) or not (a.delta > 0.0):
+        ap.error('needs 0 < --mu < 2, --gamma >= 0 and --delta > 0')
+    sig = []
+    for path in (a.mic, a.played):
+        wav, sr = dataio.read_wav(path)
+        if sr != dataio.fs:
+            ap.error('%s is sampled at %d Hz, not %d: convert it first with python -m nele_gan_amd.resample' % (path, sr, dataio.fs))
+        sig.append(wav)
+    if len(sig[0]) != len(sig[1]) or len(sig[0]) == 0:
+        ap.error('--mic and --played must have one length (got %d and %d samples)' % (len(sig[0]), len(sig[1])))
+    res, h = cancel_file(sig[0], sig[1], partitions=a.partitions, mu=a.mu, gamma=a.gamma, delta=a.delta)
+    dataio.write_wav_pcm16(a.out, res)
+    if a.echo_path:
+        np.save(a.echo_path, h)
+    print('%s: %d samples, %d partitions (%d ms of echo tail)' % (a.out, len(res), a.partitions, a.partitions * HOP * 1000 // dataio.fs))
+    return 0
+
+
+if __name__ == '__main__':
+    import sys
+    sys.exit(main())
