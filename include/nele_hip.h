@@ -819,6 +819,35 @@ int nele_aec_hop(void* state, long long state_bytes, int max_streams, int partit
                  float* residual, float* echo, void* stream);
 int nele_aec_echo_path(const void* state, long long state_bytes, int max_streams, int partitions, double* h, void* stream);
 
+/* ---- stream-rate conversion for the real-time path (csrc/resample_stream.hip) -------------------------------------------------------
+ * The resampler above, hop by hop on many concurrent streams (DESIGN.md section 15 is the arithmetic): up, down, half, the taps, the
+ * table hp[up][K] (nele_resample_taps, layout 1) and y[n] are those of nele_resample_var with gain 1.  A stream is x[0 ..) with zeros
+ * before its start; with D = half div down (nele_resample_stream_delay) its output sample m = 0, 1, .. is y[m - D], for negative m - D
+ * too (the filter's pre-ringing): for m >= D the bits nele_resample_var gives for the whole signal, D samples late.  A hop is n_in
+ * input and n_out output samples, n_in up = n_out down; nele_resample_stream_hop_lengths gives the pair with 256 samples on the
+ * 16 kHz side (to16k != 0: n_out = 256, the other rate comes in; to16k = 0: n_in = 256) and refuses a ratio whose other side is
+ * not a whole number of samples (44.1 kHz and its family: 705.6 - convert those offline with nele_resample_var).  Supported: the
+ * limits of nele_resample_var on up, down and zeros, a table of at most 16 KiB (up K 8 <= 16384), D <= n_out.
+ * `state` (nele_resample_stream_state_bytes(max_streams, K) bytes, 256-byte aligned): a 256-byte header (max_streams, K, up, down) and
+ * one record of nele_resample_stream_record_bytes(K) bytes per slot - the slot's last K - 1 input samples as float32, nothing else.
+ * nele_resample_stream_init lays it out and zeroes every slot, nele_resample_stream_reset zeroes the slots with slots[b] != 0
+ * (NULL = all).  The same (max_streams, up, down, K) in every call on one state: a kernel given other values touches nothing.
+ * nele_resample_stream_hop: x [max_streams] rows of x_stride >= nh n_in_hop floats, y rows of y_stride >= nh n_out floats
+ * (n_out = n_in_hop up / down, a whole number; nh >= 1 hops per call); writes y[b][0 .. nh n_out) and the record.  active
+ * [max_streams] (bytes, NULL = all): inactive slots are neither read nor written and their output columns are left as they were.
+ * A slot's outputs and state are the same bits whatever nh per call, max_streams and the other slots are.  The _delay, _hop_lengths,
+ * _record_bytes and _state_bytes functions make no HIP call and return -1 on bad arguments (the first two with the reason in
+ * nele_last_error_string); bad host arguments of the others are -1 before any GPU call.  No allocation, no workspace. */
+int nele_resample_stream_delay(int up, int down, int zeros);
+int nele_resample_stream_hop_lengths(int up, int down, int to16k, int* n_in, int* n_out);
+long long nele_resample_stream_record_bytes(int K);
+long long nele_resample_stream_state_bytes(int max_streams, int K);
+int nele_resample_stream_init(void* state, long long state_bytes, int max_streams, int up, int down, int K, void* stream);
+int nele_resample_stream_reset(void* state, long long state_bytes, int max_streams, int up, int down, int K, const unsigned char* slots,
+                               void* stream);
+int nele_resample_stream_hop(void* state, long long state_bytes, int max_streams, int up, int down, int K, const double* hp_dev, const float* x,
+                             long long x_stride, const unsigned char* active, int nh, int n_in_hop, float* y, long long y_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,8 @@ files at their own rate and asserts 16 kHz (dataloader.py:34-37): this is an add
     python -m nele_gan_amd.resample --in DIR --out DIR [--sr 16000] [--quality high|scipy] [--batch 64]
                                                                        every .wav under DIR as PCM_16 at --sr, same relative path,
                                                                        and DIR/resample_manifest.csv
+    StreamResampler(streams, sr_in, sr_out, quality='high').process(x_hops) -> y_hops             live streams hop by hop between 16 kHz and
+                                                                       8 .. 96 kHz (csrc/resample_stream.hip)
 
 ``quality``: 'high' = (zeros 32, Kaiser beta 12.0): stop band at most -119 dB from 1.15 x the new Nyquist frequency, pass-band ripple below
 0.001 dB up to 0.85 x; 'scipy' = (10, 5.0): resample_poly's own default (-43 dB); or a (zeros, beta) pair.  The taps are designed on the
@@ -41,6 +43,26 @@ for _n in ('nele_resample_out_len', 'nele_resample_taps_count'):
     getattr(_lib.lib, _n).restype = c_longlong
 
 TILE = int(_lib.lib.nele_resample_tile())                  # outputs per workgroup of the kernel (tests put lengths around it)
+
+# the stream converter of the real-time path (csrc/resample_stream.hip)
+_STREAM_RESTYPES = {'nele_resample_stream_delay': c_int, 'nele_resample_stream_hop_lengths': c_int,
+                    'nele_resample_stream_record_bytes': c_longlong, 'nele_resample_stream_state_bytes': c_longlong,
+                    'nele_resample_stream_init': c_int, 'nele_resample_stream_reset': c_int, 'nele_resample_stream_hop': c_int}
+_lib._SIGS.update({
+    'nele_resample_stream_delay': [c_int, c_int, c_int],
+    'nele_resample_stream_hop_lengths': [c_int, c_int, c_int, c_void_p, c_void_p],
+    'nele_resample_stream_record_bytes': [c_int],
+    'nele_resample_stream_state_bytes': [c_int, c_int],
+    'nele_resample_stream_init': [c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p],
+    'nele_resample_stream_reset': [c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    'nele_resample_stream_hop': [c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_longlong, c_void_p, c_int, c_int, c_void_p,
+                                 c_longlong, c_void_p],
+})
+for _n, _r in _STREAM_RESTYPES.items():
+    getattr(_lib.lib, _n).argtypes = _lib._SIGS[_n]
+    getattr(_lib.lib, _n).restype = _r
+
+STREAM_RATE = 16000                                        # the rate of the real-time path: one side of every stream converter
 
 
 def ratio(sr_in, sr_out):
@@ -139,6 +161,121 @@ class Resampler:
         call('nele_resample_var', x, L, ptr(ln), ptr(ids), int(rows.size), int(y.shape[1]), self.up, self.down, self.K, ptr(table), float(gain),
              ptr(y), int(y.shape[1]), ptr(n_out), stream())
         return y, n_out
+
+
+def stream_plan(sr_in, sr_out, quality='high'):
+    """The stream converter sr_in -> sr_out of DESIGN.md section 15 -> dict(up, down, zeros, beta, K, hop_in, hop_out, delay), from the
+    library's host functions: no GPU call.  One side must be 16 000 Hz and a 256-sample hop there a whole number of samples on the
+    other side; anything else is a ValueError (44.1 kHz and its family: convert those offline, python -m nele_gan_amd.resample)."""
+    sr_in, sr_out = int(sr_in), int(sr_out)
+    up, down = ratio(sr_in, sr_out)
+    if STREAM_RATE not in (sr_in, sr_out):
+        raise ValueError("StreamResampler: one side must be %d Hz, the rate of the real-time path (got %d -> %d); other pairs are converted "
+                         "offline, by Resampler / python -m nele_gan_amd.resample" % (STREAM_RATE, sr_in, sr_out))
+    zeros, beta = quality_params(quality)
+    n_in, n_out = c_int(0), c_int(0)
+    call('nele_resample_stream_hop_lengths', up, down, int(sr_out == STREAM_RATE), ctypes.byref(n_in), ctypes.byref(n_out))
+    delay = int(_lib.lib.nele_resample_stream_delay(up, down, zeros))
+    if delay < 0:
+        _lib.check(-1, 'nele_resample_stream_delay')
+    if delay > n_out.value:
+        raise ValueError("StreamResampler: the filter's delay of %d output samples is longer than a hop of %d" % (delay, n_out.value))
+    half = zeros * max(up, down)
+    return {'up': up, 'down': down, 'zeros': zeros, 'beta': beta, 'K': -(-(2 * half + 1) // up), 'hop_in': n_in.value, 'hop_out': n_out.value,
+            'delay': delay}
+
+
+class StreamResampler:
+    """``streams`` independent live streams from sr_in to sr_out, hop by hop (csrc/resample_stream.hip; the arithmetic is DESIGN.md
+    section 15).  One side is 16 kHz, where a hop is 256 samples: ``hop_in`` input samples give ``hop_out`` output samples.  What a stream
+    has emitted is, bit for bit, ``Resampler(sr_in, sr_out, quality)``'s output for the whole signal fed so far, ``delay`` output samples
+    late (the first ``delay`` outputs are the filter's pre-ringing); flush() hands out the rest.  The state of a slot is its last K - 1
+    input samples.  This class owns memory and bookkeeping only; there is no arithmetic in torch."""
+
+    def __init__(self, streams, sr_in, sr_out, quality='high', device='cuda'):
+        self.S = int(streams)
+        if self.S < 1:
+            raise ValueError("StreamResampler: streams must be >= 1")
+        self.sr_in, self.sr_out = int(sr_in), int(sr_out)
+        plan = stream_plan(sr_in, sr_out, quality)           # raises ValueError for an unsupported pair, before any GPU call
+        self.up, self.down, self.zeros, self.beta, self.K = plan['up'], plan['down'], plan['zeros'], plan['beta'], plan['K']
+        self.hop_in, self.hop_out, self.delay = plan['hop_in'], plan['hop_out'], plan['delay']
+        d = torch.device(device)
+        self.device = torch.device('cuda', torch.cuda.current_device()) if d.type == 'cuda' and d.index is None else d
+        self.table = torch.from_numpy(taps(self.up, self.down, self.zeros, self.beta, layout=1)).to(self.device)
+        self.nbytes = int(_lib.lib.nele_resample_stream_state_bytes(self.S, self.K))
+        self.state = torch.empty((self.nbytes,), dtype=torch.uint8, device=self.device)
+        self.hops = np.zeros(self.S, dtype=np.int64)
+        self._zero_hop = None
+        call('nele_resample_stream_init', ptr(self.state), c_longlong(self.nbytes), self.S, self.up, self.down, self.K, stream())
+
+    # ---- helpers (as RealtimeEnhancer's)
+    def _slots_mask(self, slots):
+        m = np.zeros(self.S, dtype=bool)
+        m[np.asarray(slots, dtype=np.int64).reshape(-1)] = True
+        return m
+
+    def _dev_bytes(self, mask):
+        return torch.from_numpy(mask.astype(np.uint8)).pin_memory().to(self.device, non_blocking=True)
+
+    def _dev_f32(self, x, shape, name):
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(np.asarray(x, dtype=np.float32))
+        if tuple(x.shape) != shape:
+            raise ValueError("StreamResampler: %s must be %s (got %s)" % (name, shape, tuple(x.shape)))
+        if x.dtype != torch.float32:
+            raise ValueError("StreamResampler: %s must be float32" % name)
+        if not x.is_cuda:
+            if not x.is_pinned():
+                x = x.pin_memory()
+            x = x.to(self.device, non_blocking=True)
+        return x.contiguous()
+
+    # ---- streaming
+    def process(self, x, active=None, out=None):
+        """x [streams, nh * hop_in] float32 (host, pinned host or device) -> y [streams, nh * hop_out] on the device.  active: host bool
+        sequence [streams] or None (all): inactive slots are neither read nor changed and their output columns are left as they were
+        (undefined in a fresh tensor; give ``out``, a float32 [streams, nh * hop_out] device tensor, to keep them).  Never blocks the
+        host."""
+        shape = tuple(np.shape(x))
+        if len(shape) != 2 or shape[0] != self.S or shape[1] % self.hop_in or shape[1] == 0:
+            raise ValueError("StreamResampler.process: x must be [%d, nh * %d] (got %s)" % (self.S, self.hop_in, shape))
+        nh = shape[1] // self.hop_in
+        act = None
+        if active is not None:
+            act = np.asarray(active, dtype=bool).reshape(-1)
+            if act.shape[0] != self.S:
+                raise ValueError("StreamResampler.process: active must hold one flag per stream (%d)" % self.S)
+        oshape = (self.S, nh * self.hop_out)
+        if out is None:
+            out = torch.empty(oshape, dtype=torch.float32, device=self.device)
+        elif not isinstance(out, torch.Tensor) or tuple(out.shape) != oshape or out.dtype != torch.float32 or not out.is_cuda \
+                or not out.is_contiguous():
+            raise ValueError("StreamResampler.process: out must be a contiguous float32 %s tensor on the device" % (oshape,))
+        xd = self._dev_f32(x, shape, 'x')                     # every check is behind us: the first transfer
+        call('nele_resample_stream_hop', ptr(self.state), c_longlong(self.nbytes), self.S, self.up, self.down, self.K, ptr(self.table), ptr(xd),
+             c_longlong(shape[1]), ptr(None if act is None else self._dev_bytes(act)), nh, self.hop_in, ptr(out), c_longlong(oshape[1]), stream())
+        self.hops[slice(None) if act is None else act] += nh
+        return out
+
+    def flush(self, slots):
+        """End the streams of ``slots``: one hop of zeros through those slots -> its first ``delay`` columns, [len(slots), delay] - the
+        outputs still inside the filter; with what was emitted that is the offline resampler's whole output.  Resets those slots."""
+        slots = np.asarray(slots, dtype=np.int64).reshape(-1)
+        if self._zero_hop is None:
+            self._zero_hop = torch.zeros((self.S, self.hop_in), dtype=torch.float32, device=self.device)
+        y = self.process(self._zero_hop, active=self._slots_mask(slots))
+        rows = torch.from_numpy(slots).pin_memory().to(self.device, non_blocking=True)
+        tail = y.index_select(0, rows)[:, :self.delay].contiguous()
+        self.reset(slots)
+        return tail
+
+    def reset(self, slots):
+        """Restart the given slots (a zero history); the other slots are not touched."""
+        m = self._slots_mask(slots)
+        call('nele_resample_stream_reset', ptr(self.state), c_longlong(self.nbytes), self.S, self.up, self.down, self.K, ptr(self._dev_bytes(m)),
+             stream())
+        self.hops[m] = 0
 
 
 _CACHE = {}

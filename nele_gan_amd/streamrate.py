@@ -1,0 +1,98 @@
+"""The real-time path at the device's sample rate: ``RateAdaptedEnhancer`` puts a ``StreamResampler`` (nele_gan_amd/resample.py,
+csrc/resample_stream.hip) in front of and behind a ``RealtimeEnhancer`` or an ``EchoCancellingEnhancer``, which
+work at 16 kHz in hops of 256 samples.  Telephony is 8 kHz, browsers and sound cards 48 kHz; supported device rates are those at which
+a 16 ms hop is a whole number of samples (8, 12, 22, 24, 32, 48, 64, 96 kHz ..; not 44.1 kHz and its family - convert those offline with
+python -m nele_gan_amd.resample).  This module owns memory and bookkeeping only; there is no arithmetic in torch.
+
+    rt48 = RateAdaptedEnhancer(RealtimeEnhancer(chkpt, streams=256), device_rate=48000)
+    out = rt48.process(clean_hops, noise_hops)                 # [256, nh * 768] each, at 48 kHz -> [256, nh * 768] at 48 kHz
+"""
+import numpy as np
+import torch
+
+from .aec import EchoCancellingEnhancer
+from .realtime import HOP, RealtimeEnhancer
+from .resample import STREAM_RATE, StreamResampler
+
+
+class RateAdaptedEnhancer:
+    """``inner`` (a RealtimeEnhancer or an EchoCancellingEnhancer of B streams) behind one down-converter of 2 B slots - the clean signal
+    in slots 0 .. B - 1, the second signal in slots B .. 2 B - 1: one launch, the same delay for both - and in front of an up-converter of
+    B slots.  ``hop``: samples per hop at the device rate (device_rate * 16 ms).  ``latency``, in device-rate samples: the down-converter's
+    delay (D_down samples at 16 kHz = D_down hop / 256), the enhancer's hop and the up-converter's delay D_up; 960 samples = 20 ms at
+    48 kHz with quality 'high'.  device_rate = 16000 passes straight through to ``inner``.
+
+    Around an EchoCancellingEnhancer the two converters' delays are a constant extra delay of the echo path the canceller learns - D_up at
+    the device rate plus D_down at 16 kHz, 64 samples at 16 kHz for 48 kHz 'high': leave room for it in the canceller's partitions (DESIGN.md
+    section 14).
+
+    Streams end through drain(): the inner path's finish() and its tails of less than a hop are not offered at the device rate."""
+
+    def __init__(self, inner, device_rate, quality='high'):
+        if not isinstance(inner, (RealtimeEnhancer, EchoCancellingEnhancer)):
+            raise ValueError("RateAdaptedEnhancer: inner must be a RealtimeEnhancer or an EchoCancellingEnhancer (got %s)" % type(inner).__name__)
+        self.inner, self.S = inner, inner.S
+        self.device_rate = int(device_rate)
+        self.device = inner.device if isinstance(inner, RealtimeEnhancer) else inner.aec.device
+        self._per_call = 1                                 # hops of the last call (an EchoCancellingEnhancer fixes them for its life)
+        if self.device_rate == STREAM_RATE:
+            self.down = self.up = self._both = None
+            self.hop, self.latency = HOP, HOP
+            return
+        # both constructors raise ValueError for an unsupported rate before any GPU call
+        self.down = StreamResampler(2 * self.S, self.device_rate, STREAM_RATE, quality, self.device)
+        self.up = StreamResampler(self.S, STREAM_RATE, self.device_rate, quality, self.device)
+        self.hop = self.down.hop_in
+        self.latency = self.down.delay * self.hop // HOP + self.hop + self.up.delay
+        self._both = None                                  # [2 S, nh * hop]: the two signals stacked for the down-converter
+
+    def _stack(self, clean, second, width):
+        if self._both is None or self._both.shape[1] != width:
+            self._both = torch.empty((2 * self.S, width), dtype=torch.float32, device=self.device)
+        shape = (self.S, width)
+        c, s = self.down._dev_f32(clean, shape, 'clean'), self.down._dev_f32(second, shape, 'second')      # both checked before the first copy
+        self._both[:self.S].copy_(c, non_blocking=True)
+        self._both[self.S:].copy_(s, non_blocking=True)
+        return self._both
+
+    def process(self, clean, second, active=None):
+        """clean, second [streams, nh * hop] float32 at the device rate (host, pinned host or device); second is the noise for a
+        RealtimeEnhancer and the microphone for an EchoCancellingEnhancer -> the enhanced signal [streams, nh * hop] at the device rate,
+        on the device, ``latency`` samples behind ``clean``.  active: host bool sequence [streams] or None (all); inactive slots are
+        neither read nor changed and their output columns are undefined.  Never blocks the host."""
+        if self.down is None:
+            self._per_call = max(1, int(np.shape(clean)[-1]) // HOP)
+            return self.inner.process(clean, second, active=active)
+        shape = tuple(np.shape(clean))
+        if len(shape) != 2 or shape[0] != self.S or shape[1] % self.hop or shape[1] == 0:
+            raise ValueError("RateAdaptedEnhancer.process: clean must be [%d, nh * %d] (got %s)" % (self.S, self.hop, shape))
+        act = None
+        if active is not None:
+            act = np.asarray(active, dtype=bool).reshape(-1)
+            if act.shape[0] != self.S:
+                raise ValueError("RateAdaptedEnhancer.process: active must hold one flag per stream (%d)" % self.S)
+        self._per_call = shape[1] // self.hop
+        low = self.down.process(self._stack(clean, second, shape[1]), active=None if act is None else np.concatenate([act, act]))
+        out = self.inner.process(low[:self.S], low[self.S:], active=act)
+        return self.up.process(out, active=act)
+
+    def drain(self, slots):
+        """ceil(latency / hop) hops of zeros through the given slots -> their outputs [len(slots), ceil(latency / hop) * hop]: what is
+        still delayed inside leaves this way (the other slots are not touched).  The zeros go in calls as wide as the last process()
+        call (an EchoCancellingEnhancer fixes its hops per call), so those slots may receive a few zero hops more than are returned."""
+        slots = np.asarray(slots, dtype=np.int64).reshape(-1)
+        act = np.zeros(self.S, dtype=bool)
+        act[slots] = True
+        nh, per = -(-self.latency // self.hop), self._per_call
+        zeros = torch.zeros((self.S, per * self.hop), dtype=torch.float32, device=self.device)
+        outs = [self.process(zeros, zeros, active=act) for _ in range(-(-nh // per))]
+        rows = torch.from_numpy(slots).pin_memory().to(self.device, non_blocking=True)
+        return torch.cat([o.index_select(0, rows) for o in outs], dim=1)[:, :nh * self.hop]
+
+    def reset(self, slots):
+        """Restart the given slots in the inner object and in both converters."""
+        self.inner.reset(slots)
+        if self.down is not None:
+            slots = np.asarray(slots, dtype=np.int64).reshape(-1)
+            self.down.reset(np.concatenate([slots, slots + self.S]))
+            self.up.reset(slots)
