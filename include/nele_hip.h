@@ -54,7 +54,7 @@ int nele_profile_collect(float* ms_out, int max_n);
  * foreign-function call instead of 25 .. 60.  The host mirror records its own per-layer loop the first time it sees a shape
  * (nele_gan_amd/_lib.py), so the layer logic exists once; a reference-side binding may build the tables itself the same way.
  * Operations: every entry point of this header whose last parameter is the stream (nele_plan_op_id(name); csrc/plan_ops.inc is generated
- * from this header by tools/gen_plan_ops.py).  streams_host [nstreams]: index 0 = the caller's stream, 1.. = the side streams the plan was
+ * from this header by tools/gen_abi.py).  streams_host [nstreams]: index 0 = the caller's stream, 1.. = the side streams the plan was
  * recorded with (weight gradients run beside the data-gradient chain). */
 #define NELE_PLAN_MAXARGS 24
 typedef struct nele_plan_job {

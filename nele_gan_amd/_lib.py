@@ -8,6 +8,8 @@ import os
 
 import torch
 
+from ._abi import CONSTS, FUNCS
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('NELE_LIB') or os.path.join(_HERE, 'libnele_hip.so')     # NELE_LIB: another build of the same ABI (A/B measurements)
 
@@ -32,117 +34,24 @@ def _load():
 
 
 lib = _load()
-lib.nele_version.restype = c_int
-lib.nele_last_error_string.restype = ctypes.c_char_p
-
-# name -> argtypes (all return int status); mirrors include/nele_hip.h
-_SIGS = {
-    'nele_device_info': [ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.c_char_p, c_int],
-    'nele_build_has_ab_switches': [],
-    'nele_stream_spin': [ctypes.c_double, c_void_p],
-    'nele_stream_occupy': [c_int, c_int, ctypes.c_double, c_void_p],
-    'nele_stft_band': [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
-    'nele_imcra_band': [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
-    'nele_gain_istft': [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
-    'nele_wav_post': [c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_void_p],
-    'nele_profile_begin': [ctypes.c_char_p],
-    'nele_profile_collect': [c_void_p, c_int],
-    'nele_profile_collect_tag': [ctypes.c_char_p, c_void_p, c_int],
-    'nele_stft_band_var': [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
-    'nele_imcra_band_var': [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
-    'nele_imcra_band_ws': [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p],
-    'nele_imcra_workspace_bytes': [c_int, c_int],
-    'nele_stft_pow_var': [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
-    'nele_imcra_band_pw': [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p],
-    'nele_gain_istft_var': [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
-    'nele_wav_post_var': [c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_void_p],
-    'nele_compute_band_E': [c_void_p, c_int, c_void_p, c_void_p],
-    'nele_interp_band_gain': [c_void_p, c_int, c_void_p, c_void_p],
-}
 
 
-def declare(name, argtypes):
-    fn = getattr(lib, name)
-    fn.argtypes = argtypes
-    fn.restype = c_int
-    return fn
+def _bind():
+    """Sets argtypes and restype of every entry point from _abi.FUNCS (generated from include/nele_hip.h by tools/gen_abi.py)
+    -> name -> argtypes."""
+    missing = sorted(n for n in FUNCS if not hasattr(lib, n))
+    if missing:
+        raise ImportError("nele_gan_amd: %s does not export %s (declared in include/nele_hip.h) -- rebuild it with "
+                          "`python -c 'import __graft_entry__ as g; g.build()'`" % (LIB_PATH, ', '.join(missing)))
+    sigs = {}
+    for name, (restype, argtypes) in FUNCS.items():
+        fn = getattr(lib, name)
+        fn.restype = getattr(ctypes, 'c_' + restype)
+        fn.argtypes = sigs[name] = [getattr(ctypes, 'c_' + a) for a in argtypes]
+    return sigs
 
 
-for _n, _a in _SIGS.items():
-    declare(_n, _a)
-_SIGS.update({
-    'nele_wav_decode_pcm16': [ctypes.c_char_p, c_void_p, c_longlong, ctypes.POINTER(c_longlong), ctypes.POINTER(c_int)],
-    'nele_wav_write_pcm16': [ctypes.c_char_p, c_void_p, c_longlong, c_int, c_int],
-    'nele_wav_read_pcm16_batch': [c_void_p, c_int, c_void_p, c_longlong, c_longlong, c_void_p, c_void_p, c_int],
-    'nele_wav_write_pcm16_batch': [c_void_p, c_int, c_void_p, c_longlong, c_void_p, c_int, c_int],
-    'nele_wav_probe_pcm16_batch': [c_void_p, c_int, c_void_p, c_int],
-    'nele_pcm16_to_float': [c_void_p, c_longlong, c_void_p, c_int, c_longlong, c_void_p, c_longlong, c_void_p],
-    'nele_float_to_pcm16': [c_void_p, c_longlong, c_int, c_longlong, c_void_p, c_longlong, c_int, c_void_p],
-    'nele_event_record': [c_void_p, c_void_p],
-    'nele_stream_wait_event': [c_void_p, c_void_p],
-    'nele_vec_add': [c_void_p, c_void_p, c_longlong, c_void_p],
-    'nele_event_create': [ctypes.POINTER(c_void_p)],
-    'nele_event_destroy': [c_void_p],
-    'nele_plan_op_id': [ctypes.c_char_p],
-    'nele_plan_op_nargs': [c_int],
-    'nele_plan_create': [ctypes.c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_void_p)],
-    'nele_plan_run': [c_void_p, ctypes.POINTER(c_void_p), c_int, ctypes.POINTER(c_longlong), c_int],
-    'nele_plan_destroy': [c_void_p],
-    'nele_plan_declare_slot': [c_void_p, c_int, c_longlong, c_int],
-    'nele_plan_slot_bytes': [c_void_p, c_int],
-    'nele_plan_run_sized': [c_void_p, ctypes.POINTER(c_void_p), c_int, ctypes.POINTER(c_longlong), ctypes.POINTER(c_longlong), c_int],
-    'nele_gen_param_count': [],
-    'nele_gen_param_layout': [ctypes.POINTER(c_longlong), c_int],
-    'nele_gen_workspace_bytes': [c_int, c_int, c_int, c_int],
-    'nele_gen_plan_build': [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p)],
-    'nele_disc_param_count': [c_int, c_int],
-    'nele_disc_param_layout': [c_int, c_int, ctypes.POINTER(c_longlong), c_int],
-    'nele_disc_workspace_bytes': [c_int, c_int, c_int, c_int],
-    'nele_disc_workspace_ddin': [c_void_p, c_int, c_int, c_int, c_int],
-    'nele_disc_plan_build': [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.POINTER(c_void_p), c_void_p, c_longlong, c_void_p,
-                             ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p)],
-    'nele_gen_fwd': [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint, ctypes.POINTER(c_void_p), c_int],
-    'nele_gen_bwd': [c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_void_p), c_int],
-    'nele_gen_plans_build': [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_void_p, ctypes.POINTER(c_void_p),
-                             ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p)],
-    'nele_disc_plans_build': [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.POINTER(c_void_p), c_void_p, c_longlong, c_int,
-                              c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p)],
-    'nele_disc_workspace_buffer': [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_char_p, ctypes.POINTER(c_int)],
-    'nele_disc_fwd': [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_void_p), c_int],
-    'nele_disc_bwd': [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_void_p), c_int],
-})
-for _n in ('nele_wav_decode_pcm16', 'nele_wav_write_pcm16', 'nele_wav_read_pcm16_batch', 'nele_wav_write_pcm16_batch', 'nele_wav_probe_pcm16_batch', 'nele_pcm16_to_float', 'nele_float_to_pcm16', 'nele_event_record', 'nele_stream_wait_event', 'nele_vec_add', 'nele_event_create', 'nele_event_destroy', 'nele_plan_op_id', 'nele_plan_op_nargs',
-           'nele_plan_create', 'nele_plan_run', 'nele_plan_destroy', 'nele_gen_fwd', 'nele_gen_bwd', 'nele_disc_fwd', 'nele_disc_bwd'):
-    declare(_n, _SIGS[_n])
-for _n in ('nele_plan_declare_slot', 'nele_plan_run_sized', 'nele_gen_param_layout', 'nele_gen_plan_build', 'nele_disc_param_layout', 'nele_disc_plan_build',
-           'nele_gen_plans_build', 'nele_disc_plans_build'):
-    declare(_n, _SIGS[_n])
-for _n in ('nele_plan_slot_bytes', 'nele_gen_param_count', 'nele_gen_workspace_bytes', 'nele_disc_param_count', 'nele_disc_workspace_bytes'):
-    getattr(lib, _n).argtypes = _SIGS[_n]
-    getattr(lib, _n).restype = c_longlong
-lib.nele_disc_workspace_ddin.argtypes = _SIGS['nele_disc_workspace_ddin']
-lib.nele_disc_workspace_ddin.restype = c_void_p
-lib.nele_disc_workspace_buffer.argtypes = _SIGS['nele_disc_workspace_buffer']
-lib.nele_disc_workspace_buffer.restype = c_void_p
-# real-time enhancement (csrc/realtime.hip, nele_gan_amd/realtime.py)
-_RT_DBG = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]
-_SIGS.update({
-    'nele_rt_init': [c_void_p, c_longlong, c_int, c_void_p, c_int, c_void_p],
-    'nele_rt_set_weights': [c_void_p, c_longlong, c_int, c_void_p, c_int, c_void_p],
-    'nele_rt_reset': [c_void_p, c_longlong, c_int, c_void_p, c_void_p],
-    'nele_rt_hop': [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p] + _RT_DBG,
-    'nele_rt_finish': [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + _RT_DBG,
-})
-for _n in ('nele_rt_init', 'nele_rt_set_weights', 'nele_rt_reset', 'nele_rt_hop', 'nele_rt_finish'):
-    declare(_n, _SIGS[_n])
-for _n, _a in (('nele_rt_state_bytes', [c_int]), ('nele_rt_stream_record_bytes', [])):
-    getattr(lib, _n).argtypes = _a
-    getattr(lib, _n).restype = c_longlong
-    _SIGS[_n] = _a
-lib.nele_imcra_workspace_bytes.restype = c_longlong
-lib.nele_wav_post_workspace_doubles.argtypes = [c_int, c_int]
-lib.nele_wav_post_workspace_doubles.restype = c_longlong
-_SIGS['nele_wav_post_workspace_doubles'] = lib.nele_wav_post_workspace_doubles.argtypes
+_SIGS = _bind()
 
 
 def check(status, name=''):
@@ -154,7 +63,7 @@ def check(status, name=''):
 
 
 # ------------------------------------------------------------------ job tables (csrc/plan.hip): the generic form of a plan's jobs
-PLAN_MAXARGS = 24
+PLAN_MAXARGS = CONSTS['NELE_PLAN_MAXARGS']
 
 
 class nele_plan_job(ctypes.Structure):

@@ -17,25 +17,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import c_double, c_int, c_longlong, c_void_p, call, ptr, stream
+from ._lib import c_longlong, call, ptr, stream
 
 HOP = 256
-MAX_PARTITIONS = 32
-
-_RESTYPES = {'nele_aec_state_bytes': c_longlong, 'nele_aec_stream_record_bytes': c_longlong, 'nele_aec_init': c_int, 'nele_aec_reset': c_int,
-             'nele_aec_hop': c_int, 'nele_aec_echo_path': c_int}
-_lib._SIGS.update({
-    'nele_aec_state_bytes': [c_int, c_int],
-    'nele_aec_stream_record_bytes': [c_int],
-    'nele_aec_init': [c_void_p, c_longlong, c_int, c_int, c_void_p],
-    'nele_aec_reset': [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p],
-    'nele_aec_hop': [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_double, c_void_p,
-                     c_void_p, c_void_p],
-    'nele_aec_echo_path': [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p],
-})
-for _n, _r in _RESTYPES.items():
-    getattr(_lib.lib, _n).argtypes = _lib._SIGS[_n]
-    getattr(_lib.lib, _n).restype = _r
+MAX_PARTITIONS = _lib.CONSTS['NELE_AEC_MAX_PARTITIONS']
 
 
 def _norm_dev(device):

@@ -10,24 +10,13 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import c_int, c_longlong, c_void_p, call, ptr, stream
+from ._lib import call, ptr, stream
 
-SILENT, BELOW_MARGIN, NO_CROSSING = 1, 2, 4                # NELE_P56_* (include/nele_hip.h)
+SILENT, BELOW_MARGIN, NO_CROSSING = (_lib.CONSTS['NELE_P56_' + _n] for _n in ('SILENT', 'BELOW_MARGIN', 'NO_CROSSING'))
 STATUS_NAMES = {SILENT: 'NELE_P56_SILENT (no sample reaches the lowest threshold)',
                 BELOW_MARGIN: 'NELE_P56_BELOW_MARGIN (long-term level less than 15.9 dB above the lowest threshold)',
                 NO_CROSSING: 'NELE_P56_NO_CROSSING (no threshold reaches the 15.9 dB margin)'}
 N_THRESHOLDS = 15
-
-_lib._SIGS.update({
-    'nele_asl_p56_var': [c_void_p, c_void_p, c_int, c_int, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    'nele_mix_noise_var': [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                           c_void_p, c_void_p],
-    'nele_asl_p56_workspace_bytes': [c_int, c_int],
-})
-for _n in ('nele_asl_p56_var', 'nele_mix_noise_var'):
-    _lib.declare(_n, _lib._SIGS[_n])
-_lib.lib.nele_asl_p56_workspace_bytes.argtypes = _lib._SIGS['nele_asl_p56_workspace_bytes']
-_lib.lib.nele_asl_p56_workspace_bytes.restype = c_longlong
 
 
 def batch_asl_P56(wav, lengths=None):

@@ -5,20 +5,12 @@ conditions, then the raw (un-mapped) SIIB / HASPI / ESTOI of (direct-path clean,
     lfilter_fir(h, x)        scipy.signal.lfilter(h, [1], x)           -> nele_fir_filter
     norm_clip(a, add, rms)   a / rms(a) * rms (+ add), audio_util.clip   -> nele_norm_clip
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib
 from . import metrics as mt
-from ._lib import c_int, c_void_p, call, declare, ptr, stream
-
-_P = c_void_p
-declare('nele_fir_filter', [_P, c_int, c_int, _P, c_int, _P, _P])
-_lib._SIGS['nele_fir_filter'] = _lib.lib.nele_fir_filter.argtypes
-declare('nele_norm_clip', [_P, _P, _P, c_int, c_int, ctypes.c_double, _P, _P, _P, _P])
-_lib._SIGS['nele_norm_clip'] = _lib.lib.nele_norm_clip.argtypes
+from ._lib import call, ptr, stream
 
 fs = 16000
 

@@ -16,75 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import c_int, c_longlong, c_void_p, call, declare, ptr, stream
-
-_P = c_void_p
-declare('nele_metric_estoi', [_P, _P, c_int, c_int, _P, c_longlong, _P, _P, _P])
-_lib._SIGS['nele_metric_estoi'] = _lib.lib.nele_metric_estoi.argtypes
-declare('nele_metric_estoi_var', [_P, _P, _P, c_int, c_int, _P, c_longlong, _P, _P, _P])
-_lib._SIGS['nele_metric_estoi_var'] = _lib.lib.nele_metric_estoi_var.argtypes
-declare('nele_metric_siib_var', [_P, _P, _P, c_int, c_int, _P, c_longlong, _P, _P, _P, c_int, _P])
-_lib._SIGS['nele_metric_siib_var'] = _lib.lib.nele_metric_siib_var.argtypes
-_lib.lib.nele_metric_estoi_workspace_bytes.argtypes = [c_int, c_int]
-_lib.lib.nele_metric_estoi_workspace_bytes.restype = c_longlong
-_lib._SIGS['nele_metric_estoi_workspace_bytes'] = _lib.lib.nele_metric_estoi_workspace_bytes.argtypes
-
-declare('nele_metric_siib', [_P, _P, c_int, c_int, _P, c_longlong, _P, _P, _P, _P])
-declare('nele_metric_siib_phase', [_P, _P, c_int, c_int, _P, c_longlong, _P, _P, _P, c_int, _P])
-_lib._SIGS['nele_metric_siib_phase'] = _lib.lib.nele_metric_siib_phase.argtypes
-_lib._SIGS['nele_metric_siib'] = _lib.lib.nele_metric_siib.argtypes
-_lib.lib.nele_metric_siib_workspace_bytes.argtypes = [c_int, c_int]
-_lib.lib.nele_metric_siib_workspace_bytes.restype = c_longlong
-_lib._SIGS['nele_metric_siib_workspace_bytes'] = _lib.lib.nele_metric_siib_workspace_bytes.argtypes
-
-declare('nele_metric_haspi', [_P, _P, c_int, c_int, c_int, _P, _P, c_longlong, _P, _P, _P, _P])
-_lib._SIGS['nele_metric_haspi'] = _lib.lib.nele_metric_haspi.argtypes
-declare('nele_metric_haspi_var', [_P, _P, _P, c_int, c_int, c_int, _P, _P, c_longlong, _P, _P, _P, c_int, _P])
-_lib._SIGS['nele_metric_haspi_var'] = _lib.lib.nele_metric_haspi_var.argtypes
-declare('nele_metric_haspi_var_hl', [_P, _P, _P, c_int, c_int, c_int, _P, ctypes.POINTER(ctypes.c_double), c_int, _P, c_longlong, _P, _P, _P, c_int, _P])
-_lib._SIGS['nele_metric_haspi_var_hl'] = _lib.lib.nele_metric_haspi_var_hl.argtypes
-_lib.lib.nele_metric_haspi_workspace_bytes.argtypes = [c_int, c_int, c_int]
-_lib.lib.nele_metric_haspi_workspace_bytes.restype = c_longlong
-_lib._SIGS['nele_metric_haspi_workspace_bytes'] = _lib.lib.nele_metric_haspi_workspace_bytes.argtypes
-_lib.lib.nele_metric_haspi_quality_workspace_bytes.argtypes = [c_int, c_int, c_int]
-_lib.lib.nele_metric_haspi_quality_workspace_bytes.restype = c_longlong
-_lib._SIGS['nele_metric_haspi_quality_workspace_bytes'] = _lib.lib.nele_metric_haspi_quality_workspace_bytes.argtypes
-declare('nele_metric_haspi_quality', [_P, _P, _P, c_int, c_int, c_int, c_int, ctypes.c_ulonglong, ctypes.c_double, _P, c_longlong, _P, _P, _P])
-_lib._SIGS['nele_metric_haspi_quality'] = _lib.lib.nele_metric_haspi_quality.argtypes
-declare('nele_metric_haspi_quality_hl', [_P, _P, _P, c_int, c_int, c_int, c_int, ctypes.c_ulonglong, ctypes.c_double, ctypes.POINTER(ctypes.c_double), c_int, _P,
-                                         c_longlong, _P, _P, _P])
-_lib._SIGS['nele_metric_haspi_quality_hl'] = _lib.lib.nele_metric_haspi_quality_hl.argtypes
-_lib.lib.nele_metric_hasqi_workspace_bytes.argtypes = [c_int, c_int, c_int]
-_lib.lib.nele_metric_hasqi_workspace_bytes.restype = c_longlong
-_lib._SIGS['nele_metric_hasqi_workspace_bytes'] = _lib.lib.nele_metric_hasqi_workspace_bytes.argtypes
-declare('nele_metric_hasqi_var', [_P, _P, _P, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_double), c_int, ctypes.c_ulonglong, _P, _P, c_longlong, _P, _P, c_int, _P])
-_lib._SIGS['nele_metric_hasqi_var'] = _lib.lib.nele_metric_hasqi_var.argtypes
-declare('nele_metric_hasqi_clean_sections', [c_int, c_int, c_int, ctypes.POINTER(c_longlong), c_int])
-_lib._SIGS['nele_metric_hasqi_clean_sections'] = _lib.lib.nele_metric_hasqi_clean_sections.argtypes
-_lib.lib.nele_metric_haspi_nsub.argtypes = [c_int, c_int]
-_lib.lib.nele_metric_haspi_nsub.restype = c_int
-_lib._SIGS['nele_metric_haspi_nsub'] = _lib.lib.nele_metric_haspi_nsub.argtypes
-
-declare('nele_metric_siib_clean_sections', [c_int, c_int, ctypes.POINTER(c_longlong), c_int])
-_lib._SIGS['nele_metric_siib_clean_sections'] = _lib.lib.nele_metric_siib_clean_sections.argtypes
-declare('nele_metric_haspi_clean_sections', [c_int, c_int, c_int, ctypes.POINTER(c_longlong), c_int])
-_lib._SIGS['nele_metric_haspi_clean_sections'] = _lib.lib.nele_metric_haspi_clean_sections.argtypes
-
-declare('nele_haspi_dither_rows', [_P, ctypes.c_ulonglong, c_int, c_int, _P, _P])
-_lib._SIGS['nele_haspi_dither_rows'] = _lib.lib.nele_haspi_dither_rows.argtypes
-
-declare('nele_eigh_sym_batched', [_P, c_int, c_int, _P, _P, _P, c_longlong, _P])
-_lib._SIGS['nele_eigh_sym_batched'] = _lib.lib.nele_eigh_sym_batched.argtypes
-declare('nele_eigh_sym_batched_range', [_P, c_int, c_int, _P, _P, _P, c_longlong, _P, ctypes.c_double, _P])
-_lib._SIGS['nele_eigh_sym_batched_range'] = _lib.lib.nele_eigh_sym_batched_range.argtypes
-declare('nele_metric_siib_kept_first', [c_int, c_int, _P, ctypes.POINTER(c_int)])
-_lib._SIGS['nele_metric_siib_kept_first'] = _lib.lib.nele_metric_siib_kept_first.argtypes
-_lib.lib.nele_eigh_repaired.argtypes = [_P, c_int, c_int]
-_lib.lib.nele_eigh_repaired.restype = c_int
-_lib._SIGS['nele_eigh_repaired'] = _lib.lib.nele_eigh_repaired.argtypes
-_lib.lib.nele_eigh_workspace_bytes.argtypes = [c_int, c_int]
-_lib.lib.nele_eigh_workspace_bytes.restype = c_longlong
-_lib._SIGS['nele_eigh_workspace_bytes'] = _lib.lib.nele_eigh_workspace_bytes.argtypes
+from ._lib import c_int, c_longlong, call, ptr, stream
 
 _ws_cache = {}
 

@@ -13,7 +13,7 @@ from . import _lib, synth
 from . import asl_P56 as _p56
 from ._lib import call, ptr, stream
 
-ZERO_NOISE, ZERO_LEVEL, BAD_ROW = 1, 2, 4                  # NELE_MIX_* (include/nele_hip.h)
+ZERO_NOISE, ZERO_LEVEL, BAD_ROW = (_lib.CONSTS['NELE_MIX_' + _n] for _n in ('ZERO_NOISE', 'ZERO_LEVEL', 'BAD_ROW'))
 
 
 def draw_words(seed, key, epoch, n=3):

@@ -1,97 +1,10 @@
 """Thin Python wrappers over the dense / glue entry points of libnele_hip.so (no arithmetic here)."""
-import ctypes
 import os
 
 import torch
 
 from . import _lib
-from ._lib import c_float, c_int, c_longlong, c_void_p, call, declare, ptr, stream
-
-_P = c_void_p
-_SIGS = {
-    'nele_conv_gemm': [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, ctypes.POINTER(c_int), _P],
-    'nele_conv_gemm_bf16': [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, ctypes.POINTER(c_int), _P],
-    'nele_conv_wgrad': [_P, _P, _P, c_longlong, c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_int, _P, _P, c_int, _P],
-    'nele_conv_wgrad_bf16': [_P, _P, _P, c_longlong, c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_int, _P, _P, c_int, _P],
-    'nele_weight_prep': [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P],
-    'nele_weight_prep_frag': [_P, c_int, c_int, _P, _P],
-    'nele_conv_span_supported': [c_int, c_int, ctypes.POINTER(c_int), c_int, c_int],
-    'nele_conv_span': [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, ctypes.POINTER(c_int), c_int, c_int, c_longlong, _P],
-    'nele_conv_span_bf16': [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, ctypes.POINTER(c_int), c_int, c_int, c_longlong, _P],
-    'nele_conv_span_bf16_supported': [c_int, c_int, ctypes.POINTER(c_int), c_int, c_int],
-    'nele_conv_span_bf16_a16_supported': [c_int, c_int, ctypes.POINTER(c_int), c_int, c_int],
-    'nele_conv_span_bf16_a16': [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, ctypes.POINTER(c_int), c_int, c_int, c_longlong, _P],
-    'nele_conv_wgrad_bf16_d16_supported': [c_int, c_int, ctypes.POINTER(c_int), c_int, c_int],
-    'nele_conv_wgrad_bf16_d16': [_P, _P, _P, c_longlong, c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_int, _P, _P, c_int, _P],
-    'nele_weight_prep_frag16': [_P, c_int, c_int, c_int, c_int, _P, _P],
-    'nele_weight_prep_frag16x3': [_P, c_int, c_int, c_int, c_int, _P, _P, _P],
-    'nele_weight_prep_frag16x3_batch': [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, _P],
-    'nele_conv_span_bf16x3_supported': [c_int, c_int, ctypes.POINTER(c_int), c_int, c_int],
-    'nele_conv_span_bf16x3': [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, ctypes.POINTER(c_int), c_int, c_int, c_longlong, _P],
-    'nele_conv_wgrad_bf16x3_supported': [c_int, c_int, ctypes.POINTER(c_int), c_int, c_int],
-    'nele_conv_wgrad_bf16x3': [_P, _P, _P, c_longlong, c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_int, _P, _P, c_int, _P],
-    'nele_conv16_supported': [c_int, c_int, ctypes.POINTER(c_int), c_int, c_int],
-    'nele_conv16_weight_prep_batch': [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, _P],
-    'nele_conv16': [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, ctypes.POINTER(c_int), c_int, c_int, _P],
-    'nele_conv16_pointwise_fwd': [_P, _P, _P, _P, c_longlong, c_int, c_float, _P],
-    'nele_conv16_gap': [_P, _P, _P, _P, c_int, c_int, c_float, ctypes.POINTER(c_int), c_int, c_int, _P, _P, _P],
-    'nele_conv16_gap_parts': [c_int, ctypes.POINTER(c_int), c_int, c_int],
-    'nele_conv_wgrad_bf16_a16d16': [_P, _P, _P, c_longlong, c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_int, _P, _P, c_int, _P],
-    'nele_g_pack': [_P, _P, _P, c_int, c_int, c_int, _P],
-    'nele_g_pack16': [_P, _P, _P, c_int, c_int, c_int, _P],
-    'nele_glayer16_supported': [c_int, c_int, c_int],
-    'nele_glayer16_weight_prep_batch': [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, _P],
-    'nele_glayer16_fwd': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_uint, c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P],
-    'nele_glayer16_conv': [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P],
-    'nele_cln_fwd': [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P],
-    'nele_cln_bwd': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P],
-    'nele_cln_chunks': [c_int],
-    'nele_colsum': [_P, c_int, c_int, _P, c_int, _P],
-    'nele_weight_prep_batch': [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, _P],
-    'nele_weight_prep_frag16_batch': [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, _P],
-    'nele_colsum2': [_P, _P, _P, _P, c_int, c_int, c_int, _P],
-    'nele_exptanh_bwd': [_P, _P, _P, c_longlong, _P],
-    'nele_energy_norm_fwd': [_P, _P, _P, c_float, c_float, _P, _P, _P, _P, c_int, c_int, _P],
-    'nele_energy_norm_bwd': [_P, _P, _P, _P, _P, _P, c_float, c_float, _P, c_int, c_int, _P],
-    'nele_energy_norm_prefix_fwd': [_P, _P, _P, c_float, c_float, _P, _P, _P, _P, c_int, c_int, _P],
-    'nele_energy_norm_prefix_bwd': [_P, _P, _P, _P, _P, _P, c_float, c_float, _P, c_int, c_int, _P],
-    'nele_d_pack': [_P, _P, _P, _P, c_int, c_int, _P],
-    'nele_d_layout': [_P, _P, c_int, c_int, c_int, c_int, _P],
-    'nele_d_gather_items': [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), ctypes.POINTER(c_longlong), c_int, c_int, c_int, _P, _P, _P],
-    'nele_spectral_norm': [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, _P, c_int, _P],
-    'nele_sn_grad': [_P, _P, _P, _P, _P, c_int, c_int, _P, c_int, _P, _P],
-    'nele_sn_grad_scratch_doubles': [c_int],
-    'nele_gap_mlp_fwd': [_P, c_int, c_int, ctypes.POINTER(c_void_p), c_int, c_float, _P, _P, _P, _P, _P, _P],
-    'nele_gap_mlp_bwd': [_P, _P, _P, _P, _P, ctypes.POINTER(c_void_p), c_int, c_float, c_int, c_int, c_int, c_int, c_int, c_int,
-                         c_int, _P, _P, _P, _P, _P, _P],
-    'nele_gap_mlp_fwd_var': [_P, c_int, c_int, c_int, _P, ctypes.POINTER(c_void_p), c_int, c_float, _P, _P, _P, _P, _P, _P],
-    'nele_gap_mlp_bwd_var': [_P, _P, _P, _P, _P, ctypes.POINTER(c_void_p), c_int, c_float, c_int, c_int, c_int, _P, c_int, c_int, c_int,
-                             c_int, _P, _P, _P, _P, _P, _P],
-    'nele_gap_mlp_bwd_var16': [_P, _P, _P, _P, _P, ctypes.POINTER(c_void_p), c_int, c_float, c_int, c_int, c_int, _P, c_int, c_int, c_int,
-                               c_int, _P, _P, _P, _P, _P, _P],
-    'nele_gap_mlp_bwd_var16a': [_P, _P, _P, _P, _P, ctypes.POINTER(c_void_p), c_int, c_float, c_int, c_int, c_int, _P, c_int, c_int, c_int,
-                                c_int, _P, _P, _P, _P, _P, _P],
-    'nele_gap_mlp_fwd_parts': [_P, c_int, c_int, c_int, c_int, _P, ctypes.POINTER(c_void_p), c_int, c_float, _P, _P, _P, _P, _P],
-    'nele_mlp_wgrad': [_P, _P, c_int, c_int, c_int, _P, _P, _P],
-    'nele_adam_step': [_P, _P, _P, _P, c_longlong, c_float, c_float, c_float, c_float, c_int, _P],
-    'nele_adam_step_guarded': [_P, _P, _P, _P, c_longlong, c_float, c_float, c_float, c_float, c_int, _P, _P],
-}
-for _n, _a in _SIGS.items():
-    declare(_n, _a)
-    _lib._SIGS[_n] = _a
-_lib.lib.nele_weight_frag16_elems.argtypes = [c_int, c_int, c_int]
-_lib.lib.nele_weight_frag16_elems.restype = c_longlong
-_lib._SIGS['nele_weight_frag16_elems'] = _lib.lib.nele_weight_frag16_elems.argtypes
-_lib.lib.nele_conv16_wfrag_elems.argtypes = [c_int, c_int, c_int]
-_lib.lib.nele_conv16_wfrag_elems.restype = c_longlong
-_lib._SIGS['nele_conv16_wfrag_elems'] = _lib.lib.nele_conv16_wfrag_elems.argtypes
-for _n in ('nele_glayer16_wfrag_elems', 'nele_glayer16_carry_bytes'):
-    getattr(_lib.lib, _n).argtypes = [c_int, c_int, c_int] if _n.endswith('elems') else [c_int, c_int]
-    getattr(_lib.lib, _n).restype = c_longlong
-    _lib._SIGS[_n] = getattr(_lib.lib, _n).argtypes
-_lib.lib.nele_conv_wgrad_workspace_floats.argtypes = [c_int, c_int, c_int, ctypes.POINTER(c_int)]
-_lib.lib.nele_conv_wgrad_workspace_floats.restype = c_longlong
-_lib._SIGS['nele_conv_wgrad_workspace_floats'] = _lib.lib.nele_conv_wgrad_workspace_floats.argtypes
+from ._lib import c_int, c_longlong, c_void_p, call, ptr, stream
 
 
 def side_stream(device):

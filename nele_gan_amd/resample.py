@@ -22,46 +22,15 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import c_double, c_int, c_longlong, c_void_p, call, ptr, stream
+from ._lib import c_int, c_longlong, c_void_p, call, ptr, stream
 
 QUALITIES = {'high': (32, 12.0), 'scipy': (10, 5.0)}
-MAX_SAMPLES = 1 << 30                                      # NELE_RESAMPLE_MAX_SAMPLES (include/nele_hip.h)
+MAX_SAMPLES = _lib.CONSTS['NELE_RESAMPLE_MAX_SAMPLES']
 MANIFEST_COLUMNS = ('name', 'sr_in', 'samples_in', 'samples_out', 'peak', 'clipped_samples')
-
-_lib._SIGS.update({
-    'nele_resample_out_len': [c_longlong, c_int, c_int],
-    'nele_resample_taps_count': [c_int, c_int, c_int, c_int],
-    'nele_resample_taps': [c_int, c_int, c_int, c_double, c_int, c_void_p],
-    'nele_resample_tile': [],
-    'nele_resample_var': [c_void_p, c_longlong, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_double, c_void_p, c_longlong,
-                          c_void_p, c_void_p],
-})
-for _n in ('nele_resample_taps', 'nele_resample_tile', 'nele_resample_var'):
-    _lib.declare(_n, _lib._SIGS[_n])
-for _n in ('nele_resample_out_len', 'nele_resample_taps_count'):
-    getattr(_lib.lib, _n).argtypes = _lib._SIGS[_n]
-    getattr(_lib.lib, _n).restype = c_longlong
 
 TILE = int(_lib.lib.nele_resample_tile())                  # outputs per workgroup of the kernel (tests put lengths around it)
 
 # the stream converter of the real-time path (csrc/resample_stream.hip)
-_STREAM_RESTYPES = {'nele_resample_stream_delay': c_int, 'nele_resample_stream_hop_lengths': c_int,
-                    'nele_resample_stream_record_bytes': c_longlong, 'nele_resample_stream_state_bytes': c_longlong,
-                    'nele_resample_stream_init': c_int, 'nele_resample_stream_reset': c_int, 'nele_resample_stream_hop': c_int}
-_lib._SIGS.update({
-    'nele_resample_stream_delay': [c_int, c_int, c_int],
-    'nele_resample_stream_hop_lengths': [c_int, c_int, c_int, c_void_p, c_void_p],
-    'nele_resample_stream_record_bytes': [c_int],
-    'nele_resample_stream_state_bytes': [c_int, c_int],
-    'nele_resample_stream_init': [c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p],
-    'nele_resample_stream_reset': [c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
-    'nele_resample_stream_hop': [c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_longlong, c_void_p, c_int, c_int, c_void_p,
-                                 c_longlong, c_void_p],
-})
-for _n, _r in _STREAM_RESTYPES.items():
-    getattr(_lib.lib, _n).argtypes = _lib._SIGS[_n]
-    getattr(_lib.lib, _n).restype = _r
-
 STREAM_RATE = 16000                                        # the rate of the real-time path: one side of every stream converter
 
 

@@ -13,18 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import c_double, c_int, c_longlong, c_void_p, call, declare, ptr, stream
-
-_P = c_void_p
-for _n, _a in (('nele_rir_bank_prepare', [_P, _P, c_int, c_int, _P, _P]),
-               ('nele_fir_fft_var', [_P, c_int, c_int, _P, _P, _P, _P, _P, _P]),
-               ('nele_norm_clip_var', [_P, _P, _P, c_int, c_int, _P, _P, _P, c_double, _P, _P, _P, _P])):
-    declare(_n, _a)
-    _lib._SIGS[_n] = _a
-for _n in ('nele_rir_bank_bytes', 'nele_fir_fft_workspace_bytes'):
-    getattr(_lib.lib, _n).argtypes = [c_int, c_int]
-    getattr(_lib.lib, _n).restype = c_longlong
-    _lib._SIGS[_n] = [c_int, c_int]
+from ._lib import call, ptr, stream
 
 fs = 16000
 

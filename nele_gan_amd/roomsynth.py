@@ -18,35 +18,21 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import c_double, c_int, c_longlong, c_void_p, call, ptr, stream
+from ._lib import call, ptr, stream
 from .mixing import draw_words
 
-BAD_SIZE, BAD_POSITION, BAD_BETA = 1, 2, 4                 # NELE_RIR_* (include/nele_hip.h)
+BAD_SIZE, BAD_POSITION, BAD_BETA = (_lib.CONSTS['NELE_RIR_BAD_' + _n] for _n in ('SIZE', 'POSITION', 'BETA'))
 FS, C, HALF_WIDTH = 16000, 343.0, 40
-
-_RESTYPES = {'nele_rir_synth_workspace_bytes': c_longlong, 'nele_rir_synth_tile': c_int, 'nele_rir_synth': c_int}
-_lib._SIGS.update({
-    'nele_rir_synth_workspace_bytes': [c_int, c_int],
-    'nele_rir_synth_tile': [],
-    'nele_rir_synth': [c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-})
-_bound = []
 
 
 def library():
-    """The library's three entry points, looked up at first use: importing this module (the training and scoring command lines do, for
-    their options) asks nothing of the library."""
-    if not _bound:
-        for name, restype in _RESTYPES.items():
-            fn = getattr(_lib.lib, name)
-            fn.argtypes, fn.restype = _lib._SIGS[name], restype
-        _bound.append(True)
+    """-> the loaded libnele_hip.so (ctypes), every entry point bound"""
     return _lib.lib
 
 
 def __getattr__(name):
     if name == 'TILE':                                     # taps per workgroup of the kernel (tests put lengths around it)
-        return int(library().nele_rir_synth_tile())
+        return int(_lib.lib.nele_rir_synth_tile())
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -87,7 +73,6 @@ def synth_rirs(rooms, taps, fs=FS, c=C, half_width=HALF_WIDTH, device='cuda', N=
     d_rooms, d_taps = torch.from_numpy(packed).to(dev), torch.from_numpy(t).to(dev)
     h = torch.empty((R, N), dtype=torch.float64, device=dev)
     status = torch.empty((R,), dtype=torch.int32, device=dev)
-    library()
     with torch.cuda.device(dev):
         call('nele_rir_synth', ptr(d_rooms), ptr(d_taps), R, N, float(fs), float(c), int(half_width), ptr(h), ptr(status), None, stream())
         torch.cuda.current_stream().synchronize()            # d_rooms / d_taps die here

@@ -16,9 +16,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import c_double, c_int, c_longlong, c_void_p, call, ptr, stream
+from ._lib import c_double, c_int, call, ptr, stream
 
-MAX_KNOTS = 8                                              # NELE_SSDRC_MAX_KNOTS (include/nele_hip.h)
+MAX_KNOTS = _lib.CONSTS['NELE_SSDRC_MAX_KNOTS']
 MANIFEST_COLUMNS = ('name', 'samples', 'input_rms', 'peak', 'clipped_samples')
 
 
@@ -26,20 +26,6 @@ class nele_ssdrc_params(ctypes.Structure):
     _fields_ = [('shape', c_int), ('compress', c_int), ('lifter_q', c_int), ('n_knots', c_int), ('beta', c_double), ('preemph', c_double),
                 ('attack', c_double), ('release', c_double), ('e0_ratio', c_double), ('knot_in_db', c_double * MAX_KNOTS),
                 ('knot_out_db', c_double * MAX_KNOTS)]
-
-
-_P = ctypes.POINTER(nele_ssdrc_params)
-_lib._SIGS.update({
-    'nele_ssdrc_ws_bytes': [c_int, c_int],
-    'nele_ssdrc_params_default': [_P],
-    'nele_ssdrc': [c_void_p, c_void_p, c_int, c_int, _P, c_void_p, c_void_p, c_void_p],
-    'nele_ssdrc_shape': [c_void_p, c_void_p, c_int, c_int, _P, c_void_p, c_void_p, c_void_p],
-    'nele_ssdrc_compress': [c_void_p, c_void_p, c_int, c_int, _P, c_void_p, c_void_p, c_void_p, c_void_p],
-})
-for _n in ('nele_ssdrc_params_default', 'nele_ssdrc', 'nele_ssdrc_shape', 'nele_ssdrc_compress'):
-    _lib.declare(_n, _lib._SIGS[_n])
-_lib.lib.nele_ssdrc_ws_bytes.argtypes = _lib._SIGS['nele_ssdrc_ws_bytes']
-_lib.lib.nele_ssdrc_ws_bytes.restype = c_longlong
 
 
 @dataclasses.dataclass(frozen=True)
