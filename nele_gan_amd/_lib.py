@@ -86,6 +86,15 @@ def ptr(t):
     return c_void_p(t.data_ptr())
 
 
+def norm_dev(dev):
+    """torch.device('cuda') != torch.device('cuda:0'): an index-less device would make every cache keyed by a device look stale (and
+    re-home model.FlatParams' buffer on every call).  Normalise to the indexed device."""
+    dev = torch.device(dev)
+    if dev.type == 'cuda' and dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    return dev
+
+
 _raw_stream = getattr(torch._C, '_cuda_getCurrentRawStream', None)
 _raw_device = getattr(torch._C, '_cuda_getDevice', None)
 

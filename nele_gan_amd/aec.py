@@ -18,63 +18,30 @@ import torch
 
 from . import _lib
 from ._lib import c_longlong, call, ptr, stream
+from ._slots import SlotState, dev_rows, to_dev
 
 HOP = 256
 MAX_PARTITIONS = _lib.CONSTS['NELE_AEC_MAX_PARTITIONS']
 
 
-def _norm_dev(device):
-    d = torch.device(device)
-    return torch.device('cuda', torch.cuda.current_device()) if d.type == 'cuda' and d.index is None else d
-
-
-class EchoCanceller:
+class EchoCanceller(SlotState):
     """B independent echo cancellers.  partitions: P in 1 .. 32, the echo tail the filter covers is 256 P samples (128 ms at P = 8);
     mu (0 < mu < 2), gamma (>= 0), delta (> 0): the step of DESIGN.md section 14 - the weights move by
     mu E conj(X_p) / (sum_p |X_p|^2 + gamma P S_e + delta), S_e the smoothed power of the residual."""
 
     def __init__(self, streams, partitions=8, mu=0.5, gamma=4.0, delta=1e-2, device='cuda'):
-        self.S, self.P = int(streams), int(partitions)
-        if self.S < 1:
-            raise ValueError("EchoCanceller: streams must be >= 1")
+        super().__init__(streams)
+        self.P = int(partitions)
         if not 1 <= self.P <= MAX_PARTITIONS:
             raise ValueError("EchoCanceller: partitions must be in 1 .. %d (got %d)" % (MAX_PARTITIONS, self.P))
         self.mu, self.gamma, self.delta = float(mu), float(gamma), float(delta)
         if not (0.0 < self.mu < 2.0) or not (self.gamma >= 0.0) or not (self.delta > 0.0):
             raise ValueError("EchoCanceller: needs 0 < mu < 2, gamma >= 0 and delta > 0 (got %g, %g, %g)" % (self.mu, self.gamma, self.delta))
-        self.device = _norm_dev(device)
-        self.nbytes = int(_lib.lib.nele_aec_state_bytes(self.S, self.P))
-        self.state = torch.empty((self.nbytes,), dtype=torch.uint8, device=self.device)
-        self.hops = np.zeros(self.S, dtype=np.int64)
+        self._alloc(device, _lib.lib.nele_aec_state_bytes(self.S, self.P))
         call('nele_aec_init', ptr(self.state), c_longlong(self.nbytes), self.S, self.P, stream())
 
-    # ---- helpers (as RealtimeEnhancer's)
     def _mask(self, flags, name):
-        m = np.asarray(flags, dtype=bool).reshape(-1)
-        if m.shape[0] != self.S:
-            raise ValueError("EchoCanceller: %s must hold one flag per stream" % name)
-        return m
-
-    def _slots_mask(self, slots):
-        m = np.zeros(self.S, dtype=bool)
-        m[np.asarray(slots, dtype=np.int64).reshape(-1)] = True
-        return m
-
-    def _dev_bytes(self, mask):
-        return torch.from_numpy(mask.astype(np.uint8)).pin_memory().to(self.device, non_blocking=True)
-
-    def _dev_f32(self, x, shape, name):
-        if not isinstance(x, torch.Tensor):
-            x = torch.as_tensor(np.asarray(x, dtype=np.float32))
-        if tuple(x.shape) != shape:
-            raise ValueError("EchoCanceller: %s must be %s (got %s)" % (name, shape, tuple(x.shape)))
-        if x.dtype != torch.float32:
-            raise ValueError("EchoCanceller: %s must be float32" % name)
-        if not x.is_cuda:
-            if not x.is_pinned():
-                x = x.pin_memory()
-            x = x.to(self.device, non_blocking=True)
-        return x.contiguous()
+        return self._flags(flags, "EchoCanceller: %s must hold one flag per stream" % name)
 
     # ---- streaming
     def process(self, mic, played, active=None, adapt=None, want_echo=False, out=None):
@@ -111,8 +78,7 @@ class EchoCanceller:
         call('nele_aec_echo_path', ptr(self.state), c_longlong(self.nbytes), self.S, self.P, ptr(h), stream())
         if slots is None:
             return h
-        idx = torch.from_numpy(np.asarray(slots, dtype=np.int64).reshape(-1)).pin_memory().to(self.device, non_blocking=True)
-        return h.index_select(0, idx)
+        return h.index_select(0, self._dev_rows(slots))
 
     def reset(self, slots):
         """Restart the given slots (zero weights, history and S_e); the other slots are not touched."""
@@ -142,16 +108,6 @@ class EchoCancellingEnhancer:
                              % (self.played.shape[1] // HOP, width // HOP))
         return self.played
 
-    def _to_dev(self, t):
-        """host tensor -> the loop's device through pinned memory, without blocking the host (as RealtimeEnhancer's arguments)"""
-        dev = self.played.device
-        if t.device == dev or dev.type != 'cuda':
-            return t.to(dev)
-        return (t if t.is_pinned() else t.pin_memory()).to(dev, non_blocking=True)
-
-    def _rows(self, slots):
-        return self._to_dev(torch.from_numpy(np.asarray(slots, dtype=np.int64).reshape(-1)))
-
     def process(self, clean, mic, active=None, debug=None):
         """clean, mic [streams, nh * 256] float32 -> out [streams, nh * 256] (RealtimeEnhancer.process on the echo-cancelled mic).
         The returned tensor is the caller's: the loop keeps its own copy of what was played.  debug: RealtimeEnhancer's RealtimeDebug."""
@@ -164,7 +120,7 @@ class EchoCancellingEnhancer:
         if active is None:
             played.copy_(out)                              # an owned buffer: later calls and reset() change it in place
         else:
-            rows = self._rows(np.nonzero(np.asarray(active, dtype=bool).reshape(-1))[0])
+            rows = dev_rows(np.nonzero(np.asarray(active, dtype=bool).reshape(-1))[0], played.device)
             played.index_copy_(0, rows, out.index_select(0, rows))
         return out
 
@@ -177,9 +133,9 @@ class EchoCancellingEnhancer:
         if mt.shape[1] > HOP:
             raise ValueError("EchoCancellingEnhancer.finish: tails must be [len(slots), <= 256]")
         played = self._played(HOP if self.played is None else self.played.shape[1])
-        rows = self._rows(slots)
+        rows = dev_rows(slots, played.device)
         mic = torch.zeros((self.S, HOP), dtype=torch.float32, device=played.device)
-        mic[:, :mt.shape[1]].index_copy_(0, rows, self._to_dev(mt))
+        mic[:, :mt.shape[1]].index_copy_(0, rows, to_dev(mt, played.device))
         act = np.zeros(self.S, dtype=bool)
         act[slots] = True
         residual = self.aec.process(mic, played[:, :HOP].contiguous(), active=act)
@@ -187,15 +143,14 @@ class EchoCancellingEnhancer:
         if ct.shape[1] < HOP:
             ct = torch.nn.functional.pad(ct, (0, HOP - ct.shape[1]))
         kw = {} if debug is None else {'debug': debug}
-        return self.rt.finish(slots, self._to_dev(ct), residual.index_select(0, rows), tail_lengths, **kw)
+        return self.rt.finish(slots, to_dev(ct, played.device), residual.index_select(0, rows), tail_lengths, **kw)
 
     def reset(self, slots):
         """Restart the given slots in both objects; they play zeros until their next call."""
         self.rt.reset(slots)
         self.aec.reset(slots)
         if self.played is not None:
-            slots = np.asarray(slots, dtype=np.int64).reshape(-1)
-            self.played.index_fill_(0, self._rows(slots), 0.0)
+            self.played.index_fill_(0, dev_rows(slots, self.played.device), 0.0)
 
 
 # ------------------------------------------------------------------------------------------------------------------ command line

@@ -3,7 +3,6 @@
 // transforms (fft512.h).  The arithmetic is DESIGN.md section 14; tests/aec_ref.py restates it in numpy.
 //   aec_hop_kernel   : one workgroup per stream and call, looping over the call's hops
 //   aec_path_kernel  : the impulse-response estimate, one wave per pair of partitions
-//   aec_reset_kernel : zeroes the records of the chosen slots
 // A spectrum of a real 512-sample signal is 256 double2: slot k = bin k for k = 1 .. 255, slot 0 = (bin 0, bin 256) - both real, so
 // their imaginary parts are zero by construction and products are taken component-wise in slot 0 (as csrc/fftconv.hip).
 // Two real transforms share one complex transform (z = a + i b); the two partitions of a pair share the constraint's inverse and
@@ -12,21 +11,21 @@
 // State is read and written with plain loads and stores by the stream's own workgroup; no atomics, nothing crosses workgroups.
 #include "common.h"
 #include "fft512.h"
+#include "slot_state.h"
 #include "../../include/nele_hip.h"
 
 namespace {
 
 #define AEC_BLK 256                                        // samples per hop = slots per spectrum
 #define AEC_MAXP NELE_AEC_MAX_PARTITIONS
-constexpr long long aec_al(long long x) { return (x + 255) / 256 * 256; }
-constexpr long long AEC_HDR_BYTES = 256;                   // int [0] = max_streams, [1] = partitions (what nele_aec_init was given)
+constexpr long long AEC_HDR_BYTES = SLOT_GEOM_HDR_BYTES;   // int [0] = max_streams, [1] = partitions (what nele_aec_init was given)
 // per-stream record, byte offsets
 constexpr long long AEC_O_HEAD = 0;                        // int: ring position of the newest far-end spectrum X_0
 constexpr long long AEC_O_XPREV = 256;                     // float [256]: the previous hop of `played` (float32 in, kept exactly)
 constexpr long long AEC_O_SE = AEC_O_XPREV + 4 * AEC_BLK;  // double [257 (+ 7)]: S_e
-constexpr long long AEC_O_X = aec_al(AEC_O_SE + 8 * 264);  // double2 [P][256]: ring of far-end spectra, X_p at (head + p) % P
+constexpr long long AEC_O_X = slot_al(AEC_O_SE + 8 * 264);  // double2 [P][256]: ring of far-end spectra, X_p at (head + p) % P
 __host__ __device__ constexpr long long aec_o_w(int P) { return AEC_O_X + 16LL * AEC_BLK * P; }       // double2 [P][256]: W_p
-__host__ __device__ constexpr long long aec_rec_bytes(int P) { return aec_al(AEC_O_X + 2 * 16LL * AEC_BLK * P); }
+__host__ __device__ constexpr long long aec_rec_bytes(int P) { return slot_al(AEC_O_X + 2 * 16LL * AEC_BLK * P); }
 
 struct AecArgs {
     unsigned char* state;
@@ -42,35 +41,6 @@ struct AecArgs {
     float* echo;                 // [S][ld] or null
 };
 
-__device__ __forceinline__ void aec_init_twiddles(double2* tw) {
-    const int k = threadIdx.x;
-    if (k < 256) {
-        double sn, cs;
-        sincospi((double)k / 256.0, &sn, &cs);
-        tw[k] = make_double2(cs, -sn);
-    }
-}
-
-// element n of the transform's input for Za + i Zb, from slot (n <= 256 ? n : 512 - n) & 255 of the spectra of two real signals
-// (a, b) and their slots 0 (a0, b0)
-__device__ __forceinline__ double2 aec_herm_pair(const double2 a, const double2 b, const double2 a0, const double2 b0, int n) {
-    if (n == 0) return make_double2(a0.x, b0.x);
-    if (n == 256) return make_double2(a0.y, b0.y);
-    return (n < 256) ? make_double2(a.x - b.y, a.y + b.x) : make_double2(a.x + b.y, b.x - a.y);
-}
-
-// slot k of the spectra of the two real signals behind Z = FFT(a + i b), Z in natural order in xw (fft512_wave_store)
-__device__ __forceinline__ void aec_split(const double2* __restrict__ xw, int k, double2& xa, double2& xb) {
-    const double2 zk = xw[fftw_slot(k)], zn = xw[fftw_slot((512 - k) & 511)];
-    xa = make_double2(0.5 * (zk.x + zn.x), 0.5 * (zk.y - zn.y));
-    xb = make_double2(0.5 * (zk.y + zn.y), 0.5 * (zn.x - zk.x));
-    if (k == 0) {
-        const double2 z256 = xw[fftw_slot(256)];
-        xa = make_double2(zk.x, z256.x);
-        xb = make_double2(zk.y, z256.y);
-    }
-}
-
 // one wave: spectrum (256 slots, to `out` in LDS) of the real signal whose sample n is val(n)
 template <class Val>
 __device__ __forceinline__ void aec_forward_real(Val val, double2* __restrict__ xw, const double2* __restrict__ tw, int lane,
@@ -84,7 +54,7 @@ __device__ __forceinline__ void aec_forward_real(Val val, double2* __restrict__ 
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
         double2 xa, xb;
-        aec_split(xw, 64 * m + lane, xa, xb);
+        fft512_packed_split(xw, 64 * m + lane, xa, xb);
         out[64 * m + lane] = xa;
     }
 }
@@ -99,8 +69,7 @@ __global__ __launch_bounds__(256) void aec_hop_kernel(AecArgs a) {
     const int b = blockIdx.x, t = threadIdx.x, w = t >> 6, lane = t & 63;
     if (b >= a.S) return;
     if (a.active && !a.active[b]) return;                  // neither read nor written
-    const int* hdr = reinterpret_cast<const int*>(a.state);
-    if (hdr[0] != a.S || hdr[1] != a.P) return;            // not the state nele_aec_init laid out for (S, P): touch nothing
+    if (!slot_hdr_matches(a.state, a.S, a.P)) return;      // not the state nele_aec_init laid out for (S, P): touch nothing
     const int P = a.P;
     unsigned char* rec = a.state + AEC_HDR_BYTES + (size_t)b * aec_rec_bytes(P);
     int* headp = reinterpret_cast<int*>(rec + AEC_O_HEAD);
@@ -113,7 +82,7 @@ __global__ __launch_bounds__(256) void aec_hop_kernel(AecArgs a) {
     const double one_m_smooth = 1.0 - NELE_AEC_SMOOTH;
     double2* xw = xws[w];
 
-    aec_init_twiddles(tw);
+    fft512_fill_twiddles(tw);
     xbuf[t] = xprev[t];
     int head = min(max(*headp, 0), P - 1);
     double se = Sep[t], se_ny = slot0 ? Sep[AEC_BLK] : 0.0;   // S_e of bin t (thread 0: bins 0 and 256)
@@ -171,7 +140,7 @@ __global__ __launch_bounds__(256) void aec_hop_kernel(AecArgs a) {
             for (int r = 0; r < 8; ++r) {
                 const int n = fftw_n(lane, r);
                 const int k = (n <= 256) ? n : 512 - n;
-                v[r] = aec_herm_pair(specB[k & 255], zero, y0, zero, n);
+                v[r] = fft512_packed_join(specB[k & 255], zero, y0, zero, n);
             }
             fftw_wave_sync();
             fft512_wave<true>(v, xw, tw, lane);
@@ -238,7 +207,7 @@ __global__ __launch_bounds__(256) void aec_hop_kernel(AecArgs a) {
                 for (int r = 0; r < 8; ++r) {
                     const int n = fftw_n(lane, r);
                     const int k = ((n <= 256) ? n : 512 - n) & 255;
-                    v[r] = aec_herm_pair(xw[k], xw[AEC_BLK + k], a0, b0, n);
+                    v[r] = fft512_packed_join(xw[k], xw[AEC_BLK + k], a0, b0, n);
                 }
                 fftw_wave_sync();
                 fft512_wave<true>(v, xw, tw, lane);        // v[m] = 512 (g_a + i g_b)[64 m + lane]
@@ -256,7 +225,7 @@ __global__ __launch_bounds__(256) void aec_hop_kernel(AecArgs a) {
                 for (int m = 0; m < 4; ++m) {
                     const int k = 64 * m + lane;
                     double2 da, db;
-                    aec_split(xw, k, da, db);
+                    fft512_packed_split(xw, k, da, db);
                     double2* Wa = Wst + (size_t)p0 * AEC_BLK + k;
                     const double2 wa = *Wa;
                     *Wa = make_double2(wa.x + da.x, wa.y + da.y);
@@ -282,11 +251,10 @@ __global__ __launch_bounds__(256) void aec_hop_kernel(AecArgs a) {
 __global__ __launch_bounds__(256) void aec_path_kernel(const unsigned char* __restrict__ state, int S, int P, double* __restrict__ hout) {
     __shared__ double2 tw[256];
     __shared__ double2 xws[4][FFTW_SLOTS];
-    aec_init_twiddles(tw);
+    fft512_fill_twiddles(tw);
     __syncthreads();
     const int b = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int* hdr = reinterpret_cast<const int*>(state);
-    if (b >= S || hdr[0] != S || hdr[1] != P) return;
+    if (b >= S || !slot_hdr_matches(state, S, P)) return;
     const int p0 = 2 * (blockIdx.y * 4 + w), p1 = p0 + 1;
     if (p0 >= P) return;
     const bool two = p1 < P;
@@ -301,7 +269,7 @@ __global__ __launch_bounds__(256) void aec_path_kernel(const unsigned char* __re
     for (int r = 0; r < 8; ++r) {
         const int n = fftw_n(lane, r);
         const int k = ((n <= 256) ? n : 512 - n) & 255;
-        v[r] = aec_herm_pair(Wa[k], two ? Wb[k] : zero, a0, b0, n);
+        v[r] = fft512_packed_join(Wa[k], two ? Wb[k] : zero, a0, b0, n);
     }
     fft512_wave<true>(v, xw, tw, lane);
     double* hb = hout + (size_t)b * P * AEC_BLK;
@@ -313,34 +281,25 @@ __global__ __launch_bounds__(256) void aec_path_kernel(const unsigned char* __re
     }
 }
 
-// slots == null: every record, and the header
-__global__ void aec_reset_kernel(unsigned char* __restrict__ state, int S, int P, const unsigned char* __restrict__ slots, int write_hdr) {
-    const int b = blockIdx.x;
-    if (write_hdr && b == 0 && threadIdx.x < AEC_HDR_BYTES / 4) {
-        int* hdr = reinterpret_cast<int*>(state);
-        hdr[threadIdx.x] = (threadIdx.x == 0) ? S : (threadIdx.x == 1 ? P : 0);
-    }
-    if (b >= S || (slots && !slots[b])) return;
-    const long long rb = aec_rec_bytes(P);
-    uint4* r = reinterpret_cast<uint4*>(state + AEC_HDR_BYTES + (size_t)b * rb);
-    for (long long i = threadIdx.x; i < rb / 16; i += blockDim.x) r[i] = make_uint4(0u, 0u, 0u, 0u);
+int aec_check(const char* name, const void* state, long long state_bytes, int S, int P) {
+    auto params = [&]() -> int {
+        NELE_CHECK_ARG(P >= 1 && P <= AEC_MAXP, "%s: partitions=%d must be in 1 .. %d", name, P, AEC_MAXP);
+        return NELE_OK;
+    };
+    return slot_state_check(name, state, state_bytes, S, params, nele_aec_state_bytes(S, P), "nele_aec_state_bytes", P);
 }
 
-int aec_check(const char* name, const void* state, long long state_bytes, int S, int P) {
-    NELE_CHECK_ARG(state, "%s: null state", name);
-    NELE_CHECK_ARG(S > 0 && S <= (1 << 20), "%s: max_streams=%d must be in 1 .. 1048576", name, S);
-    NELE_CHECK_ARG(P >= 1 && P <= AEC_MAXP, "%s: partitions=%d must be in 1 .. %d", name, P, AEC_MAXP);
-    NELE_CHECK_ARG(state_bytes >= nele_aec_state_bytes(S, P), "%s: state of %lld bytes is smaller than nele_aec_state_bytes(%d, %d) = %lld", name,
-                   state_bytes, S, P, nele_aec_state_bytes(S, P));
-    NELE_CHECK_ARG(((size_t)state % 256) == 0, "%s: state must be 256-byte aligned", name);
-    return NELE_OK;
+// slots == null: every record; write_hdr: the header too
+int aec_reset(const char* name, void* state, int S, int P, const unsigned char* slots, bool write_hdr, void* stream) {
+    const int hdr[2] = {S, P};
+    return slot_state_reset(name, state, AEC_HDR_BYTES, aec_rec_bytes(P), S, slots, write_hdr ? 2 : 0, hdr, stream);
 }
 
 }  // namespace
 
 // ============================================================================================ C ABI
 extern "C" long long nele_aec_state_bytes(int max_streams, int partitions) {
-    if (max_streams <= 0 || max_streams > (1 << 20) || partitions < 1 || partitions > AEC_MAXP) return -1;
+    if (max_streams <= 0 || max_streams > SLOT_MAX_STREAMS || partitions < 1 || partitions > AEC_MAXP) return -1;
     return AEC_HDR_BYTES + (long long)max_streams * aec_rec_bytes(partitions);
 }
 
@@ -352,18 +311,13 @@ extern "C" long long nele_aec_stream_record_bytes(int partitions) {
 extern "C" int nele_aec_init(void* state, long long state_bytes, int max_streams, int partitions, void* stream) {
     int st = aec_check("nele_aec_init", state, state_bytes, max_streams, partitions);
     if (st) return st;
-    hipLaunchKernelGGL(aec_reset_kernel, dim3(max_streams), dim3(256), 0, as_stream(stream), (unsigned char*)state, max_streams, partitions,
-                       (const unsigned char*)nullptr, 1);
-    NELE_CHECK_LAUNCH("nele_aec_init");
-    return NELE_OK;
+    return aec_reset("nele_aec_init", state, max_streams, partitions, nullptr, true, stream);
 }
 
 extern "C" int nele_aec_reset(void* state, long long state_bytes, int max_streams, int partitions, const unsigned char* slots, void* stream) {
     int st = aec_check("nele_aec_reset", state, state_bytes, max_streams, partitions);
     if (st) return st;
-    hipLaunchKernelGGL(aec_reset_kernel, dim3(max_streams), dim3(256), 0, as_stream(stream), (unsigned char*)state, max_streams, partitions, slots, 0);
-    NELE_CHECK_LAUNCH("nele_aec_reset");
-    return NELE_OK;
+    return aec_reset("nele_aec_reset", state, max_streams, partitions, slots, false, stream);
 }
 
 extern "C" int nele_aec_hop(void* state, long long state_bytes, int max_streams, int partitions, const float* mic, const float* played,

@@ -296,12 +296,8 @@ __global__ __launch_bounds__(256) void estoi_tob_wave_kernel(EstoiWs ws) {
     __shared__ __attribute__((aligned(16))) double2 xs[4][FFTW_SLOTS];
     const int b = blockIdx.y, tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
     const int nk = ws.nkept[b];
-    {
-        double sn, cs;
-        sincospi((double)tid / 256.0, &sn, &cs);
-        tw[tid] = make_double2(cs, -sn);
-        hw[tid] = hann_sym256(tid);
-    }
+    tw[tid] = fft512_twiddle(tid);
+    hw[tid] = hann_sym256(tid);
     __syncthreads();
     if ((int)blockIdx.x * ETW_NP * 4 >= nk) return;
     const int* keep = ws.keep + (size_t)b * ws.F;
@@ -347,10 +343,10 @@ __global__ __launch_bounds__(256) void estoi_tob_wave_kernel(EstoiWs ws) {
         for (int i = 0; i < 4; ++i) {
             const int q = lane + 64 * i;                    // bins 0 .. 255; the bands end at 218
             const double2 zk = xw[fftw_slot(q)], zn = xw[fftw_slot((512 - q) & 511)];
-            const double ar = 0.5 * (zk.x + zn.x), ai = 0.5 * (zk.y - zn.y);
-            const double br = 0.5 * (zk.y + zn.y), bi = 0.5 * (zn.x - zk.x);
-            px[i] = ar * ar + ai * ai;
-            py[i] = br * br + bi * bi;
+            double2 A, Bv;
+            fft512_pair_split(zk, zn, A, Bv);
+            px[i] = A.x * A.x + A.y * A.y;
+            py[i] = Bv.x * Bv.x + Bv.y * Bv.y;
         }
         fftw_wave_sync();                                   // every lane has read its bins
 #pragma unroll

@@ -160,13 +160,9 @@ __global__ __launch_bounds__(256) void stft_band_wave_kernel(const float* __rest
     if (band) band_weights_init(frw, omw);
     int Tb = T;
     if (lens) { L = min(lens[b], L); Tb = 1 + L / NELE_HOP; }
-    {
-        double sn, cs;
-        sincospi((double)tid / 256.0, &sn, &cs);
-        tw[tid] = make_double2(cs, -sn);
-        hw[tid] = hann512(tid);
-        hw[tid + 256] = hann512(tid + 256);
-    }
+    tw[tid] = fft512_twiddle(tid);
+    hw[tid] = hann512(tid);
+    hw[tid + 256] = hann512(tid + 256);
     __syncthreads();
     double2* xw = xs[wv];
     for (int it = 0; it < STW_NP; ++it) {
@@ -203,8 +199,10 @@ __global__ __launch_bounds__(256) void stft_band_wave_kernel(const float* __rest
             const int k = lane + 64 * q;
             if (k < NELE_NBINS) {
                 const double2 zk = xw[fftw_slot(k)], zn = xw[fftw_slot((NELE_NFFT - k) & (NELE_NFFT - 1))];
-                const float2 A = make_float2((float)(0.5 * (zk.x + zn.x)), (float)(0.5 * (zk.y - zn.y)));
-                const float2 Bv = make_float2((float)(0.5 * (zk.y + zn.y)), (float)(0.5 * (zn.x - zk.x)));
+                double2 Ad, Bd;
+                fft512_pair_split(zk, zn, Ad, Bd);
+                const float2 A = make_float2((float)Ad.x, (float)Ad.y);
+                const float2 Bv = make_float2((float)Bd.x, (float)Bd.y);
                 if (spec) {
                     spec[((size_t)b * T + t0) * NELE_NBINS + k] = A;
                     if (has1) spec[((size_t)b * T + t1) * NELE_NBINS + k] = Bv;
@@ -768,13 +766,9 @@ __global__ __launch_bounds__(256) void gain_istft_wave_kernel(const float* __res
         wlo[k] = (float)(1.0 - frac);
         whi[k] = (float)frac;
     }
-    {
-        double sn, cs;
-        sincospi((double)tid / 256.0, &sn, &cs);
-        tw[tid] = make_double2(cs, -sn);
-        hw[tid] = hann512(tid);
-        hw[tid + 256] = hann512(tid + 256);
-    }
+    tw[tid] = fft512_twiddle(tid);
+    hw[tid] = hann512(tid);
+    hw[tid + 256] = hann512(tid + 256);
     __syncthreads();
     double2* xw = xs[wv];
     float* out = wav + (size_t)b * (NELE_HOP * (T - 1));

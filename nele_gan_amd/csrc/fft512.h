@@ -11,13 +11,24 @@ struct Fft512Lds {
 
 __device__ __forceinline__ int fft512_brev(int i) { return (int)(__brev((unsigned)i) >> 23); }
 
-__device__ __forceinline__ void fft512_init_twiddles(Fft512Lds& s) {
+// tw[k] = exp(-2 pi i k / 512) = (cos, -sin)(pi k / 256): the one definition of the table every 512-point transform here reads
+__device__ __forceinline__ double2 fft512_twiddle(int k) {
+    double sn, cs;
+    sincospi((double)k / 256.0, &sn, &cs);
+    return make_double2(cs, -sn);
+}
+// threads 0 .. 255 of the workgroup fill tw[256]; the caller's barrier publishes it
+__device__ __forceinline__ void fft512_fill_twiddles(double2* tw) {
     const int k = threadIdx.x;
-    if (k < 256) {
-        double sn, cs;
-        sincospi((double)k / 256.0, &sn, &cs);
-        s.tw[k] = make_double2(cs, -sn);
-    }
+    if (k < 256) tw[k] = fft512_twiddle(k);
+}
+__device__ __forceinline__ void fft512_init_twiddles(Fft512Lds& s) { fft512_fill_twiddles(s.tw); }
+
+// The spectra of two real signals a, b from ONE complex transform Z = FFT(a + i b), bin k: zk = Z[k], zn = Z[(512 - k) & 511];
+// A[k] = (Z[k] + conj Z[512 - k]) / 2, B[k] = (Z[k] - conj Z[512 - k]) / (2 i).
+__device__ __forceinline__ void fft512_pair_split(const double2 zk, const double2 zn, double2& A, double2& B) {
+    A = make_double2(0.5 * (zk.x + zn.x), 0.5 * (zk.y - zn.y));
+    B = make_double2(0.5 * (zk.y + zn.y), 0.5 * (zn.x - zk.x));
 }
 
 // One radix-2 butterfly, a' = a + w b, b' = a - w b, as eight fused multiply-adds (round 6; ten separate multiplies / adds before - this
@@ -162,4 +173,25 @@ __device__ __forceinline__ void fft512_wave_store(const double2 (&v)[8], double2
 #pragma unroll
     for (int m = 0; m < 8; ++m) xw[72 * m + s0] = v[m];
     fftw_wave_sync();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The packed half spectrum of a real 512-sample signal (csrc/fftconv.hip, csrc/aec.hip): 256 double2, slot k = bin k for k = 1 .. 255,
+// slot 0 = (bin 0, bin 256) - both real, so products are taken component-wise in slot 0.
+// Split: slot k of the packed spectra of the two real signals behind Z = FFT(a + i b), Z in natural order in xw (fft512_wave_store).
+__device__ __forceinline__ void fft512_packed_split(const double2* __restrict__ xw, int k, double2& xa, double2& xb) {
+    const double2 zk = xw[fftw_slot(k)], zn = xw[fftw_slot((512 - k) & 511)];
+    fft512_pair_split(zk, zn, xa, xb);
+    if (k == 0) {
+        const double2 z256 = xw[fftw_slot(256)];
+        xa = make_double2(zk.x, z256.x);
+        xb = make_double2(zk.y, z256.y);
+    }
+}
+// Join (the Hermitian extension for the inverse): element n of the transform's input for Za + i Zb, from slot
+// (n <= 256 ? n : 512 - n) & 255 of the packed spectra of two real signals (a, b) and their slots 0 (a0, b0).
+__device__ __forceinline__ double2 fft512_packed_join(const double2 a, const double2 b, const double2 a0, const double2 b0, int n) {
+    if (n == 0) return make_double2(a0.x, b0.x);
+    if (n == 256) return make_double2(a0.y, b0.y);
+    return (n < 256) ? make_double2(a.x - b.y, a.y + b.x) : make_double2(a.x + b.y, b.x - a.y);
 }

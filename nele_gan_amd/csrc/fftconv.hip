@@ -22,17 +22,8 @@ __host__ __device__ static inline const int* fc_bank_npart(const void* bank, int
     return (const int*)((const char*)bank + FC_HDR_BYTES + (size_t)R * Pmax * FC_BLK * sizeof(double2));
 }
 
-__device__ __forceinline__ void fc_init_twiddles(double2* tw) {
-    const int k = threadIdx.x;
-    if (k < 256) {
-        double sn, cs;
-        sincospi((double)k / 256.0, &sn, &cs);
-        tw[k] = make_double2(cs, -sn);
-    }
-}
-
-// One wave: the spectra of two real 512-sample segments a, b (seg(0, n), seg(1, n)) from ONE complex transform of a + i b:
-// A[k] = (Z[k] + conj Z[512 - k]) / 2, B[k] = (Z[k] - conj Z[512 - k]) / (2 i).  Xb may be NULL.
+// One wave: the packed spectra of two real 512-sample segments a, b (seg(0, n), seg(1, n)) from ONE complex transform of a + i b
+// (fft512_packed_split).  Xb may be NULL.
 template <class Seg>
 __device__ __forceinline__ void fc_forward_pair(Seg seg, double2* __restrict__ xw, const double2* __restrict__ tw, int lane,
                                                 double2* __restrict__ Xa, double2* __restrict__ Xb) {
@@ -44,17 +35,11 @@ __device__ __forceinline__ void fc_forward_pair(Seg seg, double2* __restrict__ x
     }
     fft512_wave<false>(v, xw, tw, lane);
     fft512_wave_store(v, xw, lane);
-    const double2 z256 = xw[fftw_slot(256)];
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
         const int k = 64 * m + lane;
-        const double2 zk = xw[fftw_slot(k)], zn = xw[fftw_slot((512 - k) & 511)];
-        double2 xa = make_double2(0.5 * (zk.x + zn.x), 0.5 * (zk.y - zn.y));
-        double2 xb = make_double2(0.5 * (zk.y + zn.y), 0.5 * (zn.x - zk.x));
-        if (k == 0) {
-            xa = make_double2(zk.x, z256.x);
-            xb = make_double2(zk.y, z256.y);
-        }
+        double2 xa, xb;
+        fft512_packed_split(xw, k, xa, xb);
         Xa[k] = xa;
         if (Xb) Xb[k] = xb;
     }
@@ -66,7 +51,7 @@ __global__ __launch_bounds__(256) void fc_bank_kernel(const double* __restrict__
                                                       int Pmax, int* __restrict__ hdr, double2* __restrict__ H) {
     __shared__ double2 tw[256];
     __shared__ double2 xws[4][FFTW_SLOTS];
-    fc_init_twiddles(tw);
+    fft512_fill_twiddles(tw);
     __syncthreads();
     const int r = blockIdx.y, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int nt = min(max(taps[r], 1), Lhmax);
@@ -95,7 +80,7 @@ __global__ __launch_bounds__(256) void fc_forward_kernel(const float* __restrict
                                                          double2* __restrict__ X) {
     __shared__ double2 tw[256];
     __shared__ double2 xws[4][FFTW_SLOTS];
-    fc_init_twiddles(tw);
+    fft512_fill_twiddles(tw);
     __syncthreads();
     const int b = blockIdx.y, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int len = fc_row_length(lengths, b, Lmax);
@@ -140,7 +125,7 @@ __global__ __launch_bounds__(256) void fc_mac_inverse_kernel(const double2* __re
         for (int i = j0 * FC_BLK + t; i < min(Lmax, (j0 + FC_TILE) * FC_BLK); i += 256) yb[i] = 0.0;
         return;
     }
-    fc_init_twiddles(tw);
+    fft512_fill_twiddles(tw);
     const int P = min(fc_bank_npart(hdr, R, Pmax)[ri], Pmax);
     const int pend = min(P, j0 + FC_TILE);                   // X_i = 0 for i < 0
     const double2* Xb = X + (size_t)b * T * FC_BLK + t;
@@ -178,11 +163,7 @@ __global__ __launch_bounds__(256) void fc_mac_inverse_kernel(const double2* __re
     for (int r = 0; r < 8; ++r) {
         const int n = fftw_n(lane, r);
         const int k = (n <= 256) ? n : 512 - n;
-        const double2 ya = xw[k & 255], yb2 = xw[FC_BLK + (k & 255)];
-        double2 wv = (n < 256) ? make_double2(ya.x - yb2.y, ya.y + yb2.x) : make_double2(ya.x + yb2.y, yb2.x - ya.y);
-        if (n == 0) wv = make_double2(a0.x, b0.x);
-        if (n == 256) wv = make_double2(a0.y, b0.y);
-        v[r] = wv;
+        v[r] = fft512_packed_join(xw[k & 255], xw[FC_BLK + (k & 255)], a0, b0, n);
     }
     fftw_wave_sync();                                        // the wave's reads of Y precede the transform's writes to the same LDS
     fft512_wave<true>(v, xw, tw, lane);

@@ -13,6 +13,7 @@
 // This file is compiled with -ffp-contract=off (Makefile EXACT): the feature and IMCRA arithmetic mirrors numpy's operation order.
 #include "common.h"
 #include "fft512.h"
+#include "slot_state.h"
 #include "../../include/nele_hip.h"
 
 namespace {
@@ -45,9 +46,8 @@ __host__ __device__ constexpr long long rt_woff(int l) {
 constexpr long long RT_NW = rt_woff(6);
 
 // ---- state buffer: [weights area][stream record 0][stream record 1] ...
-constexpr long long rt_al(long long x) { return (x + 255) / 256 * 256; }
-constexpr long long RT_W_BYTES = rt_al(4 * RT_NW);                    // conv weights (float32 size; bf16 uses the first half)
-constexpr long long RT_P_BYTES = rt_al(4 * RT_NPARAMS);               // copy of the flat parameters (biases, cLN affine, fc)
+constexpr long long RT_W_BYTES = slot_al(4 * RT_NW);                  // conv weights (float32 size; bf16 uses the first half)
+constexpr long long RT_P_BYTES = slot_al(4 * RT_NPARAMS);             // copy of the flat parameters (biases, cLN affine, fc)
 constexpr long long RT_HDR_BYTES = RT_W_BYTES + RT_P_BYTES;
 
 #define RT_RING 8                                                     // history frames kept per layer input (>= taps + 1)
@@ -64,12 +64,12 @@ struct RtHead {
 constexpr long long RT_O_HEAD = 0;
 constexpr long long RT_O_CLN = 32;                                    // double [6][2][2]: running (sum, sum of squares) per layer, by frame parity
 constexpr long long RT_O_NSUM = RT_O_CLN + 8 * 24;                    // double [2]: sum P, sum mask P (prefix normalisation)
-constexpr long long RT_O_IMD = rt_al(RT_O_NSUM + 16);                 // double [26][RT_NB]: IMCRA per-bin state
+constexpr long long RT_O_IMD = slot_al(RT_O_NSUM + 16);               // double [26][RT_NB]: IMCRA per-bin state
 constexpr int RT_NIMD = 26;
 constexpr long long RT_O_LAM32 = RT_O_IMD + 8LL * RT_NIMD * RT_NB;    // float [RT_NB]
-constexpr long long RT_O_XR = rt_al(RT_O_LAM32 + 4 * RT_NB);          // float [2][3][256]: input ring (clean, noise) by hop % 3
+constexpr long long RT_O_XR = slot_al(RT_O_LAM32 + 4 * RT_NB);        // float [2][3][256]: input ring (clean, noise) by hop % 3
 constexpr long long RT_O_SPEC = RT_O_XR + 4 * 2 * 3 * 256;            // float2 [2][257]: clean spectrum by frame parity
-constexpr long long RT_O_CB = rt_al(RT_O_SPEC + 8 * 2 * 257);         // float [2][64]: clean band ** 1/6 by frame parity
+constexpr long long RT_O_CB = slot_al(RT_O_SPEC + 8 * 2 * 257);       // float [2][64]: clean band ** 1/6 by frame parity
 constexpr long long RT_O_A2 = RT_O_CB + 4 * 128;                      // float [2][64]: alpha^2 by frame parity
 __host__ __device__ constexpr long long rt_act_off(int l) {            // float [RT_RING][Cin]: layer l's input rows by frame % RT_RING
     long long o = RT_O_A2 + 4 * 128;
@@ -81,7 +81,7 @@ __host__ __device__ constexpr long long rt_y_off(int l) {              // float 
     for (int i = 0; i < l; ++i) o += 4LL * 2 * rt_nout(i);
     return o;
 }
-constexpr long long RT_REC_BYTES = rt_al(rt_y_off(6));
+constexpr long long RT_REC_BYTES = slot_al(rt_y_off(6));
 
 // IMCRA per-bin double fields
 enum { IM_S = 0, IM_TS, IM_SMIN, IM_TSMIN, IM_SMINSW, IM_TSMINSW, IM_OVL, IM_LAM64, IM_G, IM_GAMMA, IM_ST = 10, IM_TST = 18 };
@@ -252,8 +252,10 @@ __global__ __launch_bounds__(RT_FRONT_THREADS) void rt_front_kernel(RtArgs a) {
         float Y2f = 0.f;
         if (bin) {
             const double2 zk = s.x[k], zn = s.x[(NELE_NFFT - k) & (NELE_NFFT - 1)];
-            const float2 A = make_float2((float)(0.5 * (zk.x + zn.x)), (float)(0.5 * (zk.y - zn.y)));
-            const float2 Bv = make_float2((float)(0.5 * (zk.y + zn.y)), (float)(0.5 * (zn.x - zk.x)));
+            double2 Ad, Bd;
+            fft512_pair_split(zk, zn, Ad, Bd);
+            const float2 A = make_float2((float)Ad.x, (float)Ad.y);
+            const float2 Bv = make_float2((float)Bd.x, (float)Bd.y);
             specr[(f & 1) * NELE_NBINS + k] = A;
             const float m0 = rt_cabsf(A.x, A.y), m1 = rt_cabsf(Bv.x, Bv.y);
             pc[k] = m0 * m0;
@@ -637,19 +639,8 @@ __global__ void rt_weights_kernel(const float* __restrict__ params, unsigned cha
     }
 }
 
-__global__ void rt_reset_kernel(unsigned char* __restrict__ state, int S, const unsigned char* __restrict__ slots) {
-    const int b = blockIdx.x;
-    if (b >= S || (slots && !slots[b])) return;
-    unsigned* r = reinterpret_cast<unsigned*>(state + RT_HDR_BYTES + (size_t)b * RT_REC_BYTES);
-    for (long long i = threadIdx.x; i < RT_REC_BYTES / 4; i += blockDim.x) r[i] = 0u;
-}
-
 int rt_check(const char* name, void* state, long long state_bytes, int S, int prec) {
-    NELE_CHECK_ARG(state, "%s: null state", name);
-    NELE_CHECK_ARG(S > 0 && S <= (1 << 20), "%s: max_streams=%d must be in 1 .. 1048576", name, S);
-    NELE_CHECK_ARG(state_bytes >= nele_rt_state_bytes(S), "%s: state of %lld bytes is smaller than nele_rt_state_bytes(%d) = %lld", name, state_bytes, S,
-                   nele_rt_state_bytes(S));
-    NELE_CHECK_ARG(((size_t)state % 256) == 0, "%s: state must be 256-byte aligned", name);
+    if (int st = slot_state_check(name, state, state_bytes, S, [] { return NELE_OK; }, nele_rt_state_bytes(S), "nele_rt_state_bytes")) return st;
     NELE_CHECK_ARG(prec == NELE_PREC_F32 || prec == NELE_PREC_BF16, "%s: precision=%d (0: f32, 1: bf16)", name, prec);
     return NELE_OK;
 }
@@ -674,7 +665,7 @@ void rt_launch_chain(const RtArgs& a, hipStream_t st) {
 
 // ============================================================================================ C ABI
 extern "C" long long nele_rt_state_bytes(int max_streams) {
-    if (max_streams <= 0 || max_streams > (1 << 20)) return -1;
+    if (max_streams <= 0 || max_streams > SLOT_MAX_STREAMS) return -1;
     return RT_HDR_BYTES + (long long)max_streams * RT_REC_BYTES;
 }
 
@@ -692,9 +683,8 @@ extern "C" int nele_rt_set_weights(void* state, long long state_bytes, int max_s
 extern "C" int nele_rt_reset(void* state, long long state_bytes, int max_streams, const unsigned char* slots, void* stream) {
     int st = rt_check("nele_rt_reset", state, state_bytes, max_streams, NELE_PREC_F32);
     if (st) return st;
-    hipLaunchKernelGGL(rt_reset_kernel, dim3(max_streams), dim3(256), 0, as_stream(stream), (unsigned char*)state, max_streams, slots);
-    NELE_CHECK_LAUNCH("nele_rt_reset");
-    return NELE_OK;
+    // no header write: what precedes the records here is the weights area
+    return slot_state_reset("nele_rt_reset", state, RT_HDR_BYTES, RT_REC_BYTES, max_streams, slots, 0, nullptr, stream);
 }
 
 extern "C" int nele_rt_init(void* state, long long state_bytes, int max_streams, const float* params_flat, int precision, void* stream) {

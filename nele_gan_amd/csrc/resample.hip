@@ -12,20 +12,10 @@
 // bits depend on its samples alone: not on R, Lmax_out, row_ids or where a tile starts.  n down is 64-bit (2^31 is passed after 4.9 M
 // outputs at 160 / 441).  No atomics, no workspace.
 #include "common.h"
+#include "resample_poly.h"
 #include <cmath>
 #include <vector>
 #include "../../include/nele_hip.h"
-
-#define RS_TILE 256                    // outputs per workgroup = threads per workgroup
-#define RS_TAB_LDS_BYTES 16384         // tables up to this size are staged in LDS beside the input span
-#define RS_MAX_RATIO 16
-#define RS_MAX_FACTOR 1024
-#define RS_MAX_ZEROS 64
-
-// input samples a tile can touch: q_last - q_first <= floor((RS_TILE - 1) down / up) + 1, and K - 1 more in front of q_first.
-// At the extreme allowed ratio (down = 16 up, zeros = 64: K = 2049) 255 * 16 + 2049 + 1 = 6130 doubles = 49040 bytes; with the largest
-// LDS table 65424 bytes - inside the 64 KiB a launch gets without an attribute.
-__host__ __device__ static inline int rs_span(int up, int down, int K) { return (int)(((long long)(RS_TILE - 1) * down) / up) + K + 1; }
 
 template <bool TAB_LDS>
 __global__ __launch_bounds__(RS_TILE) void resample_kernel(const float* __restrict__ x, long long x_stride, const int* __restrict__ lengths_in,
@@ -63,28 +53,18 @@ __global__ __launch_bounds__(RS_TILE) void resample_kernel(const float* __restri
         const int p = (int)(c % up);
         const double* __restrict__ hrow = (TAB_LDS ? (const double*)tab : hp) + (size_t)p * K;
         const double* __restrict__ xq = xs + (int)(c / up - base);            // x[q]; x[q - k] = xq[-k], 0 <= index < span
-#pragma unroll 8
-        for (int k = 0; k < K; ++k) acc = fma(hrow[k], xq[-k], acc);
+        acc = rs_dot(hrow, xq, K);
     }
     yr[n] = n < n_out ? (float)(gain * acc) : 0.f;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------- host
-static int rs_check_ratio(const char* name, int up, int down) {
-    NELE_CHECK_ARG(up >= 1 && up <= RS_MAX_FACTOR && down >= 1 && down <= RS_MAX_FACTOR, "%s: up=%d or down=%d outside 1 .. %d", name, up, down,
-                   RS_MAX_FACTOR);
-    NELE_CHECK_ARG(down <= RS_MAX_RATIO * up && up <= RS_MAX_RATIO * down, "%s: up=%d / down=%d outside 1/%d .. %d", name, up, down, RS_MAX_RATIO,
-                   RS_MAX_RATIO);
-    return NELE_OK;
-}
 static int rs_check_design(const char* name, int up, int down, int zeros, int layout) {
     if (int st = rs_check_ratio(name, up, down)) return st;
     NELE_CHECK_ARG(zeros >= 1 && zeros <= RS_MAX_ZEROS, "%s: zeros=%d outside 1 .. %d", name, zeros, RS_MAX_ZEROS);
     NELE_CHECK_ARG(layout == 0 || layout == 1, "%s: layout=%d is neither 0 (natural order) nor 1 (polyphase table)", name, layout);
     return NELE_OK;
 }
-static inline int rs_half(int up, int down, int zeros) { return zeros * (up > down ? up : down); }
-static inline int rs_K(int up, int half) { return (2 * half + 1 + up - 1) / up; }
 
 // modified Bessel function I0 by its power series sum_k ((x / 2)^k / k!)^2 (all terms positive: no cancellation; x <= 20 needs ~45 terms)
 static double rs_i0(double x) {
@@ -158,9 +138,7 @@ extern "C" int nele_resample_var(const float* x, long long x_stride, const int* 
     NELE_CHECK_ARG(x_stride >= 1 && y_stride >= Lmax_out, "%s: x_stride=%lld below 1 or y_stride=%lld below Lmax_out=%d", name, x_stride, y_stride,
                    Lmax_out);
     NELE_CHECK_ARG(std::isfinite(gain), "%s: gain is not finite", name);
-    int zeros = 0;
-    for (int z = 1; z <= RS_MAX_ZEROS && !zeros; ++z)
-        if (rs_K(up, rs_half(up, down, z)) == K) zeros = z;
+    const int zeros = rs_zeros_of(up, down, K);
     NELE_CHECK_ARG(zeros, "%s: K=%d is not the table width of up=%d, down=%d for any zeros in 1 .. %d", name, K, up, down, RS_MAX_ZEROS);
     const int half = rs_half(up, down, zeros), span = rs_span(up, down, K);
     const bool tab_lds = (long long)up * K * (long long)sizeof(double) <= RS_TAB_LDS_BYTES;

@@ -90,15 +90,6 @@ __global__ __launch_bounds__(1024) void ssdrc_voicing_kernel(const float* __rest
         for (int t = wv; t < nfr; t += 16) pb[t] = vmax > 0.0 ? pb[t] / vmax : 0.0;               // (the thread reads what it wrote itself)
 }
 
-__device__ __forceinline__ void ss_init_twiddles(double2* tw) {
-    const int k = threadIdx.x;
-    if (k < 256) {
-        double sn, cs;
-        sincospi((double)k / 256.0, &sn, &cs);
-        tw[k] = make_double2(cs, -sn);
-    }
-}
-
 // the natural-order array the wave left in xw (fft512_wave_store) -> the transform's input order
 __device__ __forceinline__ void ss_restage(double2 (&v)[8], double2* __restrict__ xw, int lane) {
     fft512_wave_store(v, xw, lane);
@@ -114,7 +105,7 @@ __global__ __launch_bounds__(256) void ssdrc_shape_kernel(const float* __restric
                                                           double g, double* __restrict__ fr) {
     __shared__ double2 tw[256];
     __shared__ double2 xws[4][FFTW_SLOTS];
-    ss_init_twiddles(tw);
+    fft512_fill_twiddles(tw);
     __syncthreads();
     const int b = blockIdx.y, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int len = ss_row_length(lengths, b, Lmax), nfr = ss_frames(len);
@@ -141,8 +132,7 @@ __global__ __launch_bounds__(256) void ssdrc_shape_kernel(const float* __restric
     for (int m = 0; m < 8; ++m) {
         const int k = 64 * m + lane;
         const double2 zk = v[m], zn = xw[fftw_slot((SS_N - k) & (SS_N - 1))];
-        Xa[m] = make_double2(0.5 * (zk.x + zn.x), 0.5 * (zk.y - zn.y));
-        Xb[m] = make_double2(0.5 * (zk.y + zn.y), 0.5 * (zn.x - zk.x));
+        fft512_pair_split(zk, zn, Xa[m], Xb[m]);
         v[m] = make_double2(0.5 * log(fmax(Xa[m].x * Xa[m].x + Xa[m].y * Xa[m].y, 1e-20)),
                             0.5 * log(fmax(Xb[m].x * Xb[m].x + Xb[m].y * Xb[m].y, 1e-20)));
     }

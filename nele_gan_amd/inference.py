@@ -35,7 +35,7 @@ class Enhancer:
         enh / rms(enh) * 0.03 and PCM_16 are the same in both modes."""
         if norm is not None:
             M.check_norm(norm, 'Enhancer')
-        self.device = M._norm_dev(device)
+        self.device = _lib.norm_dev(device)
         self.G = G if G is not None else M.Generator_Conv1D_cLN()
         recorded = 'utterance'
         if chkpt_path is not None:

@@ -22,7 +22,7 @@ from torch.nn.utils import spectral_norm
 
 from . import ops
 from . import _lib
-from ._lib import c_longlong, c_void_p, call, ptr, stream
+from ._lib import c_longlong, c_void_p, call, norm_dev, ptr, stream
 
 
 # ------------------------------------------------------------------ parameter containers (reference names)
@@ -67,15 +67,6 @@ def _prec_code(precision):
     return _PREC_CODES.get(precision, 0)
 
 
-def _norm_dev(dev):
-    """torch.device('cuda') != torch.device('cuda:0'): an index-less device would make every cache below look stale (and re-home the
-    flat parameter buffer on every call).  Normalise to the indexed device."""
-    dev = torch.device(dev)
-    if dev.type == 'cuda' and dev.index is None:
-        dev = torch.device('cuda', torch.cuda.current_device())
-    return dev
-
-
 class FlatParams:
     """All parameters of a module as views into ONE flat buffer (+ one flat gradient buffer)."""
 
@@ -95,7 +86,7 @@ class FlatParams:
         ADDING a parameter to a module after its first forward pass is not supported."""
         if self.flat is None or self._plist is None:
             return False
-        device = _norm_dev(device)
+        device = norm_dev(device)
         if self.flat.device != device:
             return False
         f0, g0 = self.flat.data_ptr(), self.grad.data_ptr()
@@ -106,7 +97,7 @@ class FlatParams:
         return True
 
     def ensure(self, device):
-        device = _norm_dev(device)
+        device = norm_dev(device)
         if self.valid(device):
             return
         ps = self.params()
@@ -146,7 +137,7 @@ class _Anchor:
         self.t = None
 
     def get(self, device):
-        device = _norm_dev(device)
+        device = norm_dev(device)
         if self.t is None or self.t.device != device:
             self.t = torch.zeros(1, device=device, requires_grad=True)
         return self.t
@@ -303,7 +294,7 @@ class Generator_Conv1D_cLN(nn.Module):
         current parameters once, at its first forward pass from now on.  For evaluation loops whose parameters do not change
         (inference.py:79-117): forward passes on several streams then only READ their layouts.  Returns an event recorded on the current
         stream."""
-        dev = _norm_dev(dev or next(self.parameters()).device)
+        dev = norm_dev(dev or next(self.parameters()).device)
         self._flat.ensure(dev)
         self._freeze_gen += 1
         self._weights_frozen = True
@@ -315,7 +306,7 @@ class Generator_Conv1D_cLN(nn.Module):
         self._weights_frozen = False
 
     def _workspace(self, B, T, dev, need_bwd):
-        key = (B, T, str(_norm_dev(dev)), self.buffer_slot, self.precision, bool(need_bwd))
+        key = (B, T, str(norm_dev(dev)), self.buffer_slot, self.precision, bool(need_bwd))
         fl = self._flat
 
         def make():
@@ -475,7 +466,7 @@ class _DiscriminatorBase(nn.Module):
         return (c_void_p * 16)(*[t.data_ptr() for m in self._sn_modules() for t in (m.weight_u, m.weight_v)])
 
     def _workspace(self, B, T, dev):
-        key = (B, T, str(_norm_dev(dev)), self.precision)
+        key = (B, T, str(norm_dev(dev)), self.precision)
         fl = self._flat
         uv = self.sn_uv_host()
         owner = (fl.flat.data_ptr(), fl.grad.data_ptr()) + tuple(uv)
@@ -517,7 +508,7 @@ class _DiscriminatorBase(nn.Module):
         single-GPU run of the same steps would hold."""
         if not self.training:
             return
-        dev = _norm_dev(dev or next(self.parameters()).device)
+        dev = norm_dev(dev or next(self.parameters()).device)
         self._flat.ensure(dev)
         if self._sigma is None or self._sigma.device != dev:
             self._sigma = torch.zeros(8, device=dev)         # (every forward pass computes its own sigma again)

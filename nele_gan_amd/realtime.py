@@ -16,6 +16,7 @@ import torch
 from . import _lib
 from . import model as M
 from ._lib import c_longlong, call, ptr, stream
+from ._slots import SlotState
 
 HOP = 256
 NB = 64
@@ -47,7 +48,7 @@ def advance(hops, emitted, live, nh):
     hops[live] += nh
 
 
-class RealtimeEnhancer:
+class RealtimeEnhancer(SlotState):
     """B independent real-time streams.
 
     chkpt_path / G: the generator (a checkpoint with an 'enhance-model' entry, or a ``model.Generator_Conv1D_cLN``); random weights when
@@ -61,18 +62,14 @@ class RealtimeEnhancer:
     def __init__(self, chkpt_path=None, G=None, streams=1, precision='bf16', norm='prefix', device='cuda'):
         if precision not in _PREC:
             raise ValueError("RealtimeEnhancer: precision must be 'f32' or 'bf16' (got %r)" % (precision,))
-        self.S = int(streams)
-        if self.S < 1:
-            raise ValueError("RealtimeEnhancer: streams must be >= 1")
-        self.device = M._norm_dev(device)
+        super().__init__(streams)
+        self._alloc(device, _lib.lib.nele_rt_state_bytes(self.S))
         self.precision = precision
         self.prec = _PREC[precision]
         if G is None:
             G = M.Generator_Conv1D_cLN()
             if chkpt_path is not None:
                 G.load_state_dict(torch.load(chkpt_path, map_location='cpu')['enhance-model'])
-        self.nbytes = int(_lib.lib.nele_rt_state_bytes(self.S))
-        self.state = torch.empty((self.nbytes,), dtype=torch.uint8, device=self.device)
         if isinstance(norm, str):
             if norm != 'prefix':
                 raise ValueError("RealtimeEnhancer: norm must be 'prefix' or a tensor of beta^2 per stream")
@@ -82,7 +79,6 @@ class RealtimeEnhancer:
             if b2.numel() != self.S:
                 raise ValueError("RealtimeEnhancer: norm tensor must hold one beta^2 per stream (%d)" % self.S)
             self.beta2 = b2.to(self.device).contiguous()
-        self.hops = np.zeros(self.S, dtype=np.int64)
         self.emitted = np.zeros(self.S, dtype=np.int64)
         self.finished = np.zeros(self.S, dtype=bool)
         self._params = None
@@ -101,28 +97,6 @@ class RealtimeEnhancer:
         """Take the current parameters of generator G (e.g. after a training step); the streams' state is kept."""
         self._load(G, init=False)
 
-    # ---- helpers
-    def _slots_mask(self, slots):
-        m = np.zeros(self.S, dtype=bool)
-        m[np.asarray(slots, dtype=np.int64).reshape(-1)] = True
-        return m
-
-    def _dev_bytes(self, mask):
-        return torch.from_numpy(mask.astype(np.uint8)).pin_memory().to(self.device, non_blocking=True)
-
-    def _dev_f32(self, x, shape, name):
-        if not isinstance(x, torch.Tensor):
-            x = torch.as_tensor(np.asarray(x, dtype=np.float32))
-        if tuple(x.shape) != shape:
-            raise ValueError("RealtimeEnhancer: %s must be %s (got %s)" % (name, shape, tuple(x.shape)))
-        if x.dtype != torch.float32:
-            raise ValueError("RealtimeEnhancer: %s must be float32" % name)
-        if not x.is_cuda:
-            if not x.is_pinned():
-                x = x.pin_memory()
-            x = x.to(self.device, non_blocking=True)
-        return x.contiguous()
-
     # ---- streaming
     def process(self, clean, noise, active=None, debug=None):
         """clean, noise [streams, nh * 256] float32 (host, pinned host or device) -> out [streams, nh * 256] on the device.
@@ -134,9 +108,8 @@ class RealtimeEnhancer:
         nh = clean.shape[1] // HOP
         c = self._dev_f32(clean, (self.S, nh * HOP), 'clean')
         n = self._dev_f32(noise, (self.S, nh * HOP), 'noise')
-        act_host = np.ones(self.S, dtype=bool) if active is None else np.asarray(active, dtype=bool).reshape(-1)
-        if act_host.shape[0] != self.S:
-            raise ValueError("RealtimeEnhancer.process: active must hold one flag per stream")
+        act_host = np.ones(self.S, dtype=bool) if active is None \
+            else self._flags(active, "RealtimeEnhancer.process: active must hold one flag per stream")
         act = None if active is None else self._dev_bytes(act_host)
         out = torch.empty((self.S, nh * HOP), dtype=torch.float32, device=self.device)
         dbg = debug.args() if debug is not None else _nodbg()

@@ -23,6 +23,7 @@ import torch
 
 from . import _lib
 from ._lib import c_int, c_longlong, c_void_p, call, ptr, stream
+from ._slots import SlotState
 
 QUALITIES = {'high': (32, 12.0), 'scipy': (10, 5.0)}
 MAX_SAMPLES = _lib.CONSTS['NELE_RESAMPLE_MAX_SAMPLES']
@@ -61,13 +62,18 @@ def out_len(n_in, up, down):
     return n
 
 
-def taps(up, down, zeros=32, beta=12.0, layout=0):
-    """The filter as the library designs it on the host (nele_resample_taps), float64: layout 0 the taps h[0 .. 2 half] in natural order,
-    layout 1 the polyphase table hp[up][K]."""
+def taps_count(up, down, zeros, layout):
+    """2 half + 1 taps (layout 0) or the up * K entries of the polyphase table (layout 1), as the library counts them"""
     n = int(_lib.lib.nele_resample_taps_count(int(up), int(down), int(zeros), int(layout)))
     if n < 0:
         _lib.check(-1, 'nele_resample_taps_count')
-    out = np.empty(n, dtype=np.float64)
+    return n
+
+
+def taps(up, down, zeros=32, beta=12.0, layout=0):
+    """The filter as the library designs it on the host (nele_resample_taps), float64: layout 0 the taps h[0 .. 2 half] in natural order,
+    layout 1 the polyphase table hp[up][K]."""
+    out = np.empty(taps_count(up, down, zeros, layout), dtype=np.float64)
     call('nele_resample_taps', int(up), int(down), int(zeros), float(beta), int(layout), c_void_p(out.ctypes.data))
     return out.reshape(int(up), -1) if layout == 1 else out
 
@@ -149,12 +155,11 @@ def stream_plan(sr_in, sr_out, quality='high'):
         _lib.check(-1, 'nele_resample_stream_delay')
     if delay > n_out.value:
         raise ValueError("StreamResampler: the filter's delay of %d output samples is longer than a hop of %d" % (delay, n_out.value))
-    half = zeros * max(up, down)
-    return {'up': up, 'down': down, 'zeros': zeros, 'beta': beta, 'K': -(-(2 * half + 1) // up), 'hop_in': n_in.value, 'hop_out': n_out.value,
-            'delay': delay}
+    K = taps_count(up, down, zeros, 1) // up                # the table is hp[up][K]
+    return {'up': up, 'down': down, 'zeros': zeros, 'beta': beta, 'K': K, 'hop_in': n_in.value, 'hop_out': n_out.value, 'delay': delay}
 
 
-class StreamResampler:
+class StreamResampler(SlotState):
     """``streams`` independent live streams from sr_in to sr_out, hop by hop (csrc/resample_stream.hip; the arithmetic is DESIGN.md
     section 15).  One side is 16 kHz, where a hop is 256 samples: ``hop_in`` input samples give ``hop_out`` output samples.  What a stream
     has emitted is, bit for bit, ``Resampler(sr_in, sr_out, quality)``'s output for the whole signal fed so far, ``delay`` output samples
@@ -162,43 +167,15 @@ class StreamResampler:
     input samples.  This class owns memory and bookkeeping only; there is no arithmetic in torch."""
 
     def __init__(self, streams, sr_in, sr_out, quality='high', device='cuda'):
-        self.S = int(streams)
-        if self.S < 1:
-            raise ValueError("StreamResampler: streams must be >= 1")
+        super().__init__(streams)
         self.sr_in, self.sr_out = int(sr_in), int(sr_out)
         plan = stream_plan(sr_in, sr_out, quality)           # raises ValueError for an unsupported pair, before any GPU call
         self.up, self.down, self.zeros, self.beta, self.K = plan['up'], plan['down'], plan['zeros'], plan['beta'], plan['K']
         self.hop_in, self.hop_out, self.delay = plan['hop_in'], plan['hop_out'], plan['delay']
-        d = torch.device(device)
-        self.device = torch.device('cuda', torch.cuda.current_device()) if d.type == 'cuda' and d.index is None else d
+        self._alloc(device, _lib.lib.nele_resample_stream_state_bytes(self.S, self.K))
         self.table = torch.from_numpy(taps(self.up, self.down, self.zeros, self.beta, layout=1)).to(self.device)
-        self.nbytes = int(_lib.lib.nele_resample_stream_state_bytes(self.S, self.K))
-        self.state = torch.empty((self.nbytes,), dtype=torch.uint8, device=self.device)
-        self.hops = np.zeros(self.S, dtype=np.int64)
         self._zero_hop = None
         call('nele_resample_stream_init', ptr(self.state), c_longlong(self.nbytes), self.S, self.up, self.down, self.K, stream())
-
-    # ---- helpers (as RealtimeEnhancer's)
-    def _slots_mask(self, slots):
-        m = np.zeros(self.S, dtype=bool)
-        m[np.asarray(slots, dtype=np.int64).reshape(-1)] = True
-        return m
-
-    def _dev_bytes(self, mask):
-        return torch.from_numpy(mask.astype(np.uint8)).pin_memory().to(self.device, non_blocking=True)
-
-    def _dev_f32(self, x, shape, name):
-        if not isinstance(x, torch.Tensor):
-            x = torch.as_tensor(np.asarray(x, dtype=np.float32))
-        if tuple(x.shape) != shape:
-            raise ValueError("StreamResampler: %s must be %s (got %s)" % (name, shape, tuple(x.shape)))
-        if x.dtype != torch.float32:
-            raise ValueError("StreamResampler: %s must be float32" % name)
-        if not x.is_cuda:
-            if not x.is_pinned():
-                x = x.pin_memory()
-            x = x.to(self.device, non_blocking=True)
-        return x.contiguous()
 
     # ---- streaming
     def process(self, x, active=None, out=None):
@@ -210,11 +187,7 @@ class StreamResampler:
         if len(shape) != 2 or shape[0] != self.S or shape[1] % self.hop_in or shape[1] == 0:
             raise ValueError("StreamResampler.process: x must be [%d, nh * %d] (got %s)" % (self.S, self.hop_in, shape))
         nh = shape[1] // self.hop_in
-        act = None
-        if active is not None:
-            act = np.asarray(active, dtype=bool).reshape(-1)
-            if act.shape[0] != self.S:
-                raise ValueError("StreamResampler.process: active must hold one flag per stream (%d)" % self.S)
+        act = None if active is None else self._flags(active, "StreamResampler.process: active must hold one flag per stream (%d)" % self.S)
         oshape = (self.S, nh * self.hop_out)
         if out is None:
             out = torch.empty(oshape, dtype=torch.float32, device=self.device)
@@ -234,8 +207,7 @@ class StreamResampler:
         if self._zero_hop is None:
             self._zero_hop = torch.zeros((self.S, self.hop_in), dtype=torch.float32, device=self.device)
         y = self.process(self._zero_hop, active=self._slots_mask(slots))
-        rows = torch.from_numpy(slots).pin_memory().to(self.device, non_blocking=True)
-        tail = y.index_select(0, rows)[:, :self.delay].contiguous()
+        tail = y.index_select(0, self._dev_rows(slots))[:, :self.delay].contiguous()
         self.reset(slots)
         return tail
 

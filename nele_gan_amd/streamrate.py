@@ -13,6 +13,7 @@ import torch
 from .aec import EchoCancellingEnhancer
 from .realtime import HOP, RealtimeEnhancer
 from .resample import STREAM_RATE, StreamResampler
+from ._slots import dev_f32, dev_rows, host_flags
 
 
 class RateAdaptedEnhancer:
@@ -50,7 +51,8 @@ class RateAdaptedEnhancer:
         if self._both is None or self._both.shape[1] != width:
             self._both = torch.empty((2 * self.S, width), dtype=torch.float32, device=self.device)
         shape = (self.S, width)
-        c, s = self.down._dev_f32(clean, shape, 'clean'), self.down._dev_f32(second, shape, 'second')      # both checked before the first copy
+        who = type(self.down).__name__
+        c, s = dev_f32(clean, shape, 'clean', self.device, who), dev_f32(second, shape, 'second', self.device, who)   # both checked before the first copy
         self._both[:self.S].copy_(c, non_blocking=True)
         self._both[self.S:].copy_(s, non_blocking=True)
         return self._both
@@ -66,11 +68,7 @@ class RateAdaptedEnhancer:
         shape = tuple(np.shape(clean))
         if len(shape) != 2 or shape[0] != self.S or shape[1] % self.hop or shape[1] == 0:
             raise ValueError("RateAdaptedEnhancer.process: clean must be [%d, nh * %d] (got %s)" % (self.S, self.hop, shape))
-        act = None
-        if active is not None:
-            act = np.asarray(active, dtype=bool).reshape(-1)
-            if act.shape[0] != self.S:
-                raise ValueError("RateAdaptedEnhancer.process: active must hold one flag per stream (%d)" % self.S)
+        act = None if active is None else host_flags(active, self.S, "RateAdaptedEnhancer.process: active must hold one flag per stream (%d)" % self.S)
         self._per_call = shape[1] // self.hop
         low = self.down.process(self._stack(clean, second, shape[1]), active=None if act is None else np.concatenate([act, act]))
         out = self.inner.process(low[:self.S], low[self.S:], active=act)
@@ -86,7 +84,7 @@ class RateAdaptedEnhancer:
         nh, per = -(-self.latency // self.hop), self._per_call
         zeros = torch.zeros((self.S, per * self.hop), dtype=torch.float32, device=self.device)
         outs = [self.process(zeros, zeros, active=act) for _ in range(-(-nh // per))]
-        rows = torch.from_numpy(slots).pin_memory().to(self.device, non_blocking=True)
+        rows = dev_rows(slots, self.device)
         return torch.cat([o.index_select(0, rows) for o in outs], dim=1)[:, :nh * self.hop]
 
     def reset(self, slots):

@@ -25,6 +25,7 @@ from . import dist as ndist
 from . import metrics as mt
 from . import model as M
 from . import ops
+from ._lib import norm_dev
 from .optim import Adam
 
 # train_nele.py:30-43
@@ -314,7 +315,7 @@ class GanTrainer:
         self.haspi_dither = haspi_dither
         self.dither_seed = int(dither_seed)
         self.metrics = parse_metrics(target_metric)
-        self.device = M._norm_dev(device)            # indexed ('cuda' -> 'cuda:0'): torch.device('cuda') != torch.device('cuda:0')
+        self.device = norm_dev(device)            # indexed ('cuda' -> 'cuda:0'): torch.device('cuda') != torch.device('cuda:0')
         torch.manual_seed(seed)                      # same initial weights on every rank
         random.seed(seed)                            # train_nele.py:28
         self.G = M.Generator_Conv1D_cLN().to(self.device)
