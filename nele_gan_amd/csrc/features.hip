@@ -9,78 +9,8 @@
 // This file is compiled with -ffp-contract=off: the float32/float64 op sequence below mirrors numpy's.
 #include "common.h"
 #include "fft512.h"
-
-__constant__ int c_gmt[NELE_NBANDS] = {0, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23,
-                                        24, 25, 26, 28, 30, 32, 34, 36, 38, 41, 43, 46, 49, 52, 55, 58, 62, 66, 70, 74,
-                                        79, 83, 88, 93, 99, 105, 111, 117, 124, 131, 139, 147, 156, 165, 174, 184, 195,
-                                        206, 218, 230, 243, 257};
-
-// Band energy of band i from tmp[257] (= |X|^2, float32), in the accumulation order of
-// compute_band_E (audio_util.py:40-48): first the "frac" shares of band i-1's bins, then the
-// "1-frac" shares of band i's own bins; float32 products, float64 running sum.
-__device__ __forceinline__ float band_energy(const float* tmp, int i) {
-    double acc = 0.0;
-    if (i >= 1) {
-        const int g0 = c_gmt[i - 1], size = c_gmt[i] - g0;
-        for (int j = 0; j < size; ++j) {
-            const float fr = (float)((double)j / (double)size);
-            acc += (double)(fr * tmp[g0 + j]);
-        }
-    }
-    if (i <= NELE_NBANDS - 2) {
-        const int g0 = c_gmt[i], size = c_gmt[i + 1] - g0;
-        for (int j = 0; j < size; ++j) {
-            const float fr = (float)(1.0 - (double)j / (double)size);
-            acc += (double)(fr * tmp[g0 + j]);
-        }
-    }
-    return (float)acc;
-}
-
-// The same sums with the per-bin weights from LDS tables: band_energy() pays a float64 division per term on the one wave that runs it
-// (PMC: stft_band_wave_kernel and band_from_psd_kernel are bound by instruction issue, and the divisions are most of it).
-// frw[k] = (float)(j / size), omw[k] = (float)(1 - j / size) for bin k = g0 + j of its band - the very expressions above, evaluated once
-// per workgroup by one thread per BAND (<= 14 bins each; a per-bin fill that searches its band costs more than it saves: measured), so
-// every product and the order of the float64 sum are unchanged: bit-identical.
-__device__ __forceinline__ void band_weights_init(float* __restrict__ frw, float* __restrict__ omw) {
-    const int i = threadIdx.x;
-    if (i <= NELE_NBANDS - 2) {
-        const int g0 = c_gmt[i], size = c_gmt[i + 1] - g0;
-        for (int j = 0; j < size; ++j) {
-            frw[g0 + j] = (float)((double)j / (double)size);
-            omw[g0 + j] = (float)(1.0 - (double)j / (double)size);
-        }
-    }
-}
-__device__ __forceinline__ float band_energy_w(const float* tmp, const float* __restrict__ frw, const float* __restrict__ omw, int i) {
-    double acc = 0.0;
-    if (i >= 1) {
-        const int g0 = c_gmt[i - 1], g1 = c_gmt[i];
-        for (int k = g0; k < g1; ++k) acc += (double)(frw[k] * tmp[k]);
-    }
-    if (i <= NELE_NBANDS - 2) {
-        const int g0 = c_gmt[i], g1 = c_gmt[i + 1];
-        for (int k = g0; k < g1; ++k) acc += (double)(omw[k] * tmp[k]);
-    }
-    return (float)acc;
-}
-
-// np.abs(complex64) as numpy >= 1.25 computes it on FMA-capable x86 hosts (SIMD loop
-// loops_unary_complex: larger * sqrt(fma(r, r, 1)), r = smaller / larger), so that |X|^2 is
-// bit-identical to the oracle's and threshold decisions downstream (IMCRA, VAD) see the same values.
-__device__ __forceinline__ float np_cabsf(float re, float im) {
-    re = fabsf(re);
-    im = fabsf(im);
-    const float larger = fmaxf(re, im), smaller = fminf(im, re);
-    if (larger == 0.f) return 0.f;
-    const float ratio = smaller / larger;
-    return sqrtf(__builtin_fmaf(ratio, ratio, 1.0f)) * larger;
-}
-
-// the power law of the band features: nele_pow_f32 (common.h)
-__device__ __forceinline__ float pow_f32(float x, float p) { return nele_pow_f32(x, p); }
-
-__device__ __forceinline__ double hann512(int n) { return 0.5 - 0.5 * cospi((double)n / 256.0); }
+#include "featmath.h"
+#include "imcra.h"
 
 // ------------------------------------------------------------------------------------------ STFT
 // grid (ceil(T/2), B), block 256.  Frames 2p and 2p+1 share one complex FFT.
@@ -137,7 +67,7 @@ __global__ __launch_bounds__(256) void stft_band_kernel(const float* __restrict_
         const int f = threadIdx.x >> 6, i = threadIdx.x & 63, t = t0 + f;
         if (t < Tb) {
             const float e = band_energy(tmp[f], i);
-            band[((size_t)b * T + t) * NELE_NBANDS + i] = pow_f32(e, power);
+            band[((size_t)b * T + t) * NELE_NBANDS + i] = nele_pow_f32(e, power);
         }
     }
 }
@@ -227,8 +157,8 @@ __global__ __launch_bounds__(256) void stft_band_wave_kernel(const float* __rest
                 if (k < NELE_NBINS) { tmp0[k] = p0[q]; tmp1[k] = p1[q]; }
             }
             fftw_wave_sync();
-            band[((size_t)b * T + t0) * NELE_NBANDS + lane] = pow_f32(band_energy_w(tmp0, frw, omw, lane), power);
-            if (has1) band[((size_t)b * T + t1) * NELE_NBANDS + lane] = pow_f32(band_energy_w(tmp1, frw, omw, lane), power);
+            band[((size_t)b * T + t0) * NELE_NBANDS + lane] = nele_pow_f32(band_energy_w(tmp0, frw, omw, lane), power);
+            if (has1) band[((size_t)b * T + t1) * NELE_NBANDS + lane] = nele_pow_f32(band_energy_w(tmp1, frw, omw, lane), power);
         }
         fftw_wave_sync();                                   // xw is rewritten by the next pair
     }
@@ -247,10 +177,6 @@ struct ImcraLds {
     float tmp[NELE_NBINS + 3];
 };
 
-__device__ __forceinline__ double fsmooth3(const double* v, int k, double w0, double w1, double w2) {
-    return (w0 * v[k] + w1 * v[k + 1]) + w2 * v[k + 2];  // v is offset by one: v[k+1] is bin k
-}
-
 // BAND_IN_LOOP = false: the band feature is left to band_from_psd_kernel (parallel over frames); the serial loop then has two
 // barriers per frame instead of four and no 64-band reduction on the wave that paces it.
 template <bool BAND_IN_LOOP>
@@ -262,12 +188,8 @@ __global__ __launch_bounds__(IMCRA_THREADS) void imcra_band_kernel(const float2*
     const bool act = k < NELE_NBINS;
     const bool edge_lo = (k == 0), edge_hi = (k == NELE_NBINS - 1);
     const float2* Y = spec + (size_t)b * T * NELE_NBINS;
-    const double alpha_s = 0.9, alpha_d = 0.85, Bmin = 3.2, Gamma0 = 4.6, Gamma1 = 3.0, zeta0 = 1.67, beta = 1.47;
-    const double alpha_dd = 0.92, xi_min = pow(10.0, -25.0 / 20.0), p_up = 0.9;
-    const double one_m_as = 1.0 - alpha_s, one_m_ad = 1.0 - alpha_d, one_m_add = 1.0 - alpha_dd;
-    double w0 = 0.25, w1 = 0.5, w2 = 0.25;  // imcra.py:270-280 (sym_hanning(3), row-normalised)
-    if (edge_lo) { w0 = 0.0; w1 = 1.0 / 1.5; w2 = 0.5 / 1.5; }
-    if (edge_hi) { w0 = 0.5 / 1.5; w1 = 1.0 / 1.5; w2 = 0.0; }
+    double w0, w1, w2;
+    imcra_smooth_weights(k, w0, w1, w2);
 
     double S = 0, tS = 0, Smin = 0, tSmin = 0, Smin_sw = 0, tSmin_sw = 0, ovL = 0, Lam64 = 1e-6, G = 1.0, Gamma = 1.0;
     float Lam32 = 0.f;
@@ -296,41 +218,21 @@ __global__ __launch_bounds__(IMCRA_THREADS) void imcra_band_kernel(const float2*
         __syncthreads();
         if (act) {
             const double Y2 = (double)Y2f;
-            const double Sf = fsmooth3(s.y2[l & 1], k, w0, w1, w2);
-            // ---- decision-directed a-priori SNR (imcra.py:543-557)
-            const double xi_G = (l == 0) ? 1.0 : (G * G) * Gamma;
-            double term;
-            if (l == 0 || l >= 16) {
-                Gamma = Y2 / Lam64;
-                double xi_ML = Gamma - 1.0;
-                if (xi_ML < 1e-6) xi_ML = 1e-6;
-                term = one_m_add * xi_ML;
-            } else {  // Lambda_D (hence Gamma, xi_ML) is a float32 array for frames 1..15
-                const float Gf = Y2f / Lam32;
-                float xf = Gf - 1.0f;
-                if (xf < (float)1e-6) xf = (float)1e-6;
-                term = (double)((float)one_m_add * xf);
-                Gamma = (double)Gf;
-            }
-            xi = alpha_dd * xi_G + term;
-            if (xi < xi_min) xi = xi_min;
-            G = xi / (1.0 + xi);
+            const double* y2 = s.y2[l & 1];                                       // offset by one: y2[k + 1] is bin k
+            const double Sf = imcra_smooth3(w0, w1, w2, y2[k], y2[k + 1], y2[k + 2]);
+            xi = imcra_snr_step(l, Y2f, Lam64, Lam32, G, Gamma);
             // ---- imcra.update (imcra.py:363-484)
             if (l == 0) {  // init_params (imcra.py:338-361)
                 S = Sf; tS = Sf; Smin = Sf; tSmin = Sf; Smin_sw = Sf; tSmin_sw = Sf;
                 ovL = Y2;
                 Lam32 = Y2f;
             }
-            S = alpha_s * S + one_m_as * Sf;
-            Smin = fmin(Smin, S);
-            Smin_sw = fmin(Smin_sw, S);
+            imcra_s_step(Sf, S, Smin, Smin_sw);
             if (l < 15) {
-                Lam32 = (float)alpha_d * Lam32 + (float)one_m_ad * Y2f;
+                Lam32 = imcra_lambda32_step(Lam32, Y2f);
                 outv = Lam32;
             } else {
-                const double Gamma_min = Y2 / (Bmin * Smin);
-                const double zeta = S / (Bmin * Smin);
-                I = (Gamma_min < Gamma0 && zeta < zeta0) ? 1.0 : 0.0;
+                I = imcra_indicator(Y2, S, Smin) ? 1.0 : 0.0;
             }
         }
         if (l >= 15) {  // block-uniform branch
@@ -344,39 +246,22 @@ __global__ __launch_bounds__(IMCRA_THREADS) void imcra_band_kernel(const float2*
             __syncthreads();
             if (act) {
                 const double Y2 = (double)Y2f;
-                const double norm = fsmooth3(s.b, k, w0, w1, w2);
-                double tSf = fsmooth3(s.a, k, w0, w1, w2);
-                if (norm > 0.0) tSf = tSf / norm;
-                tS = alpha_s * tS + one_m_as * tSf;
-                tSmin = fmin(tSmin, tS);
-                tSmin_sw = fmin(tSmin_sw, tS);
-                const double tG = Y2 / (Bmin * tSmin);
-                const double tz = S / (Bmin * tSmin);
-                double q = 0.0;
-                if (tG <= 1.0 && tz < zeta0) q = 1.0;
-                else if (1.0 < tG && tG < Gamma1 && tz < zeta0) q = (Gamma1 - tG) / (Gamma1 - 1.0);
-                // post_speech_prob (imcra.py:22-36)
-                const double nu = Gamma * xi / (1.0 + xi);
-                double p = 0.0;
-                if (q < 1.0) p = 1.0 / (1.0 + (q / (1.0 - q)) * (1.0 + xi) * exp(-nu));
-                if (p > p_up) p = p_up;
-                const double tad = alpha_d + one_m_ad * p;
-                ovL = tad * ovL + (1.0 - tad) * Y2;
-                Lam64 = beta * ovL;
+                const double norm = imcra_smooth3(w0, w1, w2, s.b[k], s.b[k + 1], s.b[k + 2]);
+                const double tSf = imcra_smooth3(w0, w1, w2, s.a[k], s.a[k + 1], s.a[k + 2]);
+                const double r = imcra_prior_step(Y2, S, tSf, norm, tS, tSmin, tSmin_sw);
+                Lam64 = imcra_psd_step(Y2, Gamma, xi, r, ovL);
                 outv = (float)Lam64;
-                // minimum tracking (imcra.py:452-481); np.roll of the U=8 store == ring buffer
-                if (j + 1 == 15) {
-                    const int slot = u & 7;
+                int slot, n;
+                if (imcra_store_due(j, u, slot, n)) {                         // the minima store: LDS rows
                     s.st[slot][k] = Smin_sw;
                     s.tst[slot][k] = tSmin_sw;
-                    const int n = (u < 8) ? (u + 1) : 8;
                     double m = s.st[0][k], tm = s.tst[0][k];
                     for (int i = 1; i < n; ++i) { m = fmin(m, s.st[i][k]); tm = fmin(tm, s.tst[i][k]); }
                     Smin = m; tSmin = tm;
                     Smin_sw = S; tSmin_sw = tS;
                 }
             }
-            if (++j == 15) { j = 0; ++u; }
+            imcra_advance(j, u);
         }
         if (act && psd) psd[((size_t)b * T + l) * NELE_NBINS + k] = outv;
         if (BAND_IN_LOOP) {
@@ -428,9 +313,7 @@ __device__ __forceinline__ ImcraBin imcra_bin(const float* y2f, int b, int k, in
     q.y2 = y2f + (size_t)b * T * NELE_NBINS + k;
     q.dl = (k == 0) ? 0 : -1;
     q.dr = (k == NELE_NBINS - 1) ? 0 : 1;
-    q.w0 = 0.25; q.w1 = 0.5; q.w2 = 0.25;
-    if (k == 0) { q.w0 = 0.0; q.w1 = 1.0 / 1.5; q.w2 = 0.5 / 1.5; }
-    if (k == NELE_NBINS - 1) { q.w0 = 0.5 / 1.5; q.w1 = 1.0 / 1.5; q.w2 = 0.0; }
+    imcra_smooth_weights(k, q.w0, q.w1, q.w2);
     return q;
 }
 
@@ -441,8 +324,6 @@ __global__ __launch_bounds__(256) void imcra_ind_kernel(const float* __restrict_
     const int b = gid / NELE_NBINS, k = gid - b * NELE_NBINS;
     const ImcraBin bn = imcra_bin(y2f, b, k, T);
     unsigned char* Iout = ind + (size_t)b * T * NELE_NBINS + k;
-    const double alpha_s = 0.9, Bmin = 3.2, Gamma0 = 4.6, zeta0 = 1.67;
-    const double one_m_as = 1.0 - alpha_s;
     const int Tb = tlens ? min(tlens[b], T) : T;
     double S = 0, Smin = 0, Smin_sw = 0, st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int j = 0, u = 0;
@@ -459,27 +340,22 @@ __global__ __launch_bounds__(256) void imcra_ind_kernel(const float* __restrict_
     };
     auto step = [&](int l, const float (&f)[3]) {
         const double Y2 = (double)f[1];
-        const double Sf = (bn.w0 * (double)f[0] + bn.w1 * (double)f[1]) + bn.w2 * (double)f[2];
+        const double Sf = imcra_smooth3(bn.w0, bn.w1, bn.w2, (double)f[0], (double)f[1], (double)f[2]);
         if (l == 0) { S = Sf; Smin = Sf; Smin_sw = Sf; }
-        S = alpha_s * S + one_m_as * Sf;
-        Smin = fmin(Smin, S);
-        Smin_sw = fmin(Smin_sw, S);
+        imcra_s_step(Sf, S, Smin, Smin_sw);
         if (l >= 15) {
-            const double Gamma_min = Y2 / (Bmin * Smin);
-            const double zeta = S / (Bmin * Smin);
-            Iout[(size_t)l * NELE_NBINS] = (Gamma_min < Gamma0 && zeta < zeta0) ? 1 : 0;
-            if (j + 1 == 15) {                                   // minimum tracking (imcra.py:452-481); np.roll of the U = 8 store == ring buffer
-                const int slot = u & 7;
+            Iout[(size_t)l * NELE_NBINS] = imcra_indicator(Y2, S, Smin) ? 1 : 0;
+            int slot, n;
+            if (imcra_store_due(j, u, slot, n)) {                // the minima store: eight registers, written and read through selects
 #pragma unroll
                 for (int i = 0; i < 8; ++i) st[i] = (i == slot) ? Smin_sw : st[i];
-                const int n = (u < 8) ? (u + 1) : 8;
                 double m = st[0];
 #pragma unroll
                 for (int i = 1; i < 8; ++i) m = (i < n) ? fmin(m, st[i]) : m;
                 Smin = m;
                 Smin_sw = S;
             }
-            if (++j == 15) { j = 0; ++u; }
+            imcra_advance(j, u);
         }
     };
     fetch(0, fa);
@@ -510,9 +386,6 @@ __global__ __launch_bounds__(128) void imcra_track_kernel(const float* __restric
     const ImcraBin bn = imcra_bin(y2f, b, k, T);
     const unsigned char* Iin = ind + (size_t)b * T * NELE_NBINS + k;
     float* P = psd + (size_t)b * T * NELE_NBINS + k;
-    const double alpha_s = 0.9, alpha_d = 0.85, Bmin = 3.2, Gamma1 = 3.0, zeta0 = 1.67, beta = 1.47;
-    const double alpha_dd = 0.92, xi_min = pow(10.0, -25.0 / 20.0), p_up = 0.9;
-    const double one_m_as = 1.0 - alpha_s, one_m_ad = 1.0 - alpha_d, one_m_add = 1.0 - alpha_dd;
     const int Tb = live ? (tlens ? min(tlens[b], T) : T) : 0;
     int Tmax = Tb;                                                            // the lanes of a wave may belong to two utterances
 #pragma unroll
@@ -550,73 +423,40 @@ __global__ __launch_bounds__(128) void imcra_track_kernel(const float* __restric
     };
     auto prior = [&](int l, const float (&f)[3], const unsigned char (&ii)[3]) -> double {
         const double Y2 = (double)f[1];
-        const double Sf = (bn.w0 * (double)f[0] + bn.w1 * (double)f[1]) + bn.w2 * (double)f[2];
+        const double Sf = imcra_smooth3(bn.w0, bn.w1, bn.w2, (double)f[0], (double)f[1], (double)f[2]);
         if (l == 0) { S = Sf; tS = Sf; tSmin = Sf; tSmin_sw = Sf; }          // init_params (imcra.py:338-361)
-        S = alpha_s * S + one_m_as * Sf;
+        S = imcra_tsmooth(S, Sf);
         double r = -1.0;
         if (l >= 15) {
             const double I0 = (double)ii[0], I1 = (double)ii[1], I2 = (double)ii[2];
-            const double a0 = I0 * (double)f[0], a1 = I1 * (double)f[1], a2 = I2 * (double)f[2];
-            const double norm = (bn.w0 * I0 + bn.w1 * I1) + bn.w2 * I2;
-            double tSf = (bn.w0 * a0 + bn.w1 * a1) + bn.w2 * a2;
-            if (norm > 0.0) tSf = tSf / norm;
-            tS = alpha_s * tS + one_m_as * tSf;
-            tSmin = fmin(tSmin, tS);
-            tSmin_sw = fmin(tSmin_sw, tS);
-            const double tG = Y2 / (Bmin * tSmin);
-            const double tz = S / (Bmin * tSmin);
-            double q = 0.0;
-            if (tG <= 1.0 && tz < zeta0) q = 1.0;
-            else if (1.0 < tG && tG < Gamma1 && tz < zeta0) q = (Gamma1 - tG) / (Gamma1 - 1.0);
-            if (q < 1.0) r = q / (1.0 - q);                                  // post_speech_prob's q / (1 - q) (imcra.py:22-36); -1: p = 0
-            if (j + 1 == 15) {                                               // minimum tracking (imcra.py:452-481)
-                const int slot = u & 7;
+            const double a0 = I0 * (double)f[0], a1 = I1 * (double)f[1], a2 = I2 * (double)f[2];   // ahead of norm: 203 VGPRs, behind it 206
+            const double norm = imcra_smooth3(bn.w0, bn.w1, bn.w2, I0, I1, I2);
+            const double tSf = imcra_smooth3(bn.w0, bn.w1, bn.w2, a0, a1, a2);
+            r = imcra_prior_step(Y2, S, tSf, norm, tS, tSmin, tSmin_sw);
+            int slot, n;
+            if (imcra_store_due(j, u, slot, n)) {                            // the minima store: eight registers
 #pragma unroll
                 for (int i = 0; i < 8; ++i) tst[i] = (i == slot) ? tSmin_sw : tst[i];
-                const int n = (u < 8) ? (u + 1) : 8;
                 double tm = tst[0];
 #pragma unroll
                 for (int i = 1; i < 8; ++i) tm = (i < n) ? fmin(tm, tst[i]) : tm;
                 tSmin = tm;
                 tSmin_sw = tS;
             }
-            if (++j == 15) { j = 0; ++u; }
+            imcra_advance(j, u);
         }
         return r;
     };
     auto track = [&](int l, const float Y2f, const double r) {
         const double Y2 = (double)Y2f;
         float outv = 0.f;
-        // ---- decision-directed a-priori SNR (imcra.py:543-557)
-        const double xi_G = (l == 0) ? 1.0 : (G * G) * Gamma;
-        double term;
-        if (l == 0 || l >= 16) {
-            Gamma = Y2 / Lam64;
-            double xi_ML = Gamma - 1.0;
-            if (xi_ML < 1e-6) xi_ML = 1e-6;
-            term = one_m_add * xi_ML;
-        } else {  // Lambda_D (hence Gamma, xi_ML) is a float32 array for frames 1..15
-            const float Gf = Y2f / Lam32;
-            float xf = Gf - 1.0f;
-            if (xf < (float)1e-6) xf = (float)1e-6;
-            term = (double)((float)one_m_add * xf);
-            Gamma = (double)Gf;
-        }
-        double xi = alpha_dd * xi_G + term;
-        if (xi < xi_min) xi = xi_min;
-        G = xi / (1.0 + xi);
+        const double xi = imcra_snr_step(l, Y2f, Lam64, Lam32, G, Gamma);
         if (l == 0) { ovL = Y2; Lam32 = Y2f; }
         if (l < 15) {
-            Lam32 = (float)alpha_d * Lam32 + (float)one_m_ad * Y2f;
+            Lam32 = imcra_lambda32_step(Lam32, Y2f);
             outv = Lam32;
         } else {
-            const double nu = Gamma * xi / (1.0 + xi);
-            double p = 0.0;
-            if (r >= 0.0) p = 1.0 / (1.0 + r * (1.0 + xi) * exp(-nu));
-            if (p > p_up) p = p_up;
-            const double tad = alpha_d + one_m_ad * p;
-            ovL = tad * ovL + (1.0 - tad) * Y2;
-            Lam64 = beta * ovL;
+            Lam64 = imcra_psd_step(Y2, Gamma, xi, r, ovL);
             outv = (float)Lam64;
         }
         P[(size_t)l * NELE_NBINS] = outv;
@@ -669,39 +509,17 @@ __global__ __launch_bounds__(256) void band_from_psd_kernel(const float* __restr
     }
     __syncthreads();
     const int f = threadIdx.x >> 6, i = threadIdx.x & 63;
-    if (l0 + f < T) band[((size_t)b * T + l0 + f) * NELE_NBANDS + i] = pow_f32(band_energy_w(tmp[f], frw, omw, i), power);
+    if (l0 + f < T) band[((size_t)b * T + l0 + f) * NELE_NBANDS + i] = nele_pow_f32(band_energy_w(tmp[f], frw, omw, i), power);
 }
 
 // band[i] = band[i] ** power in place (the tail of imcra_band_kernel, parallel over frames)
 __global__ void band_pow_kernel(float* __restrict__ band, size_t n, float power) {
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) band[i] = pow_f32(band[i], power);
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) band[i] = nele_pow_f32(band[i], power);
 }
 
 // ------------------------------------------------------------------------------------------ iSTFT
 // grid (T-1, B), block 256: output samples [256 j, 256 j + 256) of the trimmed signal = second half
 // of frame j + first half of frame j+1; both real inverse transforms ride one complex FFT.
-__device__ __forceinline__ double band_gain_sqrt(const float* __restrict__ a2, int k) {
-    // interp_band_gain (audio_util.py:93-110) then np.sqrt (audio_util.py:85)
-    if (k <= 1) return sqrt(1e-4);
-    if (k == NELE_NBINS - 1) return sqrt(1e-2);
-    int i = 0;
-    while (c_gmt[i + 1] <= k) ++i;
-    const int size = c_gmt[i + 1] - c_gmt[i], jj = k - c_gmt[i];
-    const double frac = (double)jj / (double)size;
-    const float g = (float)(1.0 - frac) * a2[i] + (float)frac * a2[i + 1];
-    return sqrt((double)g);
-}
-
-// the same with the band of bin k looked up (gain_istft_wave_kernel fills the table once per workgroup instead of searching per bin and hop)
-__device__ __forceinline__ double band_gain_sqrt_at(const float* __restrict__ a2, int k, int i) {
-    if (k <= 1) return sqrt(1e-4);
-    if (k == NELE_NBINS - 1) return sqrt(1e-2);
-    const int size = c_gmt[i + 1] - c_gmt[i], jj = k - c_gmt[i];
-    const double frac = (double)jj / (double)size;
-    const float g = (float)(1.0 - frac) * a2[i] + (float)frac * a2[i + 1];
-    return sqrt((double)g);
-}
-
 #ifdef NELE_AB                                          // superseded variant: only in the test library (libnele_hip_ab.so)
 __global__ __launch_bounds__(256) void gain_istft_kernel(const float* __restrict__ alpha2, const float2* __restrict__ spec,
                                                          int T, float* __restrict__ wav, const int* __restrict__ tlens) {
@@ -731,12 +549,7 @@ __global__ __launch_bounds__(256) void gain_istft_kernel(const float* __restrict
         const int n = threadIdx.x;
         const double x1 = s.x[n + 256].x * (1.0 / 512.0);  // frame fa, second half
         const double x2 = s.x[n].y * (1.0 / 512.0);        // frame fb, first half
-        const double wa = hann512(n + 256), wb = hann512(n);
-        float y = (float)(wa * x1);                        // overlap-add into a float32 buffer
-        y = (float)((double)y + wb * x2);
-        float wss = (float)(wa * wa);                      // window_sumsquare, same float32 staging
-        wss = (float)((double)wss + wb * wb);
-        wav[(size_t)b * (NELE_HOP * (T - 1)) + (size_t)NELE_HOP * fa + n] = y / wss;
+        wav[(size_t)b * (NELE_HOP * (T - 1)) + (size_t)NELE_HOP * fa + n] = istft_ola(x1, x2, hann512(n + 256), hann512(n));
     }
 }
 #endif  // NELE_AB
@@ -761,10 +574,7 @@ __global__ __launch_bounds__(256) void gain_istft_wave_kernel(const float* __res
         int i = 0;
         while (i < NELE_NBANDS - 2 && c_gmt[i + 1] <= k) ++i;
         bidx[k] = (unsigned char)i;
-        const int size = c_gmt[i + 1] - c_gmt[i], jj = k - c_gmt[i];
-        const double frac = (double)jj / (double)size;
-        wlo[k] = (float)(1.0 - frac);
-        whi[k] = (float)frac;
+        band_gain_weights(k, i, wlo[k], whi[k]);
     }
     tw[tid] = fft512_twiddle(tid);
     hw[tid] = hann512(tid);
@@ -824,12 +634,7 @@ __global__ __launch_bounds__(256) void gain_istft_wave_kernel(const float* __res
             const int n = 64 * m + lane;
             const double x1 = v[m + 4].x * (1.0 / 512.0);      // frame fa, second half
             const double x2 = v[m].y * (1.0 / 512.0);          // frame fb, first half
-            const double wa = hw[n + 256], wb = hw[n];
-            float y = (float)(wa * x1);                        // overlap-add into a float32 buffer
-            y = (float)((double)y + wb * x2);
-            float wss = (float)(wa * wa);                      // window_sumsquare, same float32 staging
-            wss = (float)((double)wss + wb * wb);
-            out[(size_t)NELE_HOP * fa + n] = y / wss;
+            out[(size_t)NELE_HOP * fa + n] = istft_ola(x1, x2, hw[n + 256], hw[n]);
         }
         fftw_wave_sync();                                   // xw is restaged by the next hop
     }
@@ -990,11 +795,7 @@ __global__ void interp_gain_kernel(const float* __restrict__ bandE, int N, doubl
     if (k <= 1) v = 1e-4;
     else if (k == NELE_NBINS - 1) v = 1e-2;
     else {
-        int b = 0;
-        while (c_gmt[b + 1] <= k) ++b;
-        const int size = c_gmt[b + 1] - c_gmt[b], jj = k - c_gmt[b];
-        const double frac = (double)jj / (double)size;
-        v = (double)((float)(1.0 - frac) * bandE[(size_t)f * NELE_NBANDS + b] + (float)frac * bandE[(size_t)f * NELE_NBANDS + b + 1]);
+        v = (double)band_gain(bandE + (size_t)f * NELE_NBANDS, k);
     }
     g[i] = v;
 }

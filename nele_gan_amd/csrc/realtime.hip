@@ -13,15 +13,12 @@
 // This file is compiled with -ffp-contract=off (Makefile EXACT): the feature and IMCRA arithmetic mirrors numpy's operation order.
 #include "common.h"
 #include "fft512.h"
+#include "featmath.h"
+#include "imcra.h"
 #include "slot_state.h"
 #include "../../include/nele_hip.h"
 
 namespace {
-
-__constant__ int c_rt_gmt[NELE_NBANDS] = {0, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23,
-                                          24, 25, 26, 28, 30, 32, 34, 36, 38, 41, 43, 46, 49, 52, 55, 58, 62, 66, 70, 74,
-                                          79, 83, 88, 93, 99, 105, 111, 117, 124, 131, 139, 147, 156, 165, 174, 184, 195,
-                                          206, 218, 230, 243, 257};
 
 // ---- generator geometry (model.py:43-82)
 __host__ __device__ constexpr int rt_cin(int l) { return l == 0 ? 128 : 256; }
@@ -113,42 +110,6 @@ __device__ __forceinline__ float rt_bf16(float x) {       // round to nearest ev
     return (float)(__bf16)x;
 }
 
-// np.abs(complex64) as numpy computes it (see features.hip np_cabsf: |Y|^2 feeds IMCRA's threshold decisions)
-__device__ __forceinline__ float rt_cabsf(float re, float im) {
-    re = fabsf(re);
-    im = fabsf(im);
-    const float larger = fmaxf(re, im), smaller = fminf(im, re);
-    if (larger == 0.f) return 0.f;
-    const float ratio = smaller / larger;
-    return sqrtf(__builtin_fmaf(ratio, ratio, 1.0f)) * larger;
-}
-
-// compute_band_E's accumulation order (audio_util.py:40-48), as features.hip band_energy
-__device__ __forceinline__ float rt_band_energy(const float* tmp, int i) {
-    double acc = 0.0;
-    if (i >= 1) {
-        const int g0 = c_rt_gmt[i - 1], size = c_rt_gmt[i] - g0;
-        for (int j = 0; j < size; ++j) {
-            const float fr = (float)((double)j / (double)size);
-            acc += (double)(fr * tmp[g0 + j]);
-        }
-    }
-    if (i <= NELE_NBANDS - 2) {
-        const int g0 = c_rt_gmt[i], size = c_rt_gmt[i + 1] - g0;
-        for (int j = 0; j < size; ++j) {
-            const float fr = (float)(1.0 - (double)j / (double)size);
-            acc += (double)(fr * tmp[g0 + j]);
-        }
-    }
-    return (float)acc;
-}
-
-__device__ __forceinline__ double rt_hann(int n) { return 0.5 - 0.5 * cospi((double)n / 256.0); }
-
-__device__ __forceinline__ double rt_fsmooth3(const double* v, int k, double w0, double w1, double w2) {
-    return (w0 * v[k] + w1 * v[k + 1]) + w2 * v[k + 2];
-}
-
 // ============================================================================================ front: features + IMCRA
 #define RT_FRONT_THREADS 320
 __global__ __launch_bounds__(RT_FRONT_THREADS) void rt_front_kernel(RtArgs a) {
@@ -220,13 +181,9 @@ __global__ __launch_bounds__(RT_FRONT_THREADS) void rt_front_kernel(RtArgs a) {
         Lam32 = lam32p[bin ? k : NELE_NBINS];
         j = hd->j; u = hd->u;
     }
-    const double alpha_s = 0.9, alpha_d = 0.85, Bmin = 3.2, Gamma0 = 4.6, Gamma1 = 3.0, zeta0 = 1.67, beta = 1.47;
-    const double alpha_dd = 0.92, xi_min = pow(10.0, -25.0 / 20.0), p_up = 0.9;
-    const double one_m_as = 1.0 - alpha_s, one_m_ad = 1.0 - alpha_d, one_m_add = 1.0 - alpha_dd;
     const bool edge_lo = (k == 0), edge_hi = (k == NELE_NBINS - 1);
-    double w0 = 0.25, w1 = 0.5, w2 = 0.25;   // imcra.py:270-280
-    if (edge_lo) { w0 = 0.0; w1 = 1.0 / 1.5; w2 = 0.5 / 1.5; }
-    if (edge_hi) { w0 = 0.5 / 1.5; w1 = 1.0 / 1.5; w2 = 0.0; }
+    double w0, w1, w2;
+    imcra_smooth_weights(k, w0, w1, w2);
     __syncthreads();                                               // ring written, twiddles ready
 
     float2* specr = reinterpret_cast<float2*>(rec + RT_O_SPEC);
@@ -244,7 +201,7 @@ __global__ __launch_bounds__(RT_FRONT_THREADS) void rt_front_kernel(RtArgs a) {
         }
         __syncthreads();
         for (int n = k; n < NELE_NFFT; n += RT_FRONT_THREADS) {
-            const double w = rt_hann(n);
+            const double w = hann512(n);
             s.x[fft512_brev(n)] = make_double2(w * (double)xc[n], w * (double)xn[n]);
         }
         __syncthreads();
@@ -257,7 +214,7 @@ __global__ __launch_bounds__(RT_FRONT_THREADS) void rt_front_kernel(RtArgs a) {
             const float2 A = make_float2((float)Ad.x, (float)Ad.y);
             const float2 Bv = make_float2((float)Bd.x, (float)Bd.y);
             specr[(f & 1) * NELE_NBINS + k] = A;
-            const float m0 = rt_cabsf(A.x, A.y), m1 = rt_cabsf(Bv.x, Bv.y);
+            const float m0 = np_cabsf(A.x, A.y), m1 = np_cabsf(Bv.x, Bv.y);
             pc[k] = m0 * m0;
             Y2f = m1 * m1;                                         // np.abs(complex64) ** 2 in float32
             y2[k + 1] = (double)Y2f;
@@ -265,45 +222,25 @@ __global__ __launch_bounds__(RT_FRONT_THREADS) void rt_front_kernel(RtArgs a) {
             if (edge_hi) y2[NELE_NBINS + 1] = (double)Y2f;
         }
         __syncthreads();
-        // ---- one IMCRA frame (the body of features.hip imcra_band_kernel, state from the stream's record)
+        // ---- one IMCRA frame (the steps of imcra.h in imcra_band_kernel's order, state from the stream's record)
         const int l = f;
         float outv = 0.f;
         double xi = 0.0, I = 0.0;
         if (bin) {
             const double Y2 = (double)Y2f;
-            const double Sf = rt_fsmooth3(y2, k, w0, w1, w2);
-            const double xi_G = (l == 0) ? 1.0 : (G * G) * Gamma;
-            double term;
-            if (l == 0 || l >= 16) {
-                Gamma = Y2 / Lam64;
-                double xi_ML = Gamma - 1.0;
-                if (xi_ML < 1e-6) xi_ML = 1e-6;
-                term = one_m_add * xi_ML;
-            } else {
-                const float Gf = Y2f / Lam32;
-                float xf = Gf - 1.0f;
-                if (xf < (float)1e-6) xf = (float)1e-6;
-                term = (double)((float)one_m_add * xf);
-                Gamma = (double)Gf;
-            }
-            xi = alpha_dd * xi_G + term;
-            if (xi < xi_min) xi = xi_min;
-            G = xi / (1.0 + xi);
+            const double Sf = imcra_smooth3(w0, w1, w2, y2[k], y2[k + 1], y2[k + 2]);
+            xi = imcra_snr_step(l, Y2f, Lam64, Lam32, G, Gamma);
             if (l == 0) {
                 S = Sf; tS = Sf; Smin = Sf; tSmin = Sf; Smin_sw = Sf; tSmin_sw = Sf;
                 ovL = Y2;
                 Lam32 = Y2f;
             }
-            S = alpha_s * S + one_m_as * Sf;
-            Smin = fmin(Smin, S);
-            Smin_sw = fmin(Smin_sw, S);
+            imcra_s_step(Sf, S, Smin, Smin_sw);
             if (l < 15) {
-                Lam32 = (float)alpha_d * Lam32 + (float)one_m_ad * Y2f;
+                Lam32 = imcra_lambda32_step(Lam32, Y2f);
                 outv = Lam32;
             } else {
-                const double Gamma_min = Y2 / (Bmin * Smin);
-                const double zeta = S / (Bmin * Smin);
-                I = (Gamma_min < Gamma0 && zeta < zeta0) ? 1.0 : 0.0;
+                I = imcra_indicator(Y2, S, Smin) ? 1.0 : 0.0;
             }
         }
         if (l >= 15) {                                             // the indicator of every bin before the prior: one barrier
@@ -317,37 +254,22 @@ __global__ __launch_bounds__(RT_FRONT_THREADS) void rt_front_kernel(RtArgs a) {
             __syncthreads();
             if (bin) {
                 const double Y2 = (double)Y2f;
-                const double norm = rt_fsmooth3(sb, k, w0, w1, w2);
-                double tSf = rt_fsmooth3(sa, k, w0, w1, w2);
-                if (norm > 0.0) tSf = tSf / norm;
-                tS = alpha_s * tS + one_m_as * tSf;
-                tSmin = fmin(tSmin, tS);
-                tSmin_sw = fmin(tSmin_sw, tS);
-                const double tG = Y2 / (Bmin * tSmin);
-                const double tz = S / (Bmin * tSmin);
-                double q = 0.0;
-                if (tG <= 1.0 && tz < zeta0) q = 1.0;
-                else if (1.0 < tG && tG < Gamma1 && tz < zeta0) q = (Gamma1 - tG) / (Gamma1 - 1.0);
-                const double nu = Gamma * xi / (1.0 + xi);
-                double p = 0.0;
-                if (q < 1.0) p = 1.0 / (1.0 + (q / (1.0 - q)) * (1.0 + xi) * exp(-nu));
-                if (p > p_up) p = p_up;
-                const double tad = alpha_d + one_m_ad * p;
-                ovL = tad * ovL + (1.0 - tad) * Y2;
-                Lam64 = beta * ovL;
+                const double norm = imcra_smooth3(w0, w1, w2, sb[k], sb[k + 1], sb[k + 2]);
+                const double tSf = imcra_smooth3(w0, w1, w2, sa[k], sa[k + 1], sa[k + 2]);
+                const double r = imcra_prior_step(Y2, S, tSf, norm, tS, tSmin, tSmin_sw);
+                Lam64 = imcra_psd_step(Y2, Gamma, xi, r, ovL);
                 outv = (float)Lam64;
-                if (j + 1 == 15) {                                 // minimum tracking, U = 8 store as a ring
-                    const int slot = u & 7;
+                int slot, nst;
+                if (imcra_store_due(j, u, slot, nst)) {            // the minima store: the stream record
                     IM(IM_ST + slot) = Smin_sw;
                     IM(IM_TST + slot) = tSmin_sw;
-                    const int nst = (u < 8) ? (u + 1) : 8;
                     double mm = IM(IM_ST), tm = IM(IM_TST);
                     for (int i = 1; i < nst; ++i) { mm = fmin(mm, IM(IM_ST + i)); tm = fmin(tm, IM(IM_TST + i)); }
                     Smin = mm; tSmin = tm;
                     Smin_sw = S; tSmin_sw = tS;
                 }
             }
-            if (++j == 15) { j = 0; ++u; }
+            imcra_advance(j, u);
         }
         if (bin) {
             const float r = sqrtf(outv);                           // band feature of sqrt(PSD) (audio_util.py:446-451)
@@ -356,7 +278,7 @@ __global__ __launch_bounds__(RT_FRONT_THREADS) void rt_front_kernel(RtArgs a) {
         __syncthreads();
         if (k < 2 * NELE_NBANDS) {
             const int i = k & 63;
-            const float e = (k < NELE_NBANDS) ? rt_band_energy(pc, i) : rt_band_energy(pn, i);
+            const float e = (k < NELE_NBANDS) ? band_energy(pc, i) : band_energy(pn, i);
             const float v = nele_pow_f32(e, (float)(1.0 / 6.0));
             float* row = act0 + (f % RT_RING) * 128;
             row[k] = v;                                            // the bf16 mode rounds it where the layer stages it
@@ -584,18 +506,8 @@ __global__ __launch_bounds__(256) void rt_head_kernel(RtArgs a, const float* __r
     const float2* Xa = specr + (fa & 1) * NELE_NBINS;
     const float2* Xb = specr + (fb & 1) * NELE_NBINS;
     fft512_init_twiddles(s);
-    auto gain_of = [&](const float* g2, int kk) -> double {          // interp_band_gain + np.sqrt (audio_util.py:93-110, 85)
-        if (kk <= 1) return sqrt(1e-4);
-        if (kk == NELE_NBINS - 1) return sqrt(1e-2);
-        int i = 0;
-        while (c_rt_gmt[i + 1] <= kk) ++i;
-        const int size = c_rt_gmt[i + 1] - c_rt_gmt[i], jj = kk - c_rt_gmt[i];
-        const double frac = (double)jj / (double)size;
-        const float g = (float)(1.0 - frac) * g2[i] + (float)frac * g2[i + 1];
-        return sqrt((double)g);
-    };
     for (int kk = tid; kk < NELE_NBINS; kk += 256) {
-        const double ga = gain_of(a2a, kk), gb = gain_of(a2b, kk);
+        const double ga = band_gain_sqrt(a2a, kk), gb = band_gain_sqrt(a2b, kk);
         const float2 xa = Xa[kk], xb = Xb[kk];
         double ar = ga * (double)xa.x, ai = ga * (double)xa.y;
         double br = gb * (double)xb.x, bi = gb * (double)xb.y;
@@ -609,12 +521,7 @@ __global__ __launch_bounds__(256) void rt_head_kernel(RtArgs a, const float* __r
         const int n = tid;
         const double x1 = s.x[n + 256].x * (1.0 / 512.0);
         const double x2 = s.x[n].y * (1.0 / 512.0);
-        const double wa = rt_hann(n + 256), wb = rt_hann(n);
-        float y = (float)(wa * x1);
-        y = (float)((double)y + wb * x2);
-        float wss = (float)(wa * wa);
-        wss = (float)((double)wss + wb * wb);
-        a.out[(size_t)b * a.ld + n] = y / wss;
+        a.out[(size_t)b * a.ld + n] = istft_ola(x1, x2, hann512(n + 256), hann512(n));
     }
 }
 

@@ -230,7 +230,7 @@ def test_wave_per_transform_stft_istft_are_bit_identical_to_the_workgroup_kernel
 
 def test_band_power_law_is_the_nearest_float32_to_the_float64_power():
     """`compute_band_E(...) ** p_power` (audio_util.py:434, 451): the kernels' x ** float32(1/6) fast path (float32 hardware log2 / exp2 +
-    one float64 Newton step, features.hip pow_f32) against numpy's float64 power of the SAME band energies (power = 1 returns them raw),
+    one float64 Newton step, common.h nele_pow_f32) against numpy's float64 power of the SAME band energies (power = 1 returns them raw),
     rounded to float32: equal except where a tie falls the other way (1 ulp, a few in 10^7); general exponents take the float64 pow."""
     from nele_gan_amd import audio_util as au
     from nele_gan_amd import synth
@@ -263,11 +263,14 @@ def test_band_power_law_is_the_nearest_float32_to_the_float64_power():
     assert np.mean(nb.cpu().numpy() != w) < 5e-6
 
 
-@pytest.mark.parametrize('B,L,ragged', [(3, 40000, False), (5, 64000, True), (2, 128000, True), (1, 5000, False), (4, 3800, True)])
+@pytest.mark.parametrize('B,L,ragged', [(3, 40000, False), (5, 64000, True), (2, 128000, True), (1, 5000, False), (4, 3800, True),
+                                        (7, 40000, (157, 150, 30, 17, 16, 15, 1))])
 def test_two_kernel_imcra_is_bit_identical_to_the_one_kernel_form(B, L, ragged):
     """nele_imcra_band_ws (|Y|^2 at once, then the indicator and the prior + tracker as one thread per utterance and bin)
     against nele_imcra_band_var (everything in one serial kernel): the same PSD and band feature, bit for bit - frames 0..14 (float32
-    lambda_D), the hand-over at frames 15 / 16, minima-store rotations, short rows of a padded batch."""
+    lambda_D), the hand-over at frames 15 / 16, minima-store rotations, short rows of a padded batch.  A tuple gives the rows' frame
+    counts: a count that is no multiple of the 8-frame prefetch batch (157), the first overwrite of the eight-slot minima ring
+    (frame 149), the first minima store (frame 29), the hand-over frames 16 and 15, the last float32 frame, and the first frame alone."""
     import ctypes
     from nele_gan_amd import _lib
     from nele_gan_amd import audio_util as au
@@ -276,10 +279,14 @@ def test_two_kernel_imcra_is_bit_identical_to_the_one_kernel_form(B, L, ragged):
     x = torch.from_numpy(v + 0.3 * c).cuda()
     T = 1 + L // 256
     lens = None
-    if ragged:
+    if isinstance(ragged, tuple):                        # T_b frames: 256 (T_b - 1) + r samples (r = 200: the one-frame row reflects inside itself)
+        lens = torch.tensor([min(L, 256 * (f - 1) + 200) for f in ragged], dtype=torch.int32)
+    elif ragged:
         lens = torch.tensor([L - 777 * k for k in range(B)], dtype=torch.int32)
     spec, _ = au.stft_band(x, want_band=False, lengths=lens)
     frames = None if lens is None else (1 + lens // 256).to(torch.int32).cuda()
+    if isinstance(ragged, tuple):
+        assert frames.tolist() == list(ragged) and T == max(ragged)
     out = []
     for two in (False, True):
         psd = torch.full((B, T, 257), -1.0, dtype=torch.float32, device='cuda')
