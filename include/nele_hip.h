@@ -477,6 +477,18 @@ int nele_metric_estoi(const float* x, const float* y, int B, int L, void* worksp
                       float* mapped, void* stream);
 int nele_metric_estoi_var(const float* x, const float* y, const int* lengths, int B, int L, void* workspace, long long workspace_bytes,
                           float* raw, float* mapped, void* stream);
+/* Diagnostic (tests): what a nele_metric_estoi[_var] call leaves in its workspace, stage by stage, as byte ranges in the convention of
+ * nele_metric_siib_clean_sections: out[3k..3k+2] = {offset, stride, bytes}, utterance b's part = the first `bytes` bytes at
+ * offset + b * stride.  Six per-utterance sections, in this order (n10 = ceil(5 L / 8), F = frames of 256 at hop 128 in n10 samples, both
+ * of the padded length L; a shorter row fills the front of its part with its own n10 / F entries per plane):
+ *   0 xr    double [2][n10]    x then y at 10 kHz
+ *   1 en    double [F]         frame energies of x in dB
+ *   2 keep  int    [F]         keep[k] = original index of the k-th kept frame, k < nkept
+ *   3 nkept int                frames within 40 dB of the loudest clean frame
+ *   4 tob   double [2][15][F]  third-octave magnitudes of kept frame k of the silence-removed x, then y
+ *   5 dseg  double [F]         mean product of the normalised segment of kept frames m .. m + 29, m <= nkept - 30
+ * Returns the number of sections (max_sections >= 6) or a negative status.  Host-only: no device work. */
+int nele_metric_estoi_sections(int B, int L, long long* out, int max_sections);
 
 /* intel.py:57-100 SIIB_Wrapper[_raw]_harvard: VAD (intel.py:37-50), replication rule (intel.py:93-97) and
  * pysiib.SIIB(x, y, 16000, gauss=True) (algorithm restated, oracle/siib.py).  info [B][4] (may be NULL) =
@@ -500,6 +512,8 @@ int nele_metric_siib_phase(const float* x, const float* y, int B, int L, void* w
  * ranges of the workspace, out[3k..3k+2] = {offset, stride, bytes}: stride > 0 = per-utterance section (utterance b's part = the first
  * `bytes` bytes at offset + b * stride), stride 0 = a table all utterances share.  A caller may copy the ranges out after phase 3 and, in
  * a later call with the same L, copy them in (any row order, any B) INSTEAD of running phase 3: phase 4 then gives bit-identical scores.
+ * Order (fixed; readers index it): 0 g2, 1 tab, 2 g2t (shared tables), 3 rowstat [2][28][2], 4 xdb [NT], 5 list [NA] int, 6 info [4] int,
+ * 7 nprim int, 8 XL clean half [28][NA], 9 lam [420], 10 U [420][420], 11 mu clean half [420], 12 the eigensolver's repair flag.
  * Returns the number of sections (max_sections >= 13) or a negative status.  Host-only: no device work. */
 int nele_metric_siib_clean_sections(int B, int L, long long* out, int max_sections);
 /* Same with per-utterance lengths (the frame-periodic shortcut for L % 200 == 0 is not taken then; results are identical). */

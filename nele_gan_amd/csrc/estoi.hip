@@ -441,17 +441,49 @@ static void estoi_dims(int L, int* n10, int* F) {
     *F = (*n10 >= ES_NFRAME) ? (*n10 - ES_NFRAME) / ES_HOP + 1 : 0;
 }
 
-extern "C" long long nele_metric_estoi_workspace_bytes(int B, int L) {
+// The one place that carves a workspace: the filter with its step table, then the six stage buffers in the order of EstoiWs (each aligned
+// to 256 bytes).  w == nullptr: only the size.  *h: the filter's place.
+static size_t estoi_layout(int B, int L, EstoiWs* w, double** h, char* base) {
     int n10, F;
     estoi_dims(L, &n10, &F);
-    size_t t = align256(sizeof(double) * (ES_HPAD + ES_HTAB));
-    t += align256(sizeof(double) * (size_t)B * 2 * n10);
-    t += align256(sizeof(double) * (size_t)B * F);
-    t += align256(sizeof(int) * (size_t)B * F);
-    t += align256(sizeof(int) * (size_t)B);
-    t += align256(sizeof(double) * (size_t)B * 2 * ES_NB * F);
-    t += align256(sizeof(double) * (size_t)B * F);
-    return (long long)t;
+    size_t o = 0;
+    if (h) *h = (double*)base;
+    o += align256(sizeof(double) * (ES_HPAD + ES_HTAB));                                   // filter + the five-output step table
+#define TAKE(field, type, count) do { if (w) w->field = (type*)(base + o); o += align256(sizeof(type) * (size_t)(count)); } while (0)
+    TAKE(xr, double, (size_t)B * 2 * n10);
+    TAKE(en, double, (size_t)B * F);
+    TAKE(keep, int, (size_t)B * F);
+    TAKE(nkept, int, (size_t)B);
+    TAKE(tob, double, (size_t)B * 2 * ES_NB * F);
+    TAKE(dseg, double, (size_t)B * F);
+#undef TAKE
+    if (w) { w->n10 = n10; w->F = F; w->L = L; w->lens = nullptr; }
+    return o;
+}
+
+extern "C" long long nele_metric_estoi_workspace_bytes(int B, int L) { return (long long)estoi_layout(B, L, nullptr, nullptr, nullptr); }
+
+// What a call leaves in its workspace, stage by stage, as byte ranges: out[3 k .. 3 k + 2] = {offset, stride, bytes}, utterance b's part =
+// the first `bytes` bytes at offset + b * stride (every section is per utterance).  Strides are those of the padded length L; a shorter
+// row fills the front of its part (its own n10 and F, see es_n10 / es_frames) and leaves the rest as it was.  Order: xr [2][n10] float64
+// (10 kHz x then y), en [F] float64 (dB), keep [F] int (original frame of kept frame k, k < nkept), nkept int, tob [2][15][F] float64
+// (x then y, third-octave magnitudes of kept frame k), dseg [F] float64 (segment m = kept frames m .. m + 29, m <= nkept - 30).
+extern "C" int nele_metric_estoi_sections(int B, int L, long long* out, int max_sections) {
+    NELE_CHECK_ARG(B > 0 && L > 0 && out && max_sections >= 6, "nele_metric_estoi_sections: bad arguments (6 sections)");
+    EstoiWs w;
+    char* base = reinterpret_cast<char*>((uintptr_t)1 << 20);
+    estoi_layout(B, L, &w, nullptr, base);
+    int k = 0;
+    auto put = [&](const void* p, long long bytes) {
+        out[3 * k] = (long long)(reinterpret_cast<const char*>(p) - base); out[3 * k + 1] = bytes; out[3 * k + 2] = bytes; ++k;
+    };
+    put(w.xr, sizeof(double) * 2 * (size_t)w.n10);
+    put(w.en, sizeof(double) * (size_t)w.F);
+    put(w.keep, sizeof(int) * (size_t)w.F);
+    put(w.nkept, sizeof(int));
+    put(w.tob, sizeof(double) * 2 * ES_NB * (size_t)w.F);
+    put(w.dseg, sizeof(double) * (size_t)w.F);
+    return k;
 }
 
 extern "C" int nele_metric_estoi_var(const float* x, const float* y, const int* lengths, int B, int L, void* workspace, long long workspace_bytes,
@@ -462,16 +494,10 @@ extern "C" int nele_metric_estoi_var(const float* x, const float* y, const int* 
     if (F < 1) return nele_set_error(NELE_ERR_SIGNAL, "nele_metric_estoi: L=%d too short", L);
     if (workspace_bytes < nele_metric_estoi_workspace_bytes(B, L))
         return nele_set_error(NELE_ERR_WORKSPACE, "nele_metric_estoi: workspace too small");
-    char* p = (char*)workspace;
-    double* h = (double*)p; p += align256(sizeof(double) * (ES_HPAD + ES_HTAB));     // filter + the five-output step table
+    double* h;
     EstoiWs ws;
-    ws.n10 = n10; ws.F = F; ws.lens = lengths; ws.L = L;
-    ws.xr = (double*)p; p += align256(sizeof(double) * (size_t)B * 2 * n10);
-    ws.en = (double*)p; p += align256(sizeof(double) * (size_t)B * F);
-    ws.keep = (int*)p; p += align256(sizeof(int) * (size_t)B * F);
-    ws.nkept = (int*)p; p += align256(sizeof(int) * (size_t)B);
-    ws.tob = (double*)p; p += align256(sizeof(double) * (size_t)B * 2 * ES_NB * F);
-    ws.dseg = (double*)p;
+    estoi_layout(B, L, &ws, &h, (char*)workspace);
+    ws.lens = lengths;
     hipStream_t s = as_stream(stream);
     hipLaunchKernelGGL(estoi_filter_kernel, dim3(1), dim3(1024), 0, s, h);
     const int rs5 = NELE_SWITCH_INT("NELE_ESTOI_RS5", 1);                                   // NELE_ESTOI_RS5=0: the output-per-thread resampler (A/B diagnostic)

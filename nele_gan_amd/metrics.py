@@ -266,6 +266,75 @@ def batch_estoi(x, y, lengths=None):
     return raw, mapped
 
 
+def _section_rows(ws, sections, B):
+    """Per-utterance sections {offset, stride, bytes} of workspace ``ws`` -> one numpy uint8 array [B, bytes] each (synchronises)."""
+    return [ws[off:off + B * st].view(B, st)[:, :nb].cpu().numpy() for (off, st, nb) in sections]
+
+
+def estoi_stages(x, y, lengths=None):
+    """Diagnostic: batch_estoi on a workspace of its own (every byte 0xFF before the call: what a kernel does not write reads as NaN / -1)
+    -> (raw float32 numpy [B], stages), the workspace read through nele_metric_estoi_sections.  stages[name][b] is row b's array, cut to the
+    row's own sizes (n10 = ceil(5 len / 8) samples at 10 kHz, F frames of 256 at hop 128, nkept frames inside the 40 dB gate):
+      'xr' [2, n10] x then y at 10 kHz; 'en' [F] dB; 'keep' [nkept] original frame of each kept frame; 'nkept' int;
+      'tob' [2, 15, nkept] third-octave magnitudes of the silence-removed x then y; 'dseg' [max(nkept - 29, 0)] per-segment mean products."""
+    x, y, _ = _pair(x, y)
+    B, L = x.shape
+    ws = torch.full((int(_lib.lib.nele_metric_estoi_workspace_bytes(B, L)),), 255, dtype=torch.uint8, device=x.device)
+    raw = torch.empty(B, device=x.device)
+    call('nele_metric_estoi_var', ptr(x), ptr(y), ptr(_lens(lengths, x.device)), B, L, ptr(ws), ws.numel(), ptr(raw), None, stream())
+    buf = (c_longlong * 18)()
+    n = _lib.lib.nele_metric_estoi_sections(B, L, buf, 6)
+    if n != 6:
+        _lib.check(n, 'nele_metric_estoi_sections')
+    xr, en, keep, nkept, tob, dseg = _section_rows(ws, [(int(buf[3 * k]), int(buf[3 * k + 1]), int(buf[3 * k + 2])) for k in range(6)], B)
+    lens = np.full(B, L) if lengths is None else np.minimum(np.asarray(torch.as_tensor(lengths).cpu()), L)
+    nkept = nkept.view(np.int32)[:, 0].copy()
+    out = {k: [] for k in ('xr', 'en', 'keep', 'tob', 'dseg')}
+    out['nkept'] = nkept
+    for b in range(B):
+        n10 = -(-5 * int(lens[b]) // 8)
+        F = (n10 - 256) // 128 + 1 if n10 >= 256 else 0
+        nk = int(nkept[b])
+        out['xr'].append(xr[b].view(np.float64).reshape(2, -1)[:, :n10].copy())
+        out['en'].append(en[b].view(np.float64)[:F].copy())
+        out['keep'].append(keep[b].view(np.int32)[:max(nk, 0)].copy())
+        out['tob'].append(tob[b].view(np.float64).reshape(2, 15, -1)[:, :, :max(nk, 0)].copy())
+        out['dseg'].append(dseg[b].view(np.float64)[:max(nk - 29, 0)].copy())
+    return raw.cpu().numpy(), out
+
+
+def siib_clean_stages(x, lengths=None):
+    """Diagnostic: phase 3 of nele_metric_siib_var (the clean-signal half) on a workspace of its own (every byte 0xFF before the call)
+    -> dict of per-row numpy arrays, read through nele_metric_siib_clean_sections.  What the buffers hold after phase 3 (csrc/siib.hip):
+      'info' [B, 4] int = (M, frames of the M-times tiled signal, active frames na, status).  M is the replication factor of intel.py:93-97
+          CLAMPED to 40 (status bit 1 set when the rule asked for more): every other buffer describes the signal tiled M <= 40 times.
+      'xdb'[b] [info[b, 1]] float64: 10 log10(mean(frame^2) + eps) of EVERY frame f of the tiled signal, in the tiled frame numbering:
+          frame f holds samples (200 f + j) mod len, j < 400, of the row (zero past M * len); nothing is materialised.
+      'list'[b] [na] int: the active frames (xdb > order statistic - 40), ascending, in that tiled frame numbering.
+      'XL'[b] [28, na] float64: band-major (row j = gammatone band j, column a = a-th ACTIVE frame): log band energies of the clean
+          signal AFTER forward masking and BEFORE mean removal (the row mean is subtracted on the fly by the kernels that consume XL).
+      'rowstat'[b] [28, 2] float64 of the clean signal: (band minimum BEFORE masking, band mean AFTER masking).
+      'lam'[b] [420] float64: eigenvalues of the KLT covariance, ascending (all of them; eigenvectors exist above the 1e-10 cut only)."""
+    sp = SiibSplit(x if torch.is_tensor(x) and x.is_cuda else torch.as_tensor(np.ascontiguousarray(x)).cuda(), lengths=lengths, owner={})
+    B, L = sp.x.shape
+    sp.ws.fill_(255)
+    sp._call(3)
+    sec = CleanStateCache._sections('siib', B, L, 0)
+    if sec is None:
+        _lib.check(-1, 'nele_metric_siib_clean_sections')
+    rowstat, xdb, lst, info, _nprim, XL, lam = _section_rows(sp.ws, sec[3:10], B)      # sections 3 .. 9 (include/nele_hip.h)
+    info = info.view(np.int32).copy()
+    out = {'info': info, 'xdb': [], 'list': [], 'XL': [], 'rowstat': [], 'lam': []}
+    for b in range(B):
+        nt, na = int(info[b, 1]), int(info[b, 2])
+        out['xdb'].append(xdb[b].view(np.float64)[:nt].copy())
+        out['list'].append(lst[b].view(np.int32)[:na].copy())
+        out['XL'].append(XL[b].view(np.float64).reshape(28, -1)[:, :na].copy())
+        out['rowstat'].append(rowstat[b].view(np.float64).reshape(2, 28, 2)[0].copy())
+        out['lam'].append(lam[b].view(np.float64).copy())
+    return out
+
+
 class SiibSplit:
     """batch_siib in pieces.  front()/back(): wide kernels (VAD .. covariance) / latency-bound eigen-decomposition .. score, so
     that independent work can be enqueued in between on another stream.  clean_part()/degraded_part(y): split by data
