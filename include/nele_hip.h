@@ -579,6 +579,27 @@ int nele_metric_haspi_var(const float* x, const float* y, const int* lengths, in
  * file, recomputed by the reference every epoch): byte ranges {offset, stride, bytes} of what phase 3 leaves for phase 4.  Valid for the
  * same L, fs_in, audiogram and dither rows.  max_sections >= 16. */
 int nele_metric_haspi_clean_sections(int B, int L, int fs_in, long long* out, int max_sections);
+/* Diagnostic (tests): the per-utterance buffers a default phase-0 call of nele_metric_haspi_var[_hl] leaves in its workspace, stage by
+ * stage, {offset, stride, bytes} as above.  n24p = samples at 24 kHz of the padded length L, rounded up to 32; nsub = ceil(n24 / 9); a
+ * shorter row fills the front of each plane with its own n24 / nsub / n_active entries.  Fifteen sections, in this order:
+ *    0 r24   float  [2][n24p]       rms-normalised x then y at 24 kHz before the RMS-restore gain rinfo[2]; zeros behind the row's n24
+ *    1 mid   double [2][n24p]       middle-ear output
+ *    2 bw    double [2][32]         adjusted bandwidths BWx, BWy
+ *    3 shift int    [32]            group-delay shifts
+ *    4 rinfo float  [2][4]          {rms of the input, rms of the normalised input, restore gain, unused}
+ *    5 env   float  [2][n24p][32]   envelope in dB SL after compression, BEFORE IHC adaptation (the adapted one is never stored)
+ *    6 ctl   float  [2][n24p][32]   control-bank |u|^2 without the filter gain
+ *    7 lp    double [2][nsub+4][32] low-passed, sub-sampled adapted envelope in GROUP-space rows: frame i of channel c is row i - di(c),
+ *                                   di = (ul + shift[c] - 26) / 9 with ul = (26 - shift[c]) mod 9; rows below 0 read as zero
+ *    8 act   int    [nsub]          position of frame i among the active frames, or -1
+ *    9 info  int    [2]             {n_active, status}
+ *   10 cep   double [2][6][nsub]    cepstral sequences of x then y, mean already removed, columns < n_active
+ *   11 cmean double [2][6]          zeros on this path (what the modulation filters still subtract)
+ *   12 xf    double [nsub][64]      modulation-filtered clean sequences, rows < n_active, lane = (basis - 1) * 10 + band < 50
+ *   13 cm    double [6][10]         |rho| per (basis, band); row 0 is not written
+ *   14 loss  double [2][5][32]      stride 0 (shared): attnOHC, BWmin, lowknee, CR, attnIHC of x then y
+ * Returns the number of sections (max_sections >= 15) or a negative status.  Host-only: no device work. */
+int nele_metric_haspi_sections(int B, int L, int fs_in, long long* out, int max_sections);
 /* pyhaspi2.py:362-365: the reference dithers the envelopes in EVERY haspi_v2 call with np.random.randn(n_active, 32) rows (x, then y)
  * from numpy's global generator.  This fills the `dither` argument of nele_metric_haspi* with rows that are a pure function of
  * (seed, utt_ids[b], signal, active-frame index, channel): the same on whichever rank / in whichever batch the utterance is scored

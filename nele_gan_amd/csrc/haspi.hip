@@ -38,9 +38,14 @@
 
 // Storage type of the two per-sample, per-channel envelope arrays (12.6 GB each in float64 at B = 256, and every stage between the
 // filter banks and the envelope low-pass streams them through HBM).  All ARITHMETIC on them stays float64 (filter states, IHC
-// adaptation, FIR sums); only the stored |u|^2 / dB values are rounded to float32: 6e-8 relative = 2.6e-7 dB on |u|^2, < 4e-6 dB on
-// the dB-SL envelope (values 0..100) - against the 0.1 dB dither the reference itself adds per frame (pyhaspi2.py:362-365), and
-// 1e-4 relative on the final score (measured effect: < 1e-7, tests/test_metrics_gpu.py golden + oracle comparisons).
+// adaptation, FIR sums); only the stored |u|^2 / dB values are rounded to float32: 6e-8 relative = 2.6e-7 dB on |u|^2 (measured: 0.98
+// of half an ulp), and half an ulp of the stored dB-SL value is 1.9e-6 dB below 64 dB.  The dB-SL envelope as a whole - float32 storage
+// AND the float32 hardware log2 / exp2 gain pass that produces it (hp_log2f below) - is within 6.0e-5 dB of the float64 reference a
+// priori (tests/haspi_cases.py:env_budget_db adds up every rounding) and within 4.4e-5 dB measured (1.8e-5 .. 2.9e-5 in most cases); the
+// low-passed envelope lp within 3.6e-5 dB, the cepstra within 1.9e-5, the correlations within 6.7e-7 and the score within one float32
+// ulp (tests/test_haspi_stages_gpu.py, stage by stage against oracle/haspi.py).  An earlier version of this comment claimed "< 4e-6 dB":
+// that was the storage alone, before the gain pass moved to the float32 unit.  All of it against the 0.1 dB dither the reference
+// itself adds per frame (pyhaspi2.py:362-365).
 typedef float hp_env_t;
 
 struct HaspiWs {
@@ -718,8 +723,10 @@ __global__ __launch_bounds__(64) void haspi_bank_prefix_kernel(HaspiWs ws, int s
 #define GL_N 2048
 #define GL_W 256
 #define GL_U 8
-// log2 / exp2 on the float32 transcendental unit (v_log_f32 / v_exp_f32, 1 ulp): the dB values they produce are accurate to 1e-6 dB,
-// like the float32 storage of the envelopes (see hp_env_t); the float64 log10 / exp / sqrt calls they replace were 90 % of this
+// log2 / exp2 on the float32 transcendental unit (v_log_f32 / v_exp_f32, 1 ulp).  One ulp of a log2 result in [32, 64) - |u|^2 spans 2^56
+// here - is 3.8e-6, i.e. 1.1e-5 dB, and the float32 product 10 log10(2) log2(.) below 256 rounds by up to 7.6e-6 dB more: the dB values
+// of the gain pass are accurate to 6.0e-5 dB in the worst case and 4.4e-5 dB measured (see hp_env_t), not to the 1e-6 dB this comment
+// once claimed; the float64 log10 / exp / sqrt calls they replace were 90 % of this
 // kernel's instructions and kept it compute-bound at 0.3 of the HBM rate.
 __device__ __forceinline__ float hp_log2f(float x) { return __builtin_amdgcn_logf(x); }
 __device__ __forceinline__ float hp_exp2f(float x) { return __builtin_amdgcn_exp2f(x); }
@@ -2133,6 +2140,58 @@ extern "C" int nele_metric_haspi_clean_sections(int B, int L, int fs_in, long lo
     put(w.info, sizeof(int) * 2, sizeof(int) * 2);
     put(w.cep, sizeof(double) * 2 * HP_NBASIS * ns, sizeof(double) * HP_NBASIS * ns);                             // clean half
     put(w.xf, sizeof(double) * 64 * ns, sizeof(double) * 64 * ns);
+    return k;
+}
+
+// Diagnostic (tests): the per-utterance buffers a DEFAULT phase-0 call (no NELE_AB switch: chunk-parallel IIRs, gain pass inside the signal
+// bank, haspi_ihc_fir9_kernel, the serial cepstrum kernel, the sliding modulation filters) leaves in its workspace, as {offset, stride,
+// bytes} like nele_metric_haspi_clean_sections.  n24p = n24 of the padded length rounded up to 32, nsub = ceil(n24 / 9); a shorter row
+// fills the front of each plane with its own n24 / nsub / n_active entries, what lies behind is unspecified.
+//    0 r24   float  [2][n24p]       rms-normalised x then y at 24 kHz BEFORE the RMS-restore gain rinfo[2] (the middle-ear kernel applies it
+//                                   in float32 on load); zeros from the row's n24 to n24p
+//    1 mid   double [2][n24p]       middle-ear output
+//    2 bw    double [2][32]         adjusted bandwidths BWx, BWy
+//    3 shift int    [32]            group-delay shifts (from BWx)
+//    4 rinfo float  [2][4]          {rms of the input, rms of the normalised input, restore gain, unused} (24 kHz input: {rms, 1, 1, unused})
+//    5 env   float  [2][n24p][32]   envelope in dB SL after compression and BEFORE IHC adaptation (haspi_bank_scan_kernel<true,true,false,true>);
+//                                   the adapted envelope is never stored (haspi_ihc_fir9_kernel consumes it on the fly)
+//    6 ctl   float  [2][n24p][32]   control-bank |u|^2 WITHOUT the filter gain: control envelope = gain(BW1) sqrt(ctl)
+//    7 lp    double [2][nsub+4][32] low-passed, sub-sampled ADAPTED envelope in group-space rows: frame i of channel c is row i - di(c),
+//                                   di = (ul + shift - 26) / 9, ul = (26 - shift) mod 9; rows g < 0 read as zero (hp_lp_di / hp_lp_at)
+//    8 act   int    [nsub]          compacted position of frame i among the active frames, or -1 (grank stays unwritten on this path)
+//    9 info  int    [2]             {n_active, status}
+//   10 cep   double [2][6][nsub]    cepstral sequences of x then y, mean-removed IN PLACE, columns < n_active
+//   11 cmean double [2][6]          zeros (the mean is already removed; the modulation filters subtract cmean on load)
+//   12 xf    double [nsub][64]      modulation-filtered clean sequences, rows < n_active, lane = (basis - 1) * 10 + band < 50
+//   13 cm    double [6][10]         |rho| per (basis, band); row 0 is never written
+//   14 loss  double [2][5][32]      stride 0: attnOHC, BWmin, lowknee, CR, attnIHC of x then y
+// Returns the number of sections (max_sections >= 15) or a negative status.  Host-only: no device work.
+extern "C" int nele_metric_haspi_sections(int B, int L, int fs_in, long long* out, int max_sections) {
+    NELE_CHECK_ARG(B > 0 && out && max_sections >= 15, "nele_metric_haspi_sections: bad arguments (15 sections)");
+    NELE_CHECK_ARG(fs_in >= 1000 && fs_in <= 24000 && L >= 2400, "nele_metric_haspi_sections: bad signal geometry");
+    HaspiWs w;
+    char* base = reinterpret_cast<char*>((uintptr_t)1 << 20);
+    haspi_layout(B, L, fs_in, &w, base);
+    int k = 0;
+    auto put = [&](const void* p, size_t bytes, bool shared = false) {
+        out[3 * k] = (long long)(reinterpret_cast<const char*>(p) - base); out[3 * k + 1] = shared ? 0 : (long long)bytes; out[3 * k + 2] = (long long)bytes; ++k;
+    };
+    const size_t ns = (size_t)w.nsub, np = (size_t)w.n24p;
+    put(w.r24, sizeof(float) * 2 * np);
+    put(w.mid, sizeof(double) * 2 * np);
+    put(w.bw, sizeof(double) * 2 * HP_NCH);
+    put(w.shift, sizeof(int) * HP_NCH);
+    put(w.rinfo, sizeof(float) * 2 * 4);
+    put(w.env, sizeof(hp_env_t) * 2 * np * HP_NCH);
+    put(w.ctl, sizeof(hp_env_t) * 2 * np * HP_NCH);
+    put(w.lp, sizeof(double) * 2 * (size_t)w.nlp * HP_NCH);
+    put(w.act, sizeof(int) * ns);
+    put(w.info, sizeof(int) * 2);
+    put(w.cep, sizeof(double) * 2 * HP_NBASIS * ns);
+    put(w.cmean, sizeof(double) * 2 * HP_NBASIS);
+    put(w.xf, sizeof(double) * 64 * ns);
+    put(w.cm, sizeof(double) * HP_NBASIS * HP_NMOD);
+    put(w.loss, sizeof(double) * 2 * 5 * HP_NCH, true);
     return k;
 }
 

@@ -495,6 +495,78 @@ def batch_haspi(x, y, fs=16000, dither=None, seed=None, return_info=False, lengt
     return raw, mapped
 
 
+def haspi_stages(x, y, fs, lengths=None, dither=None, HL=None):
+    """Diagnostic: batch_haspi on a workspace of its own (every byte 0xFF before the call: what a kernel does not write reads as NaN / -1),
+    ONE nele_metric_haspi_var_hl call at phase 0 -> (raw float32 numpy [B], info int32 numpy [B, 2] = (n_active, status), stages): the
+    workspace read through nele_metric_haspi_sections.  stages[name][b] is row b's array, cut to the row's own sizes (n24 samples at
+    24 kHz, nsub = ceil(n24 / 9) frames, na = n_active frames above the silence gate):
+      'r24' [2, n24] float32: x then y at 24 kHz WITH the RMS-restore gain (float32(gain * stored), the product the middle-ear kernel forms);
+      'rinfo' [2, 4] float32; 'mid' [2, n24]; 'ctl' [2, n24, 32] float32 control |u|^2 without the filter gain; 'bw' [2, 32]; 'shift' [32];
+      'env' [2, n24, 32] float32 dB SL before IHC adaptation; 'lp' [2, nsub, 32] in FRAME order (the group-space rows of the workspace are
+      un-shuffled here: frame i of channel c = row i - di(c), rows below 0 are zero); 'index' [na] the active frames, from 'act' [nsub];
+      'cep' [2, 6, na] MEAN-REMOVED (the kernel stores the sequences mean-removed with cmean = 0; stored - cmean is returned, which is the
+      mean-removed sequence whichever of the two holds the mean); 'cmean' [2, 6] as stored; 'xf' [na, 50]; 'cm' [5, 10] (bases 1..5);
+      'loss' [2, 5, 32] (shared by the rows)."""
+    x, y, _ = _pair(x, y)
+    B, L = x.shape
+    fs = int(fs)
+    nsub = _lib.lib.nele_metric_haspi_nsub(L, fs)
+    if dither is not None:
+        dither = torch.as_tensor(dither)
+        if tuple(dither.shape) != (B, 2, nsub, 32) or dither.dtype != torch.float64:
+            raise ValueError("haspi_stages: dither must be float64 [B, 2, %d, 32]" % nsub)
+        dither = dither.to(x.device).contiguous()
+    ws = torch.full((int(_lib.lib.nele_metric_haspi_workspace_bytes(B, L, fs)),), 255, dtype=torch.uint8, device=x.device)
+    raw = torch.empty(B, device=x.device)
+    info = torch.full((B, 2), -1, dtype=torch.int32, device=x.device)
+    lens = _lens(lengths, x.device)
+    call('nele_metric_haspi_var_hl', ptr(x), ptr(y), ptr(lens), B, L, fs, ptr(dither), _hl6(HL), 0, ptr(ws), ws.numel(), ptr(raw), None, ptr(info), 0,
+         stream())
+    buf = (c_longlong * 45)()
+    n = _lib.lib.nele_metric_haspi_sections(B, L, fs, buf, 15)
+    if n != 15:
+        _lib.check(n, 'nele_metric_haspi_sections')
+    sec = [(int(buf[3 * k]), int(buf[3 * k + 1]), int(buf[3 * k + 2])) for k in range(15)]
+    r24, mid, bw, shift, rinfo, env, ctl, lp, act, winfo, cep, cmean, xf, cm = _section_rows(ws, sec[:14], B)
+    loss = ws[sec[14][0]:sec[14][0] + sec[14][2]].cpu().numpy().view(np.float64).reshape(2, 5, 32).copy()
+    info = info.cpu().numpy()
+    lens = np.full(B, L) if lengths is None else np.minimum(np.asarray(torch.as_tensor(lengths).cpu()), L)
+    names = ('r24', 'rinfo', 'mid', 'ctl', 'bw', 'shift', 'env', 'lp', 'index', 'cep', 'cmean', 'xf', 'cm', 'act', 'info')
+    out = {k: [] for k in names}
+    out['loss'] = loss
+    for b in range(B):
+        n24 = int(lens[b]) if fs == 24000 else int(np.ceil(float(int(lens[b])) * (24000.0 / fs)))
+        ns = -(-n24 // 9)
+        ri = rinfo[b].view(np.float32).reshape(2, 4).copy()
+        sh = shift[b].view(np.int32).copy()
+        a = act[b].view(np.int32)[:ns].copy()
+        wi = winfo[b].view(np.int32).copy()
+        na = max(int(wi[0]), 0)
+        out['rinfo'].append(ri)
+        out['r24'].append(ri[:, 2:3] * r24[b].view(np.float32).reshape(2, -1)[:, :n24])        # float32 product, as haspi_midear_par_kernel forms it
+        out['mid'].append(mid[b].view(np.float64).reshape(2, -1)[:, :n24].copy())
+        out['ctl'].append(ctl[b].view(np.float32).reshape(2, -1, 32)[:, :n24].copy())
+        out['env'].append(env[b].view(np.float32).reshape(2, -1, 32)[:, :n24].copy())
+        out['bw'].append(bw[b].view(np.float64).reshape(2, 32).copy())
+        out['shift'].append(sh)
+        # group-space rows -> frame order (hp_lp_di / hp_lp_at of csrc/haspi.hip)
+        di = (((26 - sh) % 9 + 9) % 9 + sh - 26) // 9
+        graw = lp[b].view(np.float64).reshape(2, nsub + 4, 32)
+        g = np.arange(ns)[:, None] - di[None, :]                                                # [ns, 32]
+        fr = graw[:, np.clip(g, 0, nsub + 3), np.arange(32)[None, :]]
+        out['lp'].append(np.where((g >= 0)[None], fr, 0.0))
+        out['act'].append(a)
+        order = np.argsort(a, kind='stable')
+        out['index'].append(order[a[order] >= 0])                                               # frame of the k-th active position
+        out['info'].append(wi)
+        cm_ = cmean[b].view(np.float64).reshape(2, 6).copy()
+        out['cmean'].append(cm_)
+        out['cep'].append(cep[b].view(np.float64).reshape(2, 6, nsub)[:, :, :na] - cm_[:, :, None])
+        out['xf'].append(xf[b].view(np.float64).reshape(nsub, 64)[:na, :50].copy())
+        out['cm'].append(cm[b].view(np.float64).reshape(6, 10)[1:].copy())
+    return raw.cpu().numpy(), info, out
+
+
 def haspi_dither_rows(utt_ids, seed, L, fs=16000, device=None):
     """Dither rows [B, 2, nsub, 32] float64 for batch_haspi / HaspiSplit, drawn per UTTERANCE ID (pyhaspi2.py:362-365 draws
     np.random.randn rows on every call; here a row is a pure function of (seed, id, signal, frame, channel), so an utterance is

@@ -285,7 +285,9 @@ def ear_model_bm(x, fx, y, fy, noise_x=None, noise_y=None, HL=None, itype=0):
 
 
 def ear_model(x, fx, y, fy, HL=None, itype=0):
-    """pyhaspi2.py:1155-1248 (envelope outputs only): -> (xdB, ydB [32, nsamp], parts)."""
+    """pyhaspi2.py:1155-1248 (envelope outputs only): -> (xdB, ydB [32, nsamp], parts).  parts also holds the intermediate stages
+    (tests/test_haspi_stages_gpu.py): x24 / y24 (the signals at 24 kHz), xmid / ymid (middle-ear outputs), xctl / yctl (control envelopes),
+    xsl / ysl (the compressed envelope in dB SL BEFORE eb_IHCadapt) and xdB / ydB (adapted and shifted, the return values), [32, nsamp]."""
     cfreq = center_freq()
     (aOx, BWminx, lkx, CRx, aIx), (aOy, BWminy, lky, CRy, aIy) = _loss_pair(HL, itype)
     _, BW1, _, _, _ = loss_parameters(100 * np.ones(6), cfreq)
@@ -296,12 +298,14 @@ def ear_model(x, fx, y, fy, HL=None, itype=0):
     ymid = middle_ear(y24)
     xdB = np.zeros((NCHAN, nsamp))
     ydB = np.zeros((NCHAN, nsamp))
+    xsl, ysl, xctl, yctl = (np.zeros((NCHAN, nsamp)) for _ in range(4))
     BWx = np.zeros(NCHAN)
     BWy = np.zeros(NCHAN)
     for n in range(NCHAN):
         coscf, sincf = cos_sin_cf(nsamp, FSAMP, cfreq[n])
         xcontrol = gammatone_env(xmid, BW1[n], coscf, sincf, cfreq[n])
         ycontrol = gammatone_env(ymid, BW1[n], coscf, sincf, cfreq[n])
+        xctl[n], yctl[n] = xcontrol, ycontrol
         BWx[n] = bw_adjust(xcontrol, BWminx[n], BW1[n])
         BWy[n] = bw_adjust(ycontrol, BWminy[n], BW1[n])
         xenv = gammatone_env(xmid, BWx[n], coscf, sincf, cfreq[n])
@@ -310,6 +314,7 @@ def ear_model(x, fx, y, fy, HL=None, itype=0):
         yc = env_compress(yenv, ycontrol, aOy[n], lky[n], CRy[n])
         xc = env_sl2(xc, aIx[n])
         yc = env_sl2(yc, aIy[n])
+        xsl[n], ysl[n] = xc, yc
         xdB[n] = ihc_adapt(xc)
         ydB[n] = ihc_adapt(yc)
     shifts = group_delay_shifts(BWx, cfreq)
@@ -318,7 +323,8 @@ def ear_model(x, fx, y, fy, HL=None, itype=0):
             s = int(shifts[n])
             if s > 0:
                 arr[n] = np.concatenate((np.zeros(s), arr[n, :nsamp - s]))
-    return xdB, ydB, dict(cfreq=cfreq, BW1=BW1, BWx=BWx, BWy=BWy, shifts=shifts)
+    return xdB, ydB, dict(cfreq=cfreq, BW1=BW1, BWx=BWx, BWy=BWy, shifts=shifts, x24=x24, y24=y24, xmid=xmid, ymid=ymid, xctl=xctl, yctl=yctl,
+                          xsl=xsl, ysl=ysl, xdB=xdB, ydB=ydB)
 
 
 def env_filt(xdB, ydB, fcut=320, fsub=2560, fsamp=FSAMP):
@@ -442,8 +448,8 @@ def mod_filt(Xenv, Yenv, fsub=2560):
     return out[0], out[1]
 
 
-def mod_corr(Xmod, Ymod):
-    """pyhaspi2.py:254-273."""
+def mod_corr(Xmod, Ymod, full=False):
+    """pyhaspi2.py:254-273.  full: also the whole matrix CM [basis, band] the returned mean over bases 2-6 is taken from."""
     nchan, nmod = len(Xmod), len(Xmod[0])
     small = 1.0e-30
     CM = np.zeros([nchan, nmod])
@@ -453,6 +459,8 @@ def mod_corr(Xmod, Ymod):
             yj = Ymod[j][m] - np.mean(Ymod[j][m])
             xsum, ysum = np.sum(xj ** 2), np.sum(yj ** 2)
             CM[j, m] = 0 if (xsum < small or ysum < small) else np.abs(np.sum(xj * yj)) / np.sqrt(xsum * ysum)
+    if full:
+        return np.mean(CM[1:6], axis=0), CM
     return np.mean(CM[1:6], axis=0)
 
 
@@ -473,10 +481,10 @@ def haspi_v2(x, fx, y, fy, dither_x=None, dither_y=None, return_parts=False, HL=
     xLP, yLP = env_filt(xdB, ydB)
     xcep, ycep, index = cep_coef(xLP, yLP, dither_x=dither_x, dither_y=dither_y)
     xmod, ymod = mod_filt(xcep, ycep)
-    aveCM = mod_corr(xmod, ymod)
+    aveCM, CM = mod_corr(xmod, ymod, full=True)
     intel = float(np.sum(WEIGHTS * aveCM))
     if return_parts:
-        parts.update(xLP=xLP, yLP=yLP, index=index, xcep=xcep, ycep=ycep, aveCM=aveCM)
+        parts.update(xLP=xLP, yLP=yLP, index=index, xcep=xcep, ycep=ycep, aveCM=aveCM, Xmod=xmod, CM=CM)
         return intel, parts
     return intel, aveCM
 
