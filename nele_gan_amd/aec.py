@@ -11,7 +11,10 @@ is DESIGN.md section 14).  This module owns memory and bookkeeping only; there i
     loop = EchoCancellingEnhancer(RealtimeEnhancer(...), aec)  # closes the loop: what process() returns is what the loudspeaker plays
     out = loop.process(clean_hops, mic_hops)                   # during the next call's capture
 
-    python -m nele_gan_amd.aec --mic mic.wav --played far.wav --out residual.wav [--partitions 8] [--echo-path h.npy]
+    python -m nele_gan_amd.aec --mic mic.wav --played far.wav --out residual.wav [--partitions 8] [--echo-path h.npy] [--bulk-blocks 32]
+
+A bulk delay (the device's playback and capture buffers) is found and taken out ahead of the canceller by nele_gan_amd/bulkdelay.py
+(``AlignedEchoCanceller``; --bulk-blocks on the command line).
 """
 import numpy as np
 import torch
@@ -154,9 +157,11 @@ class EchoCancellingEnhancer:
 
 
 # ------------------------------------------------------------------------------------------------------------------ command line
-def cancel_file(mic, played, partitions=8, mu=0.5, gamma=4.0, delta=1e-2, device='cuda'):
+def cancel_file(mic, played, partitions=8, mu=0.5, gamma=4.0, delta=1e-2, device='cuda', bulk_blocks=None):
     """mic, played: float32 arrays of one length L -> (residual [L] float32, echo path [partitions * 256] float64): the whole hops through
-    one EchoCanceller call, the last L % 256 samples zero-padded to one more hop and cut again."""
+    one EchoCanceller call, the last L % 256 samples zero-padded to one more hop and cut again.  bulk_blocks: search that many blocks
+    for a bulk delay and cancel against `played` delayed by it (bulkdelay.AlignedEchoCanceller); the return value gains a third
+    element, the delay found in hops (-1: none)."""
     mic = np.ascontiguousarray(mic, dtype=np.float32).reshape(-1)
     played = np.ascontiguousarray(played, dtype=np.float32).reshape(-1)
     if mic.shape != played.shape or mic.size == 0:
@@ -167,8 +172,13 @@ def cancel_file(mic, played, partitions=8, mu=0.5, gamma=4.0, delta=1e-2, device
     x = np.zeros((1, nh * HOP), dtype=np.float32)
     d[0, :L], x[0, :L] = mic, played
     aec = EchoCanceller(1, partitions=partitions, mu=mu, gamma=gamma, delta=delta, device=device)
+    if bulk_blocks is not None:
+        from .bulkdelay import AlignedEchoCanceller, BulkDelay
+        aec = AlignedEchoCanceller(BulkDelay(1, blocks=bulk_blocks, device=device), aec)
     res = aec.process(torch.from_numpy(d), torch.from_numpy(x))
     h = aec.echo_path()
+    if bulk_blocks is not None:
+        return res[0, :L].cpu().numpy(), h[0].cpu().numpy(), int(aec.bulk.delays()[0].item())
     return res[0, :L].cpu().numpy(), h[0].cpu().numpy()
 
 
@@ -180,6 +190,9 @@ def build_parser():
     ap.add_argument('--out', required=True, help='the residual (mic minus the estimated echo), PCM_16')
     ap.add_argument('--partitions', type=int, default=8, help='256-sample blocks of echo tail the filter covers, 1 .. 32')
     ap.add_argument('--echo-path', default=None, metavar='NPY', help='write the final impulse-response estimate (float64 [partitions * 256])')
+    ap.add_argument('--bulk-blocks', type=int, default=None, metavar='N',
+                    help='search N 256-sample blocks (2 .. 64) for a bulk delay and cancel against --played delayed by the whole hops found '
+                         '(default: no search)')
     ap.add_argument('--mu', type=float, default=0.5)
     ap.add_argument('--gamma', type=float, default=4.0)
     ap.add_argument('--delta', type=float, default=1e-2)
@@ -202,11 +215,16 @@ def main(argv=None):
         sig.append(wav)
     if len(sig[0]) != len(sig[1]) or len(sig[0]) == 0:
         ap.error('--mic and --played must have one length (got %d and %d samples)' % (len(sig[0]), len(sig[1])))
-    res, h = cancel_file(sig[0], sig[1], partitions=a.partitions, mu=a.mu, gamma=a.gamma, delta=a.delta)
+    if a.bulk_blocks is not None and not 2 <= a.bulk_blocks <= _lib.CONSTS['NELE_BULK_MAX_BLOCKS']:
+        ap.error('--bulk-blocks must be in 2 .. %d' % _lib.CONSTS['NELE_BULK_MAX_BLOCKS'])
+    res, h, *found = cancel_file(sig[0], sig[1], partitions=a.partitions, mu=a.mu, gamma=a.gamma, delta=a.delta, bulk_blocks=a.bulk_blocks)
     dataio.write_wav_pcm16(a.out, res)
     if a.echo_path:
         np.save(a.echo_path, h)
     print('%s: %d samples, %d partitions (%d ms of echo tail)' % (a.out, len(res), a.partitions, a.partitions * HOP * 1000 // dataio.fs))
+    if found:
+        print('bulk delay: %s' % ('none found in %d blocks' % a.bulk_blocks if found[0] < 0 else
+                                  '%d hops (%d ms) taken out ahead of the canceller' % (found[0], found[0] * HOP * 1000 // dataio.fs)))
     return 0
 
 

@@ -3,8 +3,11 @@
   nele_gan_amd/csrc/plan_ops.inc   one `case` per entry point whose last parameter is the stream, for the job-table executor of
                                    csrc/plan.hip (nele_plan_run);
   nele_gan_amd/_abi.py             FUNCS (name -> restype code, argtype codes: what nele_gan_amd/_lib.py binds through ctypes) and CONSTS
-                                   (the header's numeric #define NELE_* values).
-Run after changing the header; tests/test_capi_symbols.py checks that both are current.
+                                   (the header's numeric #define NELE_* values);
+and from include/nele_hip_ext.h (the entry points added after nele_hip.h's fixed set; same parser, same type map)
+  nele_gan_amd/_abi_ext.py         FUNCS and CONSTS of that header, bound by _lib.py beside _abi.py's.  None of them is a plan operation:
+                                   plan_ops.inc and the operation ids come from nele_hip.h alone.
+Run after changing a header; tests/test_capi_symbols.py and tests/test_bulk_cpu.py check that all three are current.
     python tools/gen_abi.py            # rewrite the files
     python tools/gen_abi.py --check    # exit 1 when a committed file differs
 A code is the ctypes type's name without its 'c_'.  The map is fixed: a scalar type outside it stops the tool (never a default)."""
@@ -19,8 +22,8 @@ SCALARS = {'int': 'int', 'unsigned': 'uint', 'long long': 'longlong', 'unsigned 
            'double': 'double'}
 
 
-def _header():
-    return open(os.path.join(ROOT, 'include', 'nele_hip.h')).read()
+def _header(name='nele_hip.h'):
+    return open(os.path.join(ROOT, 'include', name)).read()
 
 
 def _strip_comments(src):
@@ -116,22 +119,25 @@ def emit_plan_ops():
     return '\n'.join(lines) + '\n'
 
 
-def emit_abi():
-    lines = ['"""GENERATED by tools/gen_abi.py from include/nele_hip.h - do not edit.',
+def emit_abi(header='nele_hip.h'):
+    src = None if header == 'nele_hip.h' else _header(header)
+    lines = ['"""GENERATED by tools/gen_abi.py from include/%s - do not edit.' % header,
              'FUNCS: entry point -> (restype, argtypes), each the name of a ctypes type without its \'c_\'; CONSTS: the header\'s #define NELE_*."""',
              'CONSTS = {']
-    lines += ['    %r: %r,' % kv for kv in sorted(consts().items())]
+    lines += ['    %r: %r,' % kv for kv in sorted(consts(src).items())]
     lines += ['}', 'FUNCS = {']
-    lines += ['    %r: %r,' % kv for kv in sorted(funcs().items())]
+    lines += ['    %r: %r,' % kv for kv in sorted(funcs(src).items())]
     lines.append('}')
     return '\n'.join(lines) + '\n'
 
 
 if __name__ == '__main__':
     outputs = ((os.path.join(ROOT, 'nele_gan_amd', 'csrc', 'plan_ops.inc'), emit_plan_ops()),
-               (os.path.join(ROOT, 'nele_gan_amd', '_abi.py'), emit_abi()))
+               (os.path.join(ROOT, 'nele_gan_amd', '_abi.py'), emit_abi()),
+               (os.path.join(ROOT, 'nele_gan_amd', '_abi_ext.py'), emit_abi('nele_hip_ext.h')))
     if '--check' in sys.argv:
         sys.exit(0 if all(os.path.exists(path) and open(path).read() == text for path, text in outputs) else 1)
     for path, text in outputs:
         open(path, 'w').write(text)
-    print('wrote %s (%d operations) and %s (%d entry points)' % (outputs[0][0], outputs[0][1].count('PLAN_OP('), outputs[1][0], len(funcs())))
+    print('wrote %s (%d operations), %s (%d entry points) and %s (%d entry points)'
+          % (outputs[0][0], outputs[0][1].count('PLAN_OP('), outputs[1][0], len(funcs()), outputs[2][0], len(funcs(_header('nele_hip_ext.h')))))
