@@ -23,6 +23,8 @@ int nele_set_error(int code, const char* fmt, ...);
 __attribute__((visibility("hidden"))) int nele_eigh_sym_batched_ex(double* A, int n, int B, double* lam, double* U, void* workspace,
                                                                    long long workspace_bytes, void* stream, int cluster_batch,
                                                                    double rel_cut, int* kept_first);
+struct WsField;                                                                                  // ws_arena.h
+__attribute__((visibility("hidden"))) WsField nele_eigh_flags_field(int B, int n);               // where the flags lie inside a workspace
 __attribute__((visibility("hidden"))) const int* nele_eigh_flags(void* workspace, int B, int n);
 __attribute__((visibility("hidden"))) const int* nele_eigh_kfirst(void* workspace, int B, int n);
 extern "C" long long nele_eigh_workspace_bytes(int B, int n);
@@ -78,6 +80,12 @@ void nele_prof_mark(hipStream_t s);
         launch;                                             \
         if (prof_) nele_prof_mark(stream);                  \
     } while (0)
+
+// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the vector-memory queue (the fences of a workgroup-scope
+// barrier on this target: s_waitcnt vmcnt(0)): every load issued ahead of it - the next tile's prefetch - and every outstanding global
+// store waits right there.  Use where the threads exchange data through LDS alone; global data that changes hands between threads
+// still needs __syncthreads().
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // ---- wave64 reductions (fixed-order butterflies: deterministic) ----
 __device__ __forceinline__ float wave_sum(float v) {

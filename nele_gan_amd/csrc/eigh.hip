@@ -19,6 +19,7 @@
 // utterance's covariance, by its eigenvalue tolerance.  A tridiagonal matrix whose largest entry lies outside [2^-20, 2^20] is scaled by a
 // power of two before the bisection (eigh_prescale_kernel).
 #include "common.h"
+#include "ws_arena.h"
 #include <cstdlib>
 
 #define EG_MAXN 512
@@ -1395,10 +1396,9 @@ __global__ __launch_bounds__(512) void eigh_tridiag_cluster2_kernel(double* __re
 #define EM_RI 14
 #define EM_NC 7
 #define EM_M (16 * EM_RI)
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the wave's outstanding GLOBAL stores (vmcnt(0)); in the
+// Barriers: lds_barrier() (common.h).  __syncthreads() would also drain the wave's outstanding GLOBAL stores (vmcnt(0)); in the
 // step loop below those are the reflector row and d / e / tau, which nothing in the kernel reads back - waiting for their
 // acknowledgement at every barrier is a store round trip per step.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 // Up to EX_E = 32 more rows / columns: the trailing block's FIRST E = m - 224 rows (the ones eliminated first) sit in an LDS
 // strip S[E][256] (full rows: the E x E corner is stored twice, the off-diagonal block once), the other 224 x 224 in registers as above.
 // While the strip is alive (the first E steps) a step also updates it in place - pass A: thread per column, column sums; pass B: thread
@@ -2557,24 +2557,20 @@ __global__ __launch_bounds__(64) void eigh_cut_kernel(int n, EighWs ws, const do
 }
 
 // ------------------------------------------------------------------------------------------ C ABI
-static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-static size_t eigh_layout(int B, int n, EighWs* w, char* base) {
-    size_t o = 0;
-#define TAKE(field, type, count) do { if (w) w->field = (type*)(base + o); o += al256(sizeof(type) * (size_t)(count)); } while (0)
-    TAKE(d, double, (size_t)B * n);
-    TAKE(e, double, (size_t)B * n);
-    TAKE(tau, double, (size_t)B * n);
-    TAKE(lamp, double, (size_t)B * n);
-    TAKE(zt, double, (size_t)B * n * EG_MAXN);
-    TAKE(lu, double, (size_t)B * 6 * (n + 2) * EG_MAXN);
-    TAKE(pin, int, (size_t)B * n * EG_MAXN);
-    TAKE(xch, uint4, (size_t)B * EG_XCH * EG_MAXN);
-    TAKE(scl, double, (size_t)B);
-    TAKE(flag, int, (size_t)B + 64);
-    TAKE(kfirst, int, (size_t)B);
-#undef TAKE
-    return o;
+static WsArena eigh_layout(int B, int n, EighWs& w, void* base) {
+    WsArena a(base);
+    a.take(w.d, (size_t)B * n);
+    a.take(w.e, (size_t)B * n);
+    a.take(w.tau, (size_t)B * n);
+    a.take(w.lamp, (size_t)B * n);
+    a.take(w.zt, (size_t)B * n * EG_MAXN);
+    a.take(w.lu, (size_t)B * 6 * (n + 2) * EG_MAXN);
+    a.take(w.pin, (size_t)B * n * EG_MAXN);
+    a.take(w.xch, (size_t)B * EG_XCH * EG_MAXN);
+    a.take(w.scl, (size_t)B);
+    a.take(w.flag, (size_t)B + 64);
+    a.take(w.kfirst, (size_t)B);
+    return a;
 }
 
 #ifdef ECS_PROF
@@ -2583,14 +2579,14 @@ extern "C" int nele_ecs_prof_read(unsigned long long* out8) {
     return hipMemcpyFromSymbol(out8, HIP_SYMBOL(ecs_prof), sizeof(unsigned long long) * 8) != hipSuccess;
 }
 #endif
-extern "C" long long nele_eigh_workspace_bytes(int B, int n) { return (long long)eigh_layout(B, n, nullptr, nullptr); }
+extern "C" long long nele_eigh_workspace_bytes(int B, int n) { EighWs w; return (long long)eigh_layout(B, n, w, nullptr).off; }
 
 // Matrices of the LAST nele_eigh_sym_batched call on this workspace that the cluster tridiagonalisation gave up on and the single-workgroup
 // repair kernel redid (synchronises the device; 0 on a GPU the launch fits on).  -1 on error.
 extern "C" int nele_eigh_repaired(void* workspace, int B, int n) {
     if (!workspace || B <= 0 || n < 2) return -1;
     EighWs ws;
-    eigh_layout(B, n, &ws, (char*)workspace);
+    eigh_layout(B, n, ws, workspace);
     int v = -1;
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&v, ws.flag + B, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return v;
@@ -2598,17 +2594,15 @@ extern "C" int nele_eigh_repaired(void* workspace, int B, int n) {
 
 // Device pointer to the per-matrix give-up flags of a workspace ([B] ints, non-zero = the matrix took the repair path in the last call;
 // [B] = how many).  Internal (SIIB folds it into its status word so that a training loop can count repairs without a synchronisation).
+WsField nele_eigh_flags_field(int B, int n) { EighWs w; return eigh_layout(B, n, w, nullptr).at(w.flag); }
 const int* nele_eigh_flags(void* workspace, int B, int n) {
-    EighWs ws;
-    eigh_layout(B, n, &ws, (char*)workspace);
-    return ws.flag;
+    return reinterpret_cast<const int*>(static_cast<char*>(workspace) + nele_eigh_flags_field(B, n).off);
 }
 
 // Device pointer to kfirst [B] of a workspace: the first eigenvector the last call on it computed.  Internal (SIIB's diagnostic read-back).
 const int* nele_eigh_kfirst(void* workspace, int B, int n) {
-    EighWs ws;
-    eigh_layout(B, n, &ws, (char*)workspace);
-    return ws.kfirst;
+    EighWs w;
+    return reinterpret_cast<const int*>(static_cast<char*>(workspace) + eigh_layout(B, n, w, nullptr).at(w.kfirst).off);
 }
 
 // A [B][n][n] symmetric (destroyed: holds the Householder reflectors on exit) -> lam [B][n] ascending,
@@ -2636,7 +2630,7 @@ int nele_eigh_sym_batched_ex(double* A, int n, int B, double* lam, double* U, vo
     if (n > EG_MAXN) return nele_set_error(NELE_ERR_UNSUPPORTED, "nele_eigh_sym_batched: n=%d > %d", n, EG_MAXN);
     if (workspace_bytes < nele_eigh_workspace_bytes(B, n)) return nele_set_error(NELE_ERR_WORKSPACE, "nele_eigh_sym_batched: workspace too small");
     EighWs ws;
-    eigh_layout(B, n, &ws, (char*)workspace);
+    eigh_layout(B, n, ws, workspace);
     hipStream_t s = as_stream(stream);
     // cluster tridiagonalisation when at least 8 matrices' worth of workgroups can be co-resident, else one workgroup per matrix
     static int cluster_cap = -1;                           // matrices per cluster launch (multiple of 8), 0 = unavailable

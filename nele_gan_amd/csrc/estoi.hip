@@ -12,6 +12,7 @@
 //   k5 fixed-order sum over segments, logistic map (intel.py:136-140)
 #include "common.h"
 #include "fft512.h"
+#include "ws_arena.h"
 
 #define ES_NFRAME 256
 #define ES_HOP 128
@@ -433,8 +434,6 @@ __global__ void estoi_final_kernel(EstoiWs ws, float* __restrict__ raw, float* _
 }
 
 // ------------------------------------------------------------------------------------------ C ABI
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 static void estoi_dims(int L, int* n10, int* F) {
     const long long n = (long long)L * 5;
     *n10 = (int)(n / 8 + (n % 8 ? 1 : 0));
@@ -442,26 +441,23 @@ static void estoi_dims(int L, int* n10, int* F) {
 }
 
 // The one place that carves a workspace: the filter with its step table, then the six stage buffers in the order of EstoiWs (each aligned
-// to 256 bytes).  w == nullptr: only the size.  *h: the filter's place.
-static size_t estoi_layout(int B, int L, EstoiWs* w, double** h, char* base) {
+// to 256 bytes).  base == nullptr: only the sizes.  h: the filter's place.
+static WsArena estoi_layout(int B, int L, EstoiWs& w, double*& h, void* base) {
     int n10, F;
     estoi_dims(L, &n10, &F);
-    size_t o = 0;
-    if (h) *h = (double*)base;
-    o += align256(sizeof(double) * (ES_HPAD + ES_HTAB));                                   // filter + the five-output step table
-#define TAKE(field, type, count) do { if (w) w->field = (type*)(base + o); o += align256(sizeof(type) * (size_t)(count)); } while (0)
-    TAKE(xr, double, (size_t)B * 2 * n10);
-    TAKE(en, double, (size_t)B * F);
-    TAKE(keep, int, (size_t)B * F);
-    TAKE(nkept, int, (size_t)B);
-    TAKE(tob, double, (size_t)B * 2 * ES_NB * F);
-    TAKE(dseg, double, (size_t)B * F);
-#undef TAKE
-    if (w) { w->n10 = n10; w->F = F; w->L = L; w->lens = nullptr; }
-    return o;
+    WsArena a(base);
+    a.take(h, ES_HPAD + ES_HTAB);                                                           // filter + the five-output step table
+    a.take(w.xr, (size_t)B * 2 * n10);
+    a.take(w.en, (size_t)B * F);
+    a.take(w.keep, (size_t)B * F);
+    a.take(w.nkept, (size_t)B);
+    a.take(w.tob, (size_t)B * 2 * ES_NB * F);
+    a.take(w.dseg, (size_t)B * F);
+    w.n10 = n10; w.F = F; w.L = L; w.lens = nullptr;
+    return a;
 }
 
-extern "C" long long nele_metric_estoi_workspace_bytes(int B, int L) { return (long long)estoi_layout(B, L, nullptr, nullptr, nullptr); }
+extern "C" long long nele_metric_estoi_workspace_bytes(int B, int L) { EstoiWs w; double* h; return (long long)estoi_layout(B, L, w, h, nullptr).off; }
 
 // What a call leaves in its workspace, stage by stage, as byte ranges: out[3 k .. 3 k + 2] = {offset, stride, bytes}, utterance b's part =
 // the first `bytes` bytes at offset + b * stride (every section is per utterance).  Strides are those of the padded length L; a shorter
@@ -469,21 +465,12 @@ extern "C" long long nele_metric_estoi_workspace_bytes(int B, int L) { return (l
 // (10 kHz x then y), en [F] float64 (dB), keep [F] int (original frame of kept frame k, k < nkept), nkept int, tob [2][15][F] float64
 // (x then y, third-octave magnitudes of kept frame k), dseg [F] float64 (segment m = kept frames m .. m + 29, m <= nkept - 30).
 extern "C" int nele_metric_estoi_sections(int B, int L, long long* out, int max_sections) {
-    NELE_CHECK_ARG(B > 0 && L > 0 && out && max_sections >= 6, "nele_metric_estoi_sections: bad arguments (6 sections)");
+    NELE_CHECK_ARG(B > 0 && L > 0 && out, "nele_metric_estoi_sections: bad arguments");
     EstoiWs w;
-    char* base = reinterpret_cast<char*>((uintptr_t)1 << 20);
-    estoi_layout(B, L, &w, nullptr, base);
-    int k = 0;
-    auto put = [&](const void* p, long long bytes) {
-        out[3 * k] = (long long)(reinterpret_cast<const char*>(p) - base); out[3 * k + 1] = bytes; out[3 * k + 2] = bytes; ++k;
-    };
-    put(w.xr, sizeof(double) * 2 * (size_t)w.n10);
-    put(w.en, sizeof(double) * (size_t)w.F);
-    put(w.keep, sizeof(int) * (size_t)w.F);
-    put(w.nkept, sizeof(int));
-    put(w.tob, sizeof(double) * 2 * ES_NB * (size_t)w.F);
-    put(w.dseg, sizeof(double) * (size_t)w.F);
-    return k;
+    double* h;
+    const WsArena a = estoi_layout(B, L, w, h, nullptr);
+    return ws_sections("nele_metric_estoi_sections", a, B, out, max_sections,
+                       [&](WsSections& s) { s.rows(w.xr, w.en, w.keep, w.nkept, w.tob, w.dseg); });
 }
 
 extern "C" int nele_metric_estoi_var(const float* x, const float* y, const int* lengths, int B, int L, void* workspace, long long workspace_bytes,
@@ -496,7 +483,7 @@ extern "C" int nele_metric_estoi_var(const float* x, const float* y, const int* 
         return nele_set_error(NELE_ERR_WORKSPACE, "nele_metric_estoi: workspace too small");
     double* h;
     EstoiWs ws;
-    estoi_layout(B, L, &ws, &h, (char*)workspace);
+    estoi_layout(B, L, ws, h, workspace);
     ws.lens = lengths;
     hipStream_t s = as_stream(stream);
     hipLaunchKernelGGL(estoi_filter_kernel, dim3(1), dim3(1024), 0, s, h);

@@ -9,6 +9,7 @@
 // This file is compiled with -ffp-contract=off: the float32/float64 op sequence below mirrors numpy's.
 #include "common.h"
 #include "fft512.h"
+#include "ws_arena.h"
 #include "featmath.h"
 #include "imcra.h"
 
@@ -732,7 +733,7 @@ extern "C" int nele_imcra_band_var(const void* spec, const int* frames, int B, i
 }
 extern "C" long long nele_imcra_workspace_bytes(int B, int T) {
     if (B <= 0 || T <= 0) return -1;
-    return ((long long)B * T * NELE_NBINS * 5 + 255) / 256 * 256;             // |Y|^2 (float32) + the speech indicator (one byte)
+    return (long long)ws_round256((size_t)B * T * NELE_NBINS * 5);            // |Y|^2 (float32) + the speech indicator (one byte)
 }
 // The same result as nele_imcra_band_var(spec, frames, .., psd, band) - bit for bit - without a workgroup-wide recursion: imcra_pow_kernel,
 // imcra_ind_kernel, imcra_track_kernel (see there), |Y|^2 and the indicator in a caller-provided workspace of nele_imcra_workspace_bytes(B, T).

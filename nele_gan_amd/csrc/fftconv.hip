@@ -11,13 +11,13 @@
 // "Rooms").  The multiply-accumulate kernel reads each of them once per 8 output blocks.
 #include "common.h"
 #include "fft512.h"
+#include "ws_arena.h"
 
 #define FC_BLK 256                     // samples per block = slots per spectrum
 #define FC_TILE 8                      // output blocks per workgroup of the multiply-accumulate kernel (4 waves x 2 blocks per inverse)
 #define FC_SPEC_BYTES ((long long)FC_BLK * (long long)sizeof(double2))
 #define FC_HDR_BYTES 256                // bank: int R, int Pmax | at 256: double2 H[R][Pmax][256] | behind them: int npart[R]
 
-static inline long long fc_align256(long long v) { return (v + 255) / 256 * 256; }
 __host__ __device__ static inline const int* fc_bank_npart(const void* bank, int R, int Pmax) {
     return (const int*)((const char*)bank + FC_HDR_BYTES + (size_t)R * Pmax * FC_BLK * sizeof(double2));
 }
@@ -234,7 +234,7 @@ extern "C" long long nele_rir_bank_bytes(int R, int Lhmax) {
         nele_set_error(NELE_ERR_INVALID_ARG, "nele_rir_bank_bytes: R=%d and Lhmax=%d must be positive", R, Lhmax);
         return -1;
     }
-    return FC_HDR_BYTES + (long long)R * fc_blocks(Lhmax) * FC_SPEC_BYTES + fc_align256((long long)R * (long long)sizeof(int));
+    return FC_HDR_BYTES + (long long)R * fc_blocks(Lhmax) * FC_SPEC_BYTES + (long long)ws_round256((size_t)R * sizeof(int));
 }
 
 extern "C" int nele_rir_bank_prepare(const double* rirs, const int* taps, int R, int Lhmax, void* bank, void* stream) {

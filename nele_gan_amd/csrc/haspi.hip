@@ -22,6 +22,7 @@
 //       normalised cross-correlation of reference and processed sequences
 //   h12 average over bases 2-6, weighted sum, logistic map
 #include "common.h"
+#include "ws_arena.h"
 #include <type_traits>
 #include <cstdlib>
 
@@ -1613,10 +1614,7 @@ __global__ void haspi_cepmean_kernel(HaspiWs ws, int sig0) {
 // Frames walk through LDS in tiles of 256 frames x 16 channels (two halves per tile): in the group-space layout of lp a frame's channels
 // sit in up to ~40 different rows, and a thread that walked "its" frame through global memory alone touched a new cache line on nearly
 // every channel (1.1 ms per call at B = 256 against 0.84 in frame-space rows; staged: the 16 lanes of a frame read neighbouring rows).
-// Barrier that orders LDS traffic only.  __syncthreads() also drains the vector-memory queue (the fences of a workgroup-scope barrier on
-// this target: s_waitcnt vmcnt(0)), which makes every load that was issued ahead of it - the next tile's prefetch - wait right there.
-// Use where the threads exchange data through LDS alone; global data that changes hands between threads still needs __syncthreads().
-__device__ __forceinline__ void hp_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// Barriers: lds_barrier() (common.h), so that the next tile's prefetch does not wait at them.
 __global__ __launch_bounds__(256) void haspi_cep_kernel(HaspiWs ws, const double* __restrict__ dither, double thr_nerve, int gate, int sig0,
                                                         int nsig) {
     __shared__ double cepm[HP_NCH][HP_NBASIS];
@@ -1649,10 +1647,10 @@ __global__ __launch_bounds__(256) void haspi_cep_kernel(HaspiWs ws, const double
         for (int j = 0; j < 16; ++j) pf[j] = (i0 + fth + 16 * j < nsub) ? hp_lp_at(lpb, i0 + fth + 16 * j, c, d) : 0.0;
     };
     auto put = [&]() {                                          // registers -> tile (LDS barriers on both sides)
-        hp_lds_barrier();
+        lds_barrier();
 #pragma unroll
         for (int j = 0; j < 16; ++j) tile[fth + 16 * j][cth] = pf[j];
-        hp_lds_barrier();
+        lds_barrier();
     };
     const int ntile2 = 2 * ((nsub + 255) / 256);
     int na;
@@ -1669,17 +1667,17 @@ __global__ __launch_bounds__(256) void haspi_cep_kernel(HaspiWs ws, const double
                 const int k = (i < nsub && 20.0 * log10(sm / (double)HP_NCH) > 2.5) ? 1 : 0;
                 sm = 0.0;
                 scan[tid] = k;
-                hp_lds_barrier();
+                lds_barrier();
                 for (int o = 1; o < 256; o <<= 1) {
                     const int v = (tid >= o) ? scan[tid - o] : 0;
-                    hp_lds_barrier();
+                    lds_barrier();
                     scan[tid] += v;
-                    hp_lds_barrier();
+                    lds_barrier();
                 }
                 if (i < nsub) act[i] = k ? base + scan[tid] - 1 : -1;      // read back by the same thread only (the cepstrum loop below)
-                hp_lds_barrier();
+                lds_barrier();
                 if (tid == 255) base += scan[255];
-                hp_lds_barrier();
+                lds_barrier();
             }
         }
         na = base;
@@ -2059,53 +2057,50 @@ __global__ void haspi_final_kernel(HaspiWs ws, float* __restrict__ raw, float* _
 }
 
 // ------------------------------------------------------------------------------------------ C ABI
-static size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-
-static size_t haspi_layout(int B, int L, int fs_in, HaspiWs* w, char* base) {
+// Carves the workspace and fills `w`'s geometry of the padded length: the one place that computes it (quality_layout goes on from here).
+static WsArena haspi_layout(int B, int L, int fs_in, HaspiWs& w, void* base) {
     const int n24 = hp_n24_of(L, fs_in);
     const int nsub = (n24 + HP_SPACE - 1) / HP_SPACE;
     const int n24p = (n24 + 31) / 32 * 32;
-    size_t o = 0;
-#define TAKE(field, type, count) do { if (w) w->field = (type*)(base + o); o += al(sizeof(type) * (size_t)(count)); } while (0)
-    TAKE(win, double, HP_NWIN_AL + RS3_TAB);           // resampler half window + the 16 kHz tap table
-    TAKE(r24, float, (size_t)B * 2 * n24p);
-    TAKE(mid, double, (size_t)B * 2 * n24p);
-    TAKE(ctl, hp_env_t, (size_t)B * 2 * n24p * HP_NCH);
-    TAKE(env, hp_env_t, (size_t)B * 2 * n24p * HP_NCH);
-    TAKE(bw, double, (size_t)B * 2 * HP_NCH);
-    TAKE(loss, double, 2 * 5 * HP_NCH);
+    WsArena a(base);
+    a.take(w.win, HP_NWIN_AL + RS3_TAB);                 // resampler half window + the 16 kHz tap table
+    a.take(w.r24, (size_t)B * 2 * n24p);
+    a.take(w.mid, (size_t)B * 2 * n24p);
+    a.take(w.ctl, (size_t)B * 2 * n24p * HP_NCH);
+    a.take(w.env, (size_t)B * 2 * n24p * HP_NCH);
+    a.take(w.bw, (size_t)B * 2 * HP_NCH);
+    a.take(w.loss, 2 * 5 * HP_NCH);
     int lc = GS_LC;
     while ((n24p + lc - 1) / lc > GS_MAXC) lc += GS_LC;
     const int nchunk = (n24p + lc - 1) / lc, ncg = (n24p + (lc < GL_N ? lc : GL_N) - 1) / (lc < GL_N ? lc : GL_N);
-    TAKE(ssp, double, (size_t)B * 2 * nchunk * HP_NCH);
-    TAKE(est, double, (size_t)B * 2 * nchunk * 256);
-    TAKE(pmat, double, (size_t)(1 + B * 2) * HP_NCH * 16);
-    TAKE(ihe, double, (size_t)B * 2 * ncg * 64);
-    TAKE(pihc, double, 4);
-    TAKE(rsp, double, (size_t)B * 2 * RS_MAXC);
-    TAKE(rinfo, float, (size_t)B * 2 * 4);
-    TAKE(benv, double, 64);
-    TAKE(bkt, double, 10 * 616);
-    TAKE(shift, int, (size_t)B * HP_NCH);
-    TAKE(lp, double, (size_t)B * 2 * (nsub + 4) * HP_NCH);
+    a.take(w.ssp, (size_t)B * 2 * nchunk * HP_NCH);
+    a.take(w.est, (size_t)B * 2 * nchunk * 256);
+    a.take(w.pmat, (size_t)(1 + B * 2) * HP_NCH * 16);
+    a.take(w.ihe, (size_t)B * 2 * ncg * 64);
+    a.take(w.pihc, 4);
+    a.take(w.rsp, (size_t)B * 2 * RS_MAXC);
+    a.take(w.rinfo, (size_t)B * 2 * 4);
+    a.take(w.benv, 64);
+    a.take(w.bkt, 10 * 616);
+    a.take(w.shift, (size_t)B * HP_NCH);
+    a.take(w.lp, (size_t)B * 2 * (nsub + 4) * HP_NCH);
     const int ngb = (nsub + CP_F - 1) / CP_F;
-    TAKE(act, int, (size_t)B * nsub);
-    TAKE(grank, int, (size_t)B * nsub);
-    TAKE(gcnt, int, (size_t)B * ngb);
-    TAKE(cpsum, double, (size_t)B * 2 * ngb * HP_NBASIS);
-    TAKE(cmean, double, (size_t)B * 2 * HP_NBASIS);
-    TAKE(info, int, (size_t)B * 2);
-    TAKE(cep, double, (size_t)B * 2 * HP_NBASIS * nsub);
-    TAKE(cm, double, (size_t)B * HP_NBASIS * HP_NMOD);
-    TAKE(xf, double, (size_t)B * 64 * nsub);
-    TAKE(cpart, double, (size_t)B * MS_MAXC * 64 * 5);
-#undef TAKE
-    if (w) { w->n24 = n24; w->nsub = nsub; w->n24p = n24p; w->fs_in = fs_in; w->lens = nullptr; w->nchunk = nchunk; w->lc = lc; w->ngb = ngb;
-             w->cphi = nullptr; w->sse = nullptr; w->lcg = GL_N; w->fmul = 1; w->nlp = nsub + 4; w->lp_raw = 0; }
-    return o;
+    a.take(w.act, (size_t)B * nsub);
+    a.take(w.grank, (size_t)B * nsub);
+    a.take(w.gcnt, (size_t)B * ngb);
+    a.take(w.cpsum, (size_t)B * 2 * ngb * HP_NBASIS);
+    a.take(w.cmean, (size_t)B * 2 * HP_NBASIS);
+    a.take(w.info, (size_t)B * 2);
+    a.take(w.cep, (size_t)B * 2 * HP_NBASIS * nsub);
+    a.take(w.cm, (size_t)B * HP_NBASIS * HP_NMOD);
+    a.take(w.xf, (size_t)B * 64 * nsub);
+    a.take(w.cpart, (size_t)B * MS_MAXC * 64 * 5);
+    w.n24 = n24; w.nsub = nsub; w.n24p = n24p; w.fs_in = fs_in; w.lens = nullptr; w.nchunk = nchunk; w.lc = lc; w.ngb = ngb;
+    w.cphi = nullptr; w.sse = nullptr; w.lcg = GL_N; w.fmul = 1; w.nlp = nsub + 4; w.lp_raw = 0;
+    return a;
 }
 
-extern "C" long long nele_metric_haspi_workspace_bytes(int B, int L, int fs_in) { return (long long)haspi_layout(B, L, fs_in, nullptr, nullptr); }
+extern "C" long long nele_metric_haspi_workspace_bytes(int B, int L, int fs_in) { HaspiWs w; return (long long)haspi_layout(B, L, fs_in, w, nullptr).off; }
 
 // What phase 3 (the reference-signal half: ear model, envelope filter, silence gate, group-delay shifts, cepstra, modulation filters of
 // the CLEAN signal) leaves in a workspace for phase 4, as byte ranges {offset, stride, bytes} exactly like
@@ -2114,33 +2109,20 @@ extern "C" long long nele_metric_haspi_workspace_bytes(int B, int L, int fs_in) 
 // the reference's dither rows: a loop that scores the same clean files every epoch may keep it and skip phase 3 (same L, fs_in, HL,
 // dither; any row order, any B).  Returns the number of sections (<= max_sections) or a negative status.
 extern "C" int nele_metric_haspi_clean_sections(int B, int L, int fs_in, long long* out, int max_sections) {
-    NELE_CHECK_ARG(B > 0 && out && max_sections >= 16, "nele_metric_haspi_clean_sections: bad arguments (16 sections)");
+    NELE_CHECK_ARG(B > 0 && out, "nele_metric_haspi_clean_sections: bad arguments");
     NELE_CHECK_ARG(fs_in >= 1000 && fs_in <= 24000 && L >= 2400, "nele_metric_haspi_clean_sections: bad signal geometry");
     HaspiWs w;
-    char* base = reinterpret_cast<char*>((uintptr_t)1 << 20);
-    haspi_layout(B, L, fs_in, &w, base);
-    int k = 0;
-    auto put = [&](const void* p, long long stride, long long bytes) {
-        out[3 * k] = (long long)(reinterpret_cast<const char*>(p) - base); out[3 * k + 1] = stride; out[3 * k + 2] = bytes; ++k;
-    };
-    const size_t ns = (size_t)w.nsub;
-    put(w.win, 0, sizeof(double) * (HP_NWIN_AL + RS3_TAB));
-    put(w.pmat, 0, sizeof(double) * HP_NCH * 16);                                   // entry 0: the control bank (per channel only)
-    put(w.pihc, 0, sizeof(double) * 4);
-    put(w.benv, 0, sizeof(double) * 64);
-    put(w.bkt, 0, sizeof(double) * 10 * 616);
-    put(w.bw, sizeof(double) * 2 * HP_NCH, sizeof(double) * 2 * HP_NCH);
-    put(w.rinfo, sizeof(float) * 2 * 4, sizeof(float) * 2 * 4);
-    put(w.shift, sizeof(int) * HP_NCH, sizeof(int) * HP_NCH);
-    put(w.act, sizeof(int) * ns, sizeof(int) * ns);
-    put(w.grank, sizeof(int) * ns, sizeof(int) * ns);
-    put(w.gcnt, sizeof(int) * (size_t)w.ngb, sizeof(int) * (size_t)w.ngb);
-    put(w.cpsum, sizeof(double) * 2 * (size_t)w.ngb * HP_NBASIS, sizeof(double) * (size_t)w.ngb * HP_NBASIS);   // clean half
-    put(w.cmean, sizeof(double) * 2 * HP_NBASIS, sizeof(double) * 2 * HP_NBASIS);
-    put(w.info, sizeof(int) * 2, sizeof(int) * 2);
-    put(w.cep, sizeof(double) * 2 * HP_NBASIS * ns, sizeof(double) * HP_NBASIS * ns);                             // clean half
-    put(w.xf, sizeof(double) * 64 * ns, sizeof(double) * 64 * ns);
-    return k;
+    const WsArena a = haspi_layout(B, L, fs_in, w, nullptr);
+    return ws_sections("nele_metric_haspi_clean_sections", a, B, out, max_sections, [&](WsSections& s) {
+        s.shared(w.win);
+        s.shared_entry0(w.pmat, 1 + 2 * (size_t)B);                               // entry 0: the control bank (per channel only)
+        s.shared(w.pihc, w.benv, w.bkt);
+        s.rows(w.bw, w.rinfo, w.shift, w.act, w.grank, w.gcnt);
+        s.half_rows(w.cpsum);                                                     // clean half
+        s.rows(w.cmean, w.info);
+        s.half_rows(w.cep);                                                       // clean half
+        s.rows(w.xf);
+    });
 }
 
 // Diagnostic (tests): the per-utterance buffers a DEFAULT phase-0 call (no NELE_AB switch: chunk-parallel IIRs, gain pass inside the signal
@@ -2165,34 +2147,16 @@ extern "C" int nele_metric_haspi_clean_sections(int B, int L, int fs_in, long lo
 //   12 xf    double [nsub][64]      modulation-filtered clean sequences, rows < n_active, lane = (basis - 1) * 10 + band < 50
 //   13 cm    double [6][10]         |rho| per (basis, band); row 0 is never written
 //   14 loss  double [2][5][32]      stride 0: attnOHC, BWmin, lowknee, CR, attnIHC of x then y
-// Returns the number of sections (max_sections >= 15) or a negative status.  Host-only: no device work.
+// Returns the number of sections (15; max_sections must hold them) or a negative status.  Host-only: no device work.
 extern "C" int nele_metric_haspi_sections(int B, int L, int fs_in, long long* out, int max_sections) {
-    NELE_CHECK_ARG(B > 0 && out && max_sections >= 15, "nele_metric_haspi_sections: bad arguments (15 sections)");
+    NELE_CHECK_ARG(B > 0 && out, "nele_metric_haspi_sections: bad arguments");
     NELE_CHECK_ARG(fs_in >= 1000 && fs_in <= 24000 && L >= 2400, "nele_metric_haspi_sections: bad signal geometry");
     HaspiWs w;
-    char* base = reinterpret_cast<char*>((uintptr_t)1 << 20);
-    haspi_layout(B, L, fs_in, &w, base);
-    int k = 0;
-    auto put = [&](const void* p, size_t bytes, bool shared = false) {
-        out[3 * k] = (long long)(reinterpret_cast<const char*>(p) - base); out[3 * k + 1] = shared ? 0 : (long long)bytes; out[3 * k + 2] = (long long)bytes; ++k;
-    };
-    const size_t ns = (size_t)w.nsub, np = (size_t)w.n24p;
-    put(w.r24, sizeof(float) * 2 * np);
-    put(w.mid, sizeof(double) * 2 * np);
-    put(w.bw, sizeof(double) * 2 * HP_NCH);
-    put(w.shift, sizeof(int) * HP_NCH);
-    put(w.rinfo, sizeof(float) * 2 * 4);
-    put(w.env, sizeof(hp_env_t) * 2 * np * HP_NCH);
-    put(w.ctl, sizeof(hp_env_t) * 2 * np * HP_NCH);
-    put(w.lp, sizeof(double) * 2 * (size_t)w.nlp * HP_NCH);
-    put(w.act, sizeof(int) * ns);
-    put(w.info, sizeof(int) * 2);
-    put(w.cep, sizeof(double) * 2 * HP_NBASIS * ns);
-    put(w.cmean, sizeof(double) * 2 * HP_NBASIS);
-    put(w.xf, sizeof(double) * 64 * ns);
-    put(w.cm, sizeof(double) * HP_NBASIS * HP_NMOD);
-    put(w.loss, sizeof(double) * 2 * 5 * HP_NCH, true);
-    return k;
+    const WsArena a = haspi_layout(B, L, fs_in, w, nullptr);
+    return ws_sections("nele_metric_haspi_sections", a, B, out, max_sections, [&](WsSections& s) {
+        s.rows(w.r24, w.mid, w.bw, w.shift, w.rinfo, w.env, w.ctl, w.lp, w.act, w.info, w.cep, w.cmean, w.xf, w.cm);
+        s.shared(w.loss);
+    });
 }
 
 extern "C" int nele_metric_haspi_nsub(int L, int fs_in) {
@@ -2341,7 +2305,7 @@ static int haspi_var_impl(const float* x, const float* y, const int* lengths, in
     if (workspace_bytes < nele_metric_haspi_workspace_bytes(B, L, fs_in))
         return nele_set_error(NELE_ERR_WORKSPACE, "nele_metric_haspi: workspace too small");
     HaspiWs ws;
-    haspi_layout(B, L, fs_in, &ws, (char*)workspace);
+    haspi_layout(B, L, fs_in, ws, workspace);
     ws.lens = lengths;
     ws.lp_raw = haspi_lp_raw();
     hipStream_t s = as_stream(stream);

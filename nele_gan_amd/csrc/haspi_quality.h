@@ -534,31 +534,26 @@ __global__ __launch_bounds__(256) void hq_final_kernel(HaspiWs ws, QualWs q, dou
     }
 }
 
-static size_t quality_layout(int B, int L, int fs_in, HaspiWs* w, QualWs* q, char* base) {
-    size_t o = haspi_layout(B, L, fs_in, w, base);
-    const int n24 = hp_n24_of(L, fs_in);
-    const int n24p = (n24 + 31) / 32 * 32;
-    const int nseg = 1 + n24 / HQ_NWIN + (n24 - HQ_NHALF) / HQ_NWIN;
-    int lc = GS_LC;
-    while ((n24p + lc - 1) / lc > GS_MAXC) lc += GS_LC;
-    const int nchunk = (n24p + lc - 1) / lc;
-#define TAKEQ(ptr, type, count) do { if (w) ptr = (type*)(base + o); o += al(sizeof(type) * (size_t)(count)); } while (0)
-    TAKEQ(w->cphi, float, (size_t)B * 2 * n24p * HP_NCH);
-    TAKEQ(w->sse, double, (size_t)B * 2 * nchunk * HP_NCH);
-    TAKEQ(q->sm, double, (size_t)B * 2 * nseg * HP_NCH);
-    TAKEQ(q->cov, double, (size_t)B * nseg * HP_NCH);
-    TAKEQ(q->msx, double, (size_t)B * nseg * HP_NCH);
-    TAKEQ(q->msy, double, (size_t)B * nseg * HP_NCH);
-    TAKEQ(q->corr, double, 128);
-    TAKEQ(q->segl, double, (size_t)B * 2 * nseg);
-    TAKEQ(q->qinfo, int, (size_t)B * 4);
-#undef TAKEQ
-    if (q) q->nseg = nseg;
-    return o;
+// HaspiWs's carve with the quality part behind it; the geometry is the one haspi_layout left in `w`.
+static WsArena quality_layout(int B, int L, int fs_in, HaspiWs& w, QualWs& q, void* base) {
+    WsArena a = haspi_layout(B, L, fs_in, w, base);
+    const int nseg = 1 + w.n24 / HQ_NWIN + (w.n24 - HQ_NHALF) / HQ_NWIN;
+    a.take(w.cphi, (size_t)B * 2 * w.n24p * HP_NCH);
+    a.take(w.sse, (size_t)B * 2 * w.nchunk * HP_NCH);
+    a.take(q.sm, (size_t)B * 2 * nseg * HP_NCH);
+    a.take(q.cov, (size_t)B * nseg * HP_NCH);
+    a.take(q.msx, (size_t)B * nseg * HP_NCH);
+    a.take(q.msy, (size_t)B * nseg * HP_NCH);
+    a.take(q.corr, 128);
+    a.take(q.segl, (size_t)B * 2 * nseg);
+    a.take(q.qinfo, (size_t)B * 4);
+    q.nseg = nseg;
+    return a;
 }
 
 extern "C" long long nele_metric_haspi_quality_workspace_bytes(int B, int L, int fs_in) {
-    return (long long)quality_layout(B, L, fs_in, nullptr, nullptr, nullptr);
+    HaspiWs w; QualWs q;
+    return (long long)quality_layout(B, L, fs_in, w, q, nullptr).off;
 }
 
 // x, y [B][L] float32 (reference, processed); lengths [B] or NULL; noise != 0: eb_BMaddnoise with the counter-based generator seeded
@@ -593,7 +588,7 @@ static int haspi_quality_impl(const float* x, const float* y, const int* lengths
         return nele_set_error(NELE_ERR_WORKSPACE, "nele_metric_haspi_quality: workspace too small");
     HaspiWs ws;
     QualWs q;
-    quality_layout(B, L, fs_in, &ws, &q, (char*)workspace);
+    quality_layout(B, L, fs_in, ws, q, workspace);
     ws.lens = lengths;
     q.seed = seed; q.noise = noise ? 1 : 0; q.ids = nullptr;
     hipStream_t s = as_stream(stream);
@@ -621,7 +616,7 @@ static int haspi_quality_impl(const float* x, const float* y, const int* lengths
 //   phase 0  phase 3 and phase 4 on the same workspace, as the one-shot call's launches: both signals per launch, one segment launch
 // Phase 4 may be repeated after one phase 3 (several processed versions of one reference).  The workspace is the one-shot call's.
 extern "C" long long nele_metric_hasqi_workspace_bytes(int B, int L, int fs_in) {
-    return (long long)quality_layout(B, L, fs_in, nullptr, nullptr, nullptr);
+    return nele_metric_haspi_quality_workspace_bytes(B, L, fs_in);
 }
 
 // What phase 3 leaves for phase 4, as {offset, stride, bytes} ranges (see nele_metric_haspi_clean_sections): the BM motion of x
@@ -629,30 +624,20 @@ extern "C" long long nele_metric_hasqi_workspace_bytes(int B, int L, int fs_in) 
 // bandwidths and the sum-of-squares partials of x that eb_aveSL reads, and the constant tables.  The per-sample envelope of x is not
 // part of it.  With noise 1 / 2 the noise of signal 0 is inside the kept BM motion.
 extern "C" int nele_metric_hasqi_clean_sections(int B, int L, int fs_in, long long* out, int max_sections) {
-    NELE_CHECK_ARG(B > 0 && out && max_sections >= 12, "nele_metric_hasqi_clean_sections: bad arguments (12 sections)");
+    NELE_CHECK_ARG(B > 0 && out, "nele_metric_hasqi_clean_sections: bad arguments");
     NELE_CHECK_ARG(fs_in >= 1000 && fs_in <= 24000 && L >= 2400, "nele_metric_hasqi_clean_sections: bad signal geometry");
     HaspiWs w;
     QualWs q;
-    char* base = reinterpret_cast<char*>((uintptr_t)1 << 20);
-    quality_layout(B, L, fs_in, &w, &q, base);
-    int k = 0;
-    auto put = [&](const void* p, long long stride, long long bytes) {
-        out[3 * k] = (long long)(reinterpret_cast<const char*>(p) - base); out[3 * k + 1] = stride; out[3 * k + 2] = bytes; ++k;
-    };
-    const size_t ns = (size_t)q.nseg, nc = (size_t)w.nchunk;
-    put(w.win, 0, sizeof(double) * (HP_NWIN_AL + RS3_TAB));
-    put(w.pmat, 0, sizeof(double) * HP_NCH * 16);                                   // entry 0: the control bank (per channel only)
-    put(w.pihc, 0, sizeof(double) * 4);
-    put(q.corr, 0, sizeof(double) * 128);
-    put(w.bw, sizeof(double) * 2 * HP_NCH, sizeof(double) * HP_NCH);                // reference half of each [2][..] block, here and below
-    put(w.shift, sizeof(int) * HP_NCH, sizeof(int) * HP_NCH);
-    put(w.ssp, sizeof(double) * 2 * nc * HP_NCH, sizeof(double) * nc * HP_NCH);
-    put(w.sse, sizeof(double) * 2 * nc * HP_NCH, sizeof(double) * nc * HP_NCH);
-    put(w.cphi, sizeof(float) * 2 * (size_t)w.n24p * HP_NCH, sizeof(float) * (size_t)w.n24p * HP_NCH);
-    put(q.sm, sizeof(double) * 2 * ns * HP_NCH, sizeof(double) * ns * HP_NCH);
-    put(q.msx, sizeof(double) * ns * HP_NCH, sizeof(double) * ns * HP_NCH);
-    put(q.segl, sizeof(double) * 2 * ns, sizeof(double) * 2 * ns);
-    return k;
+    const WsArena a = quality_layout(B, L, fs_in, w, q, nullptr);
+    return ws_sections("nele_metric_hasqi_clean_sections", a, B, out, max_sections, [&](WsSections& s) {
+        s.shared(w.win);
+        s.shared_entry0(w.pmat, 1 + 2 * (size_t)B);                               // entry 0: the control bank (per channel only)
+        s.shared(w.pihc, q.corr);
+        s.half_rows(w.bw);                                                        // reference half of each [2][..] block, here and below
+        s.rows(w.shift);
+        s.half_rows(w.ssp, w.sse, w.cphi, q.sm);
+        s.rows(q.msx, q.segl);
+    });
 }
 
 // x, y [B][L] float32 (reference, processed; x may be NULL in phase 4, y in phase 3); lengths [B] or NULL; hl6_host: audiogram (HOST
@@ -678,7 +663,7 @@ extern "C" int nele_metric_hasqi_var(const float* x, const float* y, const int* 
         return nele_set_error(NELE_ERR_WORKSPACE, "nele_metric_hasqi_var: workspace too small");
     HaspiWs ws;
     QualWs q;
-    quality_layout(B, L, fs_in, &ws, &q, (char*)workspace);
+    quality_layout(B, L, fs_in, ws, q, workspace);
     ws.lens = lengths;
     q.seed = seed; q.noise = noise; q.ids = utt_ids;
     hipStream_t s = as_stream(stream);

@@ -14,6 +14,7 @@
 // (nele_gen_param_layout / nele_disc_param_layout return the offsets; tests/test_model_cpu.py compares them with named_parameters()).
 #include "common.h"
 #include "conv_common.h"
+#include "ws_arena.h"
 #include "../../include/nele_hip.h"
 #include <cstring>
 #include <initializer_list>
@@ -43,8 +44,8 @@ struct Ws {
     explicit Ws(void* b) : base(reinterpret_cast<char*>(b)) {}
     Buf take(long long elems, int elsize, bool b16 = false) {
         Buf r; r.elems = elems; r.b16 = b16;
-        r.p = base ? base + off : nullptr;
-        off += ((size_t)elems * elsize + 255) & ~(size_t)255;
+        const size_t at = ws_bump(&off, (size_t)elems * elsize);
+        r.p = base ? base + at : nullptr;
         return r;
     }
     Buf f32(long long n) { return take(n, 4); }

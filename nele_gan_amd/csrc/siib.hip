@@ -14,6 +14,7 @@
 //   s8  Xp = U^T Xs, Yp = U^T Ys fused with the per-component sums of Xp^2, Yp^2, Xp Yp
 //   s9  rho, I = -1/2 log2(1 - rho_p^2 rho^2), SIIB = R/K sum I, logistic map
 #include "common.h"
+#include "ws_arena.h"
 #include <cstdlib>
 
 #define SB_WLEN 400
@@ -1292,8 +1293,6 @@ __global__ __launch_bounds__(512) void siib_final_kernel(SiibWs ws, float* __res
 #endif  // NELE_AB
 
 // ------------------------------------------------------------------------------------------ C ABI
-static size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-
 static void siib_dims(int L, int* NT, int* NA, int* NTL) {
     long long total = (long long)SB_MMAX * L;
     if (total < SB_WLEN + 1) total = SB_WLEN + 1;
@@ -1313,25 +1312,24 @@ static bool siib_lag_path() {
     return on;
 }
 
-static size_t siib_layout(int B, int L, SiibWs* w, char* base) {
+static WsArena siib_layout(int B, int L, SiibWs& w, void* base) {
     int NT, NA, NTL;
     siib_dims(L, &NT, &NA, &NTL);
-    size_t o = 0;
-#define TAKE(field, type, count) do { if (w) w->field = (type*)(base + o); o += al(sizeof(type) * (size_t)(count)); } while (0)
-    TAKE(g2, double, SB_J * SB_NBIN);
-    TAKE(tab, double, 3 * SB_WLEN);
-    TAKE(g2t, double, SB_NBIN * SB_J);
-    TAKE(rowstat, double, (size_t)B * 2 * SB_J * 2);
-    TAKE(xdb, double, (size_t)B * NT);
-    TAKE(list, int, (size_t)B * NA);
-    TAKE(info, int, (size_t)B * 4);
-    TAKE(nprim, int, (size_t)B);
-    TAKE(XL, double, (size_t)B * 2 * SB_J * NA);
-    TAKE(C, double, (size_t)B * SB_D * SB_D);
-    TAKE(lam, double, (size_t)B * SB_D);
-    TAKE(U, double, (size_t)B * SB_D * SB_D);
-    TAKE(eigws, char, (size_t)nele_eigh_workspace_bytes(B, SB_D));
-    TAKE(part, double, (size_t)B * SB_D * NTL * 3);
+    WsArena a(base);
+    a.take(w.g2, SB_J * SB_NBIN);
+    a.take(w.tab, 3 * SB_WLEN);
+    a.take(w.g2t, SB_NBIN * SB_J);
+    a.take(w.rowstat, (size_t)B * 2 * SB_J * 2);
+    a.take(w.xdb, (size_t)B * NT);
+    a.take(w.list, (size_t)B * NA);
+    a.take(w.info, (size_t)B * 4);
+    a.take(w.nprim, (size_t)B);
+    a.take(w.XL, (size_t)B * 2 * SB_J * NA);
+    a.take(w.C, (size_t)B * SB_D * SB_D);
+    a.take(w.lam, (size_t)B * SB_D);
+    a.take(w.U, (size_t)B * SB_D * SB_D);
+    a.take(w.eigws, (size_t)nele_eigh_workspace_bytes(B, SB_D));
+    a.take(w.part, (size_t)B * SB_D * NTL * 3);
     // Frame segments of the lag-product kernel: more workgroups at small batches.  NOTE (documented non-invariance): the partial sums
     // of an utterance are added in segment order, so the association of its covariance sums - and with it the last bits of its score -
     // depends on the batch-size class (B < 48 / < 128 / >= 128) it is scored in; the products and their order inside a segment do not.
@@ -1339,24 +1337,22 @@ static size_t siib_layout(int B, int L, SiibWs* w, char* base) {
     // of 256 + 20 spilled; always writing four partials costs 0.84 GB of traffic per B = 256 call.  tests/test_metrics_gpu.py compares
     // B = 1, 50 and 130 (equal at the float32 precision of the returned score).
     const int nseg = B >= 128 ? 1 : (B >= 48 ? 2 : 4);
+    w.Xs = w.px = w.lagp = w.mu = w.S2 = w.qpart = nullptr;
     if (siib_lag_path()) {
         // the lag path needs neither the stacked frames nor the kept clean projections: Xs / px shrink to nothing
-        TAKE(lagp, double, (size_t)B * 3 * SL_NSEG * SL_ND * SB_J * SB_J);
-        TAKE(mu, double, (size_t)B * 2 * SB_D);
-        TAKE(S2, double, (size_t)B * 2 * SB_D * SB_D);
-        TAKE(qpart, double, (size_t)B * SB_D * 14);
-        if (w) { w->Xs = nullptr; w->px = nullptr; }
+        a.take(w.lagp, (size_t)B * 3 * SL_NSEG * SL_ND * SB_J * SB_J);
+        a.take(w.mu, (size_t)B * 2 * SB_D);
+        a.take(w.S2, (size_t)B * 2 * SB_D * SB_D);
+        a.take(w.qpart, (size_t)B * SB_D * 14);
     } else {
-        TAKE(Xs, double, (size_t)B * 2 * SB_D * NA);
-        TAKE(px, double, (size_t)B * 7 * NTL * 16 * 256);
-        if (w) { w->lagp = nullptr; w->mu = nullptr; w->S2 = nullptr; w->qpart = nullptr; }
+        a.take(w.Xs, (size_t)B * 2 * SB_D * NA);
+        a.take(w.px, (size_t)B * 7 * NTL * 16 * 256);
     }
-#undef TAKE
-    if (w) { w->NT = NT; w->NA = NA; w->NTL = NTL; w->Bn = B; w->nseg = nseg; }
-    return o;
+    w.NT = NT; w.NA = NA; w.NTL = NTL; w.Bn = B; w.nseg = nseg;
+    return a;
 }
 
-extern "C" long long nele_metric_siib_workspace_bytes(int B, int L) { return (long long)siib_layout(B, L, nullptr, nullptr); }
+extern "C" long long nele_metric_siib_workspace_bytes(int B, int L) { SiibWs w; return (long long)siib_layout(B, L, w, nullptr).off; }
 
 // What phase 3 (the clean-signal half) leaves in a workspace for phase 4, as byte ranges of the workspace: out[3 k .. 3 k + 2] =
 // {offset, stride, bytes}.  stride > 0: a per-utterance section - utterance b's state is the first `bytes` bytes at offset + b * stride;
@@ -1367,30 +1363,18 @@ extern "C" long long nele_metric_siib_workspace_bytes(int B, int L) { return (lo
 // with the same L, copy them into the workspace INSTEAD of running phase 3 (utterances may sit at other rows b, B may differ).
 // Returns the number of sections (<= max_sections), or a negative status.
 extern "C" int nele_metric_siib_clean_sections(int B, int L, long long* out, int max_sections) {
-    NELE_CHECK_ARG(B > 0 && out && max_sections >= 13, "nele_metric_siib_clean_sections: bad arguments (13 sections)");
+    NELE_CHECK_ARG(B > 0 && out, "nele_metric_siib_clean_sections: bad arguments");
     if (!siib_lag_path()) return nele_set_error(NELE_ERR_UNSUPPORTED, "nele_metric_siib_clean_sections: lag-product path only");
     SiibWs w;
-    char* base = reinterpret_cast<char*>((uintptr_t)1 << 20);
-    siib_layout(B, L, &w, base);
-    const int* fl = nele_eigh_flags(w.eigws, B, SB_D);
-    int k = 0;
-    auto put = [&](const void* p, long long stride, long long bytes) {
-        out[3 * k] = (long long)(reinterpret_cast<const char*>(p) - base); out[3 * k + 1] = stride; out[3 * k + 2] = bytes; ++k;
-    };
-    put(w.g2, 0, sizeof(double) * SB_J * SB_NBIN);
-    put(w.tab, 0, sizeof(double) * 3 * SB_WLEN);
-    put(w.g2t, 0, sizeof(double) * SB_NBIN * SB_J);
-    put(w.rowstat, sizeof(double) * 2 * SB_J * 2, sizeof(double) * 2 * SB_J * 2);
-    put(w.xdb, sizeof(double) * (size_t)w.NT, sizeof(double) * (size_t)w.NT);
-    put(w.list, sizeof(int) * (size_t)w.NA, sizeof(int) * (size_t)w.NA);
-    put(w.info, sizeof(int) * 4, sizeof(int) * 4);
-    put(w.nprim, sizeof(int), sizeof(int));
-    put(w.XL, sizeof(double) * 2 * SB_J * (size_t)w.NA, sizeof(double) * SB_J * (size_t)w.NA);        // the clean half of [2][28][NA]
-    put(w.lam, sizeof(double) * SB_D, sizeof(double) * SB_D);
-    put(w.U, sizeof(double) * SB_D * SB_D, sizeof(double) * SB_D * SB_D);
-    put(w.mu, sizeof(double) * 2 * SB_D, sizeof(double) * SB_D);                                       // the clean half of [2][420]
-    put(fl, sizeof(int), sizeof(int));
-    return k;
+    const WsArena a = siib_layout(B, L, w, nullptr);
+    return ws_sections("nele_metric_siib_clean_sections", a, B, out, max_sections, [&](WsSections& s) {
+        s.shared(w.g2, w.tab, w.g2t);
+        s.rows(w.rowstat, w.xdb, w.list, w.info, w.nprim);
+        s.half_rows(w.XL);                                                        // the clean half of [2][28][NA]
+        s.rows(w.lam, w.U);
+        s.half_rows(w.mu);                                                        // the clean half of [2][420]
+        s.nested_elems(w.eigws, nele_eigh_flags_field(B, SB_D));                  // the eigensolver's repair flag of each utterance
+    });
 }
 
 // phase: 0 = everything, 1 = front only (VAD .. covariance), 2 = back only (eigenvectors .. score): the split lets the caller put
@@ -1408,8 +1392,7 @@ extern "C" int nele_metric_siib_var(const float* x, const float* y, const int* l
     if (workspace_bytes < nele_metric_siib_workspace_bytes(B, L))
         return nele_set_error(NELE_ERR_WORKSPACE, "nele_metric_siib: workspace too small");
     SiibWs ws;
-    const size_t used = siib_layout(B, L, &ws, (char*)workspace);
-    (void)used;
+    siib_layout(B, L, ws, workspace);
     ws.lens = lengths;
     hipStream_t s = as_stream(stream);
     int g = L, r = SB_SHIFT;
@@ -1497,7 +1480,7 @@ extern "C" int nele_metric_siib_var(const float* x, const float* y, const int* l
 extern "C" int nele_metric_siib_kept_first(int B, int L, void* workspace, int* kept_first) {
     NELE_CHECK_ARG(B > 0 && workspace && kept_first, "nele_metric_siib_kept_first: bad arguments");
     SiibWs ws;
-    siib_layout(B, L, &ws, (char*)workspace);
+    siib_layout(B, L, ws, workspace);
     if (hipDeviceSynchronize() != hipSuccess ||
         hipMemcpy(kept_first, nele_eigh_kfirst(ws.eigws, B, SB_D), sizeof(int) * (size_t)B, hipMemcpyDeviceToHost) != hipSuccess)
         return nele_set_error(NELE_ERR_HIP, "nele_metric_siib_kept_first: copy failed");

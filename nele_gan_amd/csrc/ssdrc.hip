@@ -15,6 +15,7 @@
 // its position in the batch.  With both stages off sum y^2 is sum x^2 bit for bit, the scale is 1.0 and the output is the input.
 #include "common.h"
 #include "fft512.h"
+#include "ws_arena.h"
 #include <cmath>
 #include "../../include/nele_hip.h"
 
@@ -305,7 +306,7 @@ __global__ __launch_bounds__(1024) void ssdrc_final_kernel(const float* __restri
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------- host
-static inline long long ss_align256(long long v) { return (v + 255) / 256 * 256; }
+static inline long long ss_align256(long long v) { return (long long)ws_round256((size_t)v); }
 static inline int ss_nf(int Lmax) { return ss_frames(Lmax); }
 
 struct SsLayout {

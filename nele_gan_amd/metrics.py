@@ -61,15 +61,15 @@ class CleanStateCache:
         self.hits = self.misses = self.stored = self.declined = self.partial = 0
         self.poison = False         # tests: fill the workspace with 0xFF bytes before a restore (a forgotten section cannot go unnoticed)
 
-    @staticmethod
-    def _sections(kind, B, L, fs):
+    # kind -> (section list of the library, whether it takes the sampling rate)
+    _SECTION_FUNCS = {'siib': ('nele_metric_siib_clean_sections', False), 'haspi': ('nele_metric_haspi_clean_sections', True),
+                      'hasqi': ('nele_metric_hasqi_clean_sections', True)}
+
+    @classmethod
+    def _sections(cls, kind, B, L, fs):
+        name, takes_fs = cls._SECTION_FUNCS[kind]
         buf = (c_longlong * (3 * 24))()
-        if kind == 'siib':
-            n = _lib.lib.nele_metric_siib_clean_sections(int(B), int(L), buf, 24)
-        elif kind == 'hasqi':
-            n = _lib.lib.nele_metric_hasqi_clean_sections(int(B), int(L), int(fs), buf, 24)
-        else:
-            n = _lib.lib.nele_metric_haspi_clean_sections(int(B), int(L), int(fs), buf, 24)
+        n = getattr(_lib.lib, name)(int(B), int(L), *([int(fs)] if takes_fs else []), buf, 24)
         if n < 0:
             return None
         return [(int(buf[3 * k]), int(buf[3 * k + 1]), int(buf[3 * k + 2])) for k in range(n)]
@@ -109,15 +109,17 @@ class CleanStateCache:
         return rows if 0 < len(rows) < len(keys) else None
 
     @staticmethod
-    def _runs(slots):
-        """[(block, row)] in batch order -> runs (first batch row, block, first block row, count) of consecutive rows"""
+    def _runs(slots, rows=None):
+        """[(block, row)] of batch rows ``rows`` (default: 0, 1, ..) -> runs (first batch row, block, first block row, count) of consecutive
+        batch rows that sit in consecutive rows of one block"""
+        rows = range(len(slots)) if rows is None else rows
         runs, k = [], 0
         while k < len(slots):
             b, r = slots[k]
             n = 1
-            while k + n < len(slots) and slots[k + n] == (b, r + n):
+            while k + n < len(slots) and rows[k + n] == rows[k] + n and slots[k + n] == (b, r + n):
                 n += 1
-            runs.append((k, b, r, n))
+            runs.append((rows[k], b, r, n))
             k += n
         return runs
 
@@ -170,14 +172,7 @@ class CleanStateCache:
         new = new[:len(slots)]
         if not new:
             return False
-        # runs of consecutive batch rows that landed in consecutive pool rows
-        runs, k = [], 0
-        while k < len(new):
-            n = 1
-            while (k + n < len(new) and new[k + n][0] == new[k][0] + n and slots[k + n] == (slots[k][0], slots[k][1] + n)):
-                n += 1
-            runs.append((new[k][0], slots[k][0], slots[k][1], n))
-            k += n
+        runs = self._runs(slots, [k for k, _key in new])
         j = 0
         for (off, st, nb) in sec:
             if st == 0:
@@ -335,11 +330,64 @@ def siib_clean_stages(x, lengths=None):
     return out
 
 
-class SiibSplit:
+class _CleanSplit:
+    """The clean-part protocol of SiibSplit, HaspiSplit and HasqiSplit.  A class names its CleanStateCache kind (its workspaces are
+    KIND_split and, for a sub-batch, KIND_split_sub) and supplies, with whatever per-call arguments its clean_part() takes:
+      _geom(*args)       the geometry key of the state phase 3 leaves, or None when this call's state must not be cached
+      _phase3(*args)     the library call
+      _sub(rows, *args)  -> (an object of the same class for batch rows ``rows`` on the sub-batch workspace, its own *args)"""
+
+    KIND = None
+    fs = 0                                      # what the section lists take as the sampling rate (SIIB: none)
+
+    def _sub_kw(self, rows):
+        return dict(lengths=None if self.lengths is None else self.lengths[rows], owner=self.owner, ws_kind=self.KIND + '_split_sub')
+
+    def clean_part(self, cache=None, keys=None):
+        """cache / keys: see _clean_part (the CleanStateCache kind is the class's KIND)."""
+        return self._clean_part(cache, keys)
+
+    def _clean_part(self, cache, keys, *args):
+        """cache (CleanStateCache) + keys (one hashable per utterance, e.g. the file name): when every utterance's clean-signal state is
+        cached it is copied into the workspace instead of being recomputed; when some are, phase 3 runs for the others only (a batch of
+        their own on a second workspace) and everything is copied in; otherwise phase 3 runs for the batch and its utterances are stored.
+        -> True when the state came from the cache."""
+        geom = None if cache is None or keys is None else self._geom(*args)
+        if geom is None:
+            self._phase3(*args)
+            return False
+        kind, fs = self.KIND, self.fs
+        B, L = self.x.shape
+        full = list(keys)                       # a key stands for the clean waveform, its own length included
+        slots = cache.lookup(kind, geom, full)
+        if slots is not None:
+            cache.restore(kind, geom, self.ws, B, L, fs, slots)
+            return True
+        rows = cache.missing(kind, geom, full)
+        if rows is not None:
+            # some utterances of the batch are known (a loop that re-draws its batches every epoch): phase 3 for the others only, as a batch
+            # of their own on a second workspace, then everything comes from the cache (the kernels are batch-invariant: an utterance's state
+            # does not depend on its row or on its batch-mates)
+            sub, sub_args = self._sub(rows, *args)
+            sub._phase3(*sub_args)
+            if cache.store(kind, geom, sub.ws, len(rows), L, fs, [full[i] for i in rows]):
+                slots = cache.lookup(kind, geom, full, count=False)
+                if slots is not None:
+                    cache.partial += 1
+                    cache.restore(kind, geom, self.ws, B, L, fs, slots)
+                    return True
+        self._phase3(*args)
+        cache.store(kind, geom, self.ws, B, L, fs, full)
+        return False
+
+
+class SiibSplit(_CleanSplit):
     """batch_siib in pieces.  front()/back(): wide kernels (VAD .. covariance) / latency-bound eigen-decomposition .. score, so
     that independent work can be enqueued in between on another stream.  clean_part()/degraded_part(y): split by data
     dependence - SIIB's Karhunen-Loeve basis comes from the clean signal alone, so VAD, the clean spectra, the covariance and its
     eigen-decomposition can run before the degraded signal exists."""
+
+    KIND = 'siib'
 
     def __init__(self, x, y=None, lengths=None, owner=None, ws_kind='siib_split'):
         self.lengths = None
@@ -370,36 +418,14 @@ class SiibSplit:
         self._call(2)
         return self.raw, self.mapped
 
-    def clean_part(self, cache=None, keys=None):
-        """cache (CleanStateCache) + keys (one hashable per utterance, e.g. the file name): when every utterance's clean-signal state is
-        cached it is copied into the workspace instead of being recomputed; when some are, phase 3 runs for the others only (a batch of
-        their own on a second workspace) and everything is copied in; otherwise phase 3 runs for the batch and its utterances are stored."""
-        if cache is None or keys is None:
-            self._call(3)
-            return False
-        B, L = self.x.shape
-        geom = ('L', L)
-        full = list(keys)                       # a key stands for the clean waveform, its own length included
-        slots = cache.lookup('siib', geom, full)
-        if slots is not None:
-            cache.restore('siib', geom, self.ws, B, L, 0, slots)
-            return True
-        rows = cache.missing('siib', geom, full)
-        if rows is not None:
-            # some utterances of the batch are known (a loop that re-draws its batches every epoch): phase 3 for the others only, as a batch
-            # of their own on a second workspace, then everything comes from the cache (the kernels are batch-invariant: an utterance's state
-            # does not depend on its row or on its batch-mates)
-            sub = SiibSplit(self.x[rows], lengths=None if self.lengths is None else self.lengths[rows], owner=self.owner, ws_kind='siib_split_sub')
-            sub._call(3)
-            if cache.store('siib', geom, sub.ws, len(rows), L, 0, [full[i] for i in rows]):
-                slots = cache.lookup('siib', geom, full, count=False)
-                if slots is not None:
-                    cache.partial += 1
-                    cache.restore('siib', geom, self.ws, B, L, 0, slots)
-                    return True
+    def _geom(self):
+        return ('L', self.x.shape[1])
+
+    def _phase3(self):
         self._call(3)
-        cache.store('siib', geom, self.ws, B, L, 0, full)
-        return False
+
+    def _sub(self, rows):
+        return SiibSplit(self.x[rows], **self._sub_kw(rows)), ()
 
     def degraded_part(self, y):
         assert y.shape == self.x.shape
@@ -411,18 +437,11 @@ class SiibSplit:
 def batch_siib(x, y, return_info=False, lengths=None):
     """clean x [B,L], degraded y [B,L] (16 kHz) -> (raw [B] bits/s, mapped [B]); the replication rule of
     intel.py:93-97 is applied per utterance on the device.  info [B,4] = (M, tiled frames, active frames, status)."""
-    x, y, _ = _pair(x, y)
-    B, L = x.shape
-    nb = _lib.lib.nele_metric_siib_workspace_bytes(B, L)
-    ws = _workspace('siib', nb, x.device)
-    raw = torch.empty(B, device=x.device)
-    mapped = torch.empty(B, device=x.device)
-    info = torch.zeros((B, 4), dtype=torch.int32, device=x.device)
-    call('nele_metric_siib_var', ptr(x), ptr(y), ptr(_lens(lengths, x.device)), B, L, ptr(ws), ws.numel(), ptr(raw), ptr(mapped), ptr(info), 0,
-         stream())
+    sp = SiibSplit(x, y, lengths=lengths, ws_kind='siib')
+    sp._call(0)
     if return_info:
-        return raw, mapped, info
-    return raw, mapped
+        return sp.raw, sp.mapped, sp.info
+    return sp.raw, sp.mapped
 
 
 def _siib_checked(x, y):
@@ -581,10 +600,12 @@ def haspi_dither_rows(utt_ids, seed, L, fs=16000, device=None):
     return out
 
 
-class HaspiSplit:
+class HaspiSplit(_CleanSplit):
     """batch_haspi split by data dependence: clean_part() runs the whole reference-signal chain (ear model, envelope filter,
     silence gate, group-delay shifts, cepstra, modulation filters) before the degraded signal exists; degraded_part(y) does the same
     for y and correlates.  Own workspace: the clean-signal state must survive until degraded_part()."""
+
+    KIND = 'haspi'
 
     def __init__(self, x, fs=16000, lengths=None, owner=None, ws_kind='haspi_split'):
         self.x = x.contiguous().float()
@@ -602,33 +623,22 @@ class HaspiSplit:
         call('nele_metric_haspi_var', ptr(self.x), ptr(y), ptr(self.lengths), B, L, self.fs, ptr(dither), ptr(self.ws), self.ws.numel(),
              ptr(self.raw), ptr(self.mapped), ptr(self.info), phase, stream())
 
-    def clean_part(self, dither=None, cache=None, keys=None, dither_tag=None):
-        """cache / keys: as SiibSplit.clean_part.  ``dither_tag``: hashable that identifies the reference's dither rows (None = no dither;
-        e.g. ('utterance', seed) for rows drawn per utterance id) - a cached state is only valid for the dither it was computed with;
-        a dither with no tag is never cached."""
-        if cache is None or keys is None or (dither is not None and dither_tag is None):
-            self._call(None, dither, 3)
-            return False
-        B, L = self.x.shape
-        geom = ('L', L, 'fs', self.fs, 'dither', dither_tag)
-        full = list(keys)
-        slots = cache.lookup('haspi', geom, full)
-        if slots is not None:
-            cache.restore('haspi', geom, self.ws, B, L, self.fs, slots)
-            return True
-        rows = cache.missing('haspi', geom, full)
-        if rows is not None:                                      # (see SiibSplit.clean_part: the unknown utterances as a batch of their own)
-            sub = HaspiSplit(self.x[rows], fs=self.fs, lengths=None if self.lengths is None else self.lengths[rows], owner=self.owner, ws_kind='haspi_split_sub')
-            sub._call(None, None if dither is None else dither[rows].contiguous(), 3)
-            if cache.store('haspi', geom, sub.ws, len(rows), L, self.fs, [full[i] for i in rows]):
-                slots = cache.lookup('haspi', geom, full, count=False)
-                if slots is not None:
-                    cache.partial += 1
-                    cache.restore('haspi', geom, self.ws, B, L, self.fs, slots)
-                    return True
+    def _geom(self, dither, dither_tag):
+        if dither is not None and dither_tag is None:
+            return None
+        return ('L', self.x.shape[1], 'fs', self.fs, 'dither', dither_tag)
+
+    def _phase3(self, dither, dither_tag):
         self._call(None, dither, 3)
-        cache.store('haspi', geom, self.ws, B, L, self.fs, full)
-        return False
+
+    def _sub(self, rows, dither, dither_tag):
+        return (HaspiSplit(self.x[rows], fs=self.fs, **self._sub_kw(rows)), (None if dither is None else dither[rows].contiguous(), dither_tag))
+
+    def clean_part(self, dither=None, cache=None, keys=None, dither_tag=None):
+        """cache / keys: see _CleanSplit._clean_part (CleanStateCache kind 'haspi').  ``dither_tag``: hashable that identifies the reference's
+        dither rows (None = no dither; e.g. ('utterance', seed) for rows drawn per utterance id) - a cached state is only valid for the
+        dither it was computed with; a dither with no tag is never cached."""
+        return self._clean_part(cache, keys, dither, dither_tag)
 
     def degraded_part(self, y, dither=None):
         assert y.shape == self.x.shape
@@ -670,7 +680,7 @@ QUALITY_TARGET_FIELDS = ('Nonlin', 'Linear')          # D_Qua's two targets when
 _HASQI_NOISE = {False: 0, None: 0, 0: 0, True: 1, 1: 1, 'row': 1, 'utterance': 2, 2: 2}
 
 
-class HasqiSplit:
+class HasqiSplit(_CleanSplit):
     """HASQI v2 (pyhaspi2.py:32-74) of a batch, split by data dependence like HaspiSplit: clean_part() runs everything that needs the
     reference x alone (its ear model with the basilar-membrane motion, group-delay shifts, smoothed envelope, mean squares, segment
     loudness) and degraded_part(y) - any number of times - the chain of y, the cross-covariance and the scores: float64 [B, 7]
@@ -678,6 +688,8 @@ class HasqiSplit:
     noise: False | True (eb_BMaddnoise keyed by (seed, row of the batch)) | 'utterance' (keyed by (seed, utt_ids[b]): an utterance is
     scored alike at any row of any batch on any rank).  The noise of x is part of what clean_part() leaves.  HL: audiogram heard by both
     signals.  Own workspace: the clean-signal state must survive until degraded_part()."""
+
+    KIND = 'hasqi'
 
     def __init__(self, x, fs=16000, lengths=None, noise=False, seed=0, utt_ids=None, HL=None, owner=None, ws_kind='hasqi_split'):
         self.x = x.contiguous().float()
@@ -705,36 +717,17 @@ class HasqiSplit:
              ptr(self.ws), self.ws.numel(), ptr(out), ptr(self.info), phase, stream())
 
     def _geom(self):
-        B, L = self.x.shape
         # a cached state is valid for the noise it holds: none, or the per-utterance one of this seed; row-keyed noise is never cached
-        return ('L', L, 'fs', self.fs, 'noise', (self.noise, self.seed) if self.noise else 0, 'HL', None if self.hl is None else tuple(self.hl))
+        if self.noise == 1:
+            return None
+        return ('L', self.x.shape[1], 'fs', self.fs, 'noise', (self.noise, self.seed) if self.noise else 0, 'HL', None if self.hl is None else tuple(self.hl))
 
-    def clean_part(self, cache=None, keys=None):
-        """cache / keys: as SiibSplit.clean_part (CleanStateCache kind 'hasqi')."""
-        if cache is None or keys is None or self.noise == 1:
-            self._call(None, 3)
-            return False
-        B, L = self.x.shape
-        geom = self._geom()
-        full = list(keys)
-        slots = cache.lookup('hasqi', geom, full)
-        if slots is not None:
-            cache.restore('hasqi', geom, self.ws, B, L, self.fs, slots)
-            return True
-        rows = cache.missing('hasqi', geom, full)
-        if rows is not None:                                      # (see SiibSplit.clean_part: the unknown utterances as a batch of their own)
-            sub = HasqiSplit(self.x[rows], fs=self.fs, lengths=None if self.lengths is None else self.lengths[rows], noise=self.noise, seed=self.seed,
-                             utt_ids=None if self.utt_ids is None else self.utt_ids[rows], HL=self.HL, owner=self.owner, ws_kind='hasqi_split_sub')
-            sub._call(None, 3)
-            if cache.store('hasqi', geom, sub.ws, len(rows), L, self.fs, [full[i] for i in rows]):
-                slots = cache.lookup('hasqi', geom, full, count=False)
-                if slots is not None:
-                    cache.partial += 1
-                    cache.restore('hasqi', geom, self.ws, B, L, self.fs, slots)
-                    return True
+    def _phase3(self):
         self._call(None, 3)
-        cache.store('hasqi', geom, self.ws, B, L, self.fs, full)
-        return False
+
+    def _sub(self, rows):
+        return HasqiSplit(self.x[rows], fs=self.fs, noise=self.noise, seed=self.seed, utt_ids=None if self.utt_ids is None else self.utt_ids[rows],
+                          HL=self.HL, **self._sub_kw(rows)), ()
 
     def degraded_part(self, y):
         assert y.shape == self.x.shape
