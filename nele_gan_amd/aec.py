@@ -12,9 +12,11 @@ is DESIGN.md section 14).  This module owns memory and bookkeeping only; there i
     out = loop.process(clean_hops, mic_hops)                   # during the next call's capture
 
     python -m nele_gan_amd.aec --mic mic.wav --played far.wav --out residual.wav [--partitions 8] [--echo-path h.npy] [--bulk-blocks 32]
+                               [--suppress [--res-beta 2.0] [--res-gmin 0.1]]
 
 A bulk delay (the device's playback and capture buffers) is found and taken out ahead of the canceller by nele_gan_amd/bulkdelay.py
-(``AlignedEchoCanceller``; --bulk-blocks on the command line).
+(``AlignedEchoCanceller``; --bulk-blocks on the command line).  The echo the canceller leaves is suppressed behind it by
+nele_gan_amd/res.py (``SuppressedEchoCanceller``; --suppress on the command line).
 """
 import numpy as np
 import torch
@@ -157,11 +159,13 @@ class EchoCancellingEnhancer:
 
 
 # ------------------------------------------------------------------------------------------------------------------ command line
-def cancel_file(mic, played, partitions=8, mu=0.5, gamma=4.0, delta=1e-2, device='cuda', bulk_blocks=None):
+def cancel_file(mic, played, partitions=8, mu=0.5, gamma=4.0, delta=1e-2, device='cuda', bulk_blocks=None, suppress=None):
     """mic, played: float32 arrays of one length L -> (residual [L] float32, echo path [partitions * 256] float64): the whole hops through
     one EchoCanceller call, the last L % 256 samples zero-padded to one more hop and cut again.  bulk_blocks: search that many blocks
     for a bulk delay and cancel against `played` delayed by it (bulkdelay.AlignedEchoCanceller); the return value gains a third
-    element, the delay found in hops (-1: none)."""
+    element, the delay found in hops (-1: none).  suppress: (beta, gmin) of a res.ResidualEchoSuppressor behind the canceller
+    (res.SuppressedEchoCanceller): the residual is the suppressed one, one hop late as process() returns it - its first 256 samples
+    are the canceller's own residual and the file's last hop does not come out."""
     mic = np.ascontiguousarray(mic, dtype=np.float32).reshape(-1)
     played = np.ascontiguousarray(played, dtype=np.float32).reshape(-1)
     if mic.shape != played.shape or mic.size == 0:
@@ -174,11 +178,15 @@ def cancel_file(mic, played, partitions=8, mu=0.5, gamma=4.0, delta=1e-2, device
     aec = EchoCanceller(1, partitions=partitions, mu=mu, gamma=gamma, delta=delta, device=device)
     if bulk_blocks is not None:
         from .bulkdelay import AlignedEchoCanceller, BulkDelay
-        aec = AlignedEchoCanceller(BulkDelay(1, blocks=bulk_blocks, device=device), aec)
+        bulk = BulkDelay(1, blocks=bulk_blocks, device=device)
+        aec = AlignedEchoCanceller(bulk, aec)
+    if suppress is not None:
+        from .res import ResidualEchoSuppressor, SuppressedEchoCanceller
+        aec = SuppressedEchoCanceller(aec, ResidualEchoSuppressor(1, beta=suppress[0], gmin=suppress[1], device=device))
     res = aec.process(torch.from_numpy(d), torch.from_numpy(x))
     h = aec.echo_path()
     if bulk_blocks is not None:
-        return res[0, :L].cpu().numpy(), h[0].cpu().numpy(), int(aec.bulk.delays()[0].item())
+        return res[0, :L].cpu().numpy(), h[0].cpu().numpy(), int(bulk.delays()[0].item())
     return res[0, :L].cpu().numpy(), h[0].cpu().numpy()
 
 
@@ -193,6 +201,10 @@ def build_parser():
     ap.add_argument('--bulk-blocks', type=int, default=None, metavar='N',
                     help='search N 256-sample blocks (2 .. 64) for a bulk delay and cancel against --played delayed by the whole hops found '
                          '(default: no search)')
+    ap.add_argument('--suppress', action='store_true',
+                    help='suppress the echo the canceller leaves (nele_gan_amd/res.py); the output is then one 256-sample hop late')
+    ap.add_argument('--res-beta', type=float, default=2.0, help='with --suppress: the over-subtraction factor, >= 0')
+    ap.add_argument('--res-gmin', type=float, default=0.1, help='with --suppress: the floor of the gain, in (0, 1]')
     ap.add_argument('--mu', type=float, default=0.5)
     ap.add_argument('--gamma', type=float, default=4.0)
     ap.add_argument('--delta', type=float, default=1e-2)
@@ -217,7 +229,11 @@ def main(argv=None):
         ap.error('--mic and --played must have one length (got %d and %d samples)' % (len(sig[0]), len(sig[1])))
     if a.bulk_blocks is not None and not 2 <= a.bulk_blocks <= _lib.CONSTS['NELE_BULK_MAX_BLOCKS']:
         ap.error('--bulk-blocks must be in 2 .. %d' % _lib.CONSTS['NELE_BULK_MAX_BLOCKS'])
-    res, h, *found = cancel_file(sig[0], sig[1], partitions=a.partitions, mu=a.mu, gamma=a.gamma, delta=a.delta, bulk_blocks=a.bulk_blocks)
+    if a.suppress and (not (0.0 <= a.res_beta < float('inf')) or not (0.0 < a.res_gmin <= 1.0)):
+        ap.error('needs --res-beta >= 0 and 0 < --res-gmin <= 1')
+    suppress = (a.res_beta, a.res_gmin) if a.suppress else None
+    res, h, *found = cancel_file(sig[0], sig[1], partitions=a.partitions, mu=a.mu, gamma=a.gamma, delta=a.delta, bulk_blocks=a.bulk_blocks,
+                                 suppress=suppress)
     dataio.write_wav_pcm16(a.out, res)
     if a.echo_path:
         np.save(a.echo_path, h)
@@ -225,6 +241,8 @@ def main(argv=None):
     if found:
         print('bulk delay: %s' % ('none found in %d blocks' % a.bulk_blocks if found[0] < 0 else
                                   '%d hops (%d ms) taken out ahead of the canceller' % (found[0], found[0] * HOP * 1000 // dataio.fs)))
+    if a.suppress:
+        print('residual echo suppressed (beta %g, gmin %g): the output is one hop (%d ms) late' % (a.res_beta, a.res_gmin, HOP * 1000 // dataio.fs))
     return 0
 
 
