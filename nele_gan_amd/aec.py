@@ -11,11 +11,12 @@ is DESIGN.md section 14).  This module owns memory and bookkeeping only; there i
     loop = EchoCancellingEnhancer(RealtimeEnhancer(...), aec)  # closes the loop: what process() returns is what the loudspeaker plays
     out = loop.process(clean_hops, mic_hops)                   # during the next call's capture
 
-    python -m nele_gan_amd.aec --mic mic.wav --played far.wav --out residual.wav [--partitions 8] [--echo-path h.npy] [--bulk-blocks 32]
+    python -m nele_gan_amd.aec --mic mic.wav --played far.wav --out residual.wav [--partitions 8] [--echo-path h.npy] [--bulk-blocks 32 [--bulk-track]]
                                [--suppress [--res-beta 2.0] [--res-gmin 0.1]]
 
 A bulk delay (the device's playback and capture buffers) is found and taken out ahead of the canceller by nele_gan_amd/bulkdelay.py
-(``AlignedEchoCanceller``; --bulk-blocks on the command line).  The echo the canceller leaves is suppressed behind it by
+(``AlignedEchoCanceller``; --bulk-blocks on the command line), and followed when it moves later by nele_gan_amd/bulktrack.py
+(``TrackedEchoCanceller``; --bulk-track).  The echo the canceller leaves is suppressed behind it by
 nele_gan_amd/res.py (``SuppressedEchoCanceller``; --suppress on the command line).
 """
 import numpy as np
@@ -91,6 +92,14 @@ class EchoCanceller(SlotState):
         call('nele_aec_reset', ptr(self.state), c_longlong(self.nbytes), self.S, self.P, ptr(self._dev_bytes(m)), stream())
         self.hops[m] = 0
 
+    def reset_flagged(self, flags):
+        """reset() of the slots with flags[b] != 0, flags a uint8 [streams] tensor ON THE DEVICE (bulktrack.TrackingBulkDelay's `moved`):
+        which slots restart is decided on the GPU, the host neither reads the flags nor waits - and so its counter ``hops`` is not
+        told."""
+        if tuple(flags.shape) != (self.S,) or flags.dtype != torch.uint8:
+            raise ValueError("EchoCanceller.reset_flagged: flags must be uint8 [%d] on the device" % self.S)
+        call('nele_aec_reset', ptr(self.state), c_longlong(self.nbytes), self.S, self.P, ptr(flags), stream())
+
 
 class EchoCancellingEnhancer:
     """``RealtimeEnhancer`` behind an ``EchoCanceller``, the loop closed: per call
@@ -159,12 +168,14 @@ class EchoCancellingEnhancer:
 
 
 # ------------------------------------------------------------------------------------------------------------------ command line
-def cancel_file(mic, played, partitions=8, mu=0.5, gamma=4.0, delta=1e-2, device='cuda', bulk_blocks=None, suppress=None):
+def cancel_file(mic, played, partitions=8, mu=0.5, gamma=4.0, delta=1e-2, device='cuda', bulk_blocks=None, suppress=None, bulk_track=False):
     """mic, played: float32 arrays of one length L -> (residual [L] float32, echo path [partitions * 256] float64): the whole hops through
     one EchoCanceller call, the last L % 256 samples zero-padded to one more hop and cut again.  bulk_blocks: search that many blocks
     for a bulk delay and cancel against `played` delayed by it (bulkdelay.AlignedEchoCanceller); the return value gains a third
-    element, the delay found in hops (-1: none).  suppress: (beta, gmin) of a res.ResidualEchoSuppressor behind the canceller
-    (res.SuppressedEchoCanceller): the residual is the suppressed one, one hop late as process() returns it - its first 256 samples
+    element, the delay found in hops (-1: none).  bulk_track (with bulk_blocks): the search goes on behind the lock and follows the delay
+    when it moves (bulktrack.TrackedEchoCanceller); the file then goes through hop by hop, the delay is read back after every hop, and
+    the third element is the list of (hop, delay in hops) of the lock and of every move (empty: none found).  suppress: (beta, gmin)
+    of a res.ResidualEchoSuppressor behind the canceller (res.SuppressedEchoCanceller): the residual is the suppressed one, one hop late as process() returns it - its first 256 samples
     are the canceller's own residual and the file's last hop does not come out."""
     mic = np.ascontiguousarray(mic, dtype=np.float32).reshape(-1)
     played = np.ascontiguousarray(played, dtype=np.float32).reshape(-1)
@@ -176,13 +187,27 @@ def cancel_file(mic, played, partitions=8, mu=0.5, gamma=4.0, delta=1e-2, device
     x = np.zeros((1, nh * HOP), dtype=np.float32)
     d[0, :L], x[0, :L] = mic, played
     aec = EchoCanceller(1, partitions=partitions, mu=mu, gamma=gamma, delta=delta, device=device)
-    if bulk_blocks is not None:
+    if bulk_blocks is not None and bulk_track:
+        from .bulktrack import TrackedEchoCanceller, TrackingBulkDelay
+        bulk = TrackingBulkDelay(1, blocks=bulk_blocks, device=device)
+        aec = TrackedEchoCanceller(bulk, aec)
+    elif bulk_blocks is not None:
         from .bulkdelay import AlignedEchoCanceller, BulkDelay
         bulk = BulkDelay(1, blocks=bulk_blocks, device=device)
         aec = AlignedEchoCanceller(bulk, aec)
     if suppress is not None:
         from .res import ResidualEchoSuppressor, SuppressedEchoCanceller
         aec = SuppressedEchoCanceller(aec, ResidualEchoSuppressor(1, beta=suppress[0], gmin=suppress[1], device=device))
+    if bulk_blocks is not None and bulk_track:
+        dd, xd = to_dev(torch.from_numpy(d), bulk.device), to_dev(torch.from_numpy(x), bulk.device)
+        res, events, last = [], [], -1
+        for k in range(nh):
+            res.append(aec.process(dd[:, k * HOP:(k + 1) * HOP].contiguous(), xd[:, k * HOP:(k + 1) * HOP].contiguous()))
+            now = int(bulk.delays()[0].item())
+            if now != last:
+                events.append((k, now))
+                last = now
+        return torch.cat(res, dim=1)[0, :L].cpu().numpy(), aec.echo_path()[0].cpu().numpy(), events
     res = aec.process(torch.from_numpy(d), torch.from_numpy(x))
     h = aec.echo_path()
     if bulk_blocks is not None:
@@ -201,6 +226,8 @@ def build_parser():
     ap.add_argument('--bulk-blocks', type=int, default=None, metavar='N',
                     help='search N 256-sample blocks (2 .. 64) for a bulk delay and cancel against --played delayed by the whole hops found '
                          '(default: no search)')
+    ap.add_argument('--bulk-track', action='store_true',
+                    help='with --bulk-blocks: go on searching behind the lock and follow the delay when it moves (nele_gan_amd/bulktrack.py)')
     ap.add_argument('--suppress', action='store_true',
                     help='suppress the echo the canceller leaves (nele_gan_amd/res.py); the output is then one 256-sample hop late')
     ap.add_argument('--res-beta', type=float, default=2.0, help='with --suppress: the over-subtraction factor, >= 0')
@@ -231,14 +258,22 @@ def main(argv=None):
         ap.error('--bulk-blocks must be in 2 .. %d' % _lib.CONSTS['NELE_BULK_MAX_BLOCKS'])
     if a.suppress and (not (0.0 <= a.res_beta < float('inf')) or not (0.0 < a.res_gmin <= 1.0)):
         ap.error('needs --res-beta >= 0 and 0 < --res-gmin <= 1')
+    if a.bulk_track and a.bulk_blocks is None:
+        ap.error('--bulk-track needs --bulk-blocks')
     suppress = (a.res_beta, a.res_gmin) if a.suppress else None
     res, h, *found = cancel_file(sig[0], sig[1], partitions=a.partitions, mu=a.mu, gamma=a.gamma, delta=a.delta, bulk_blocks=a.bulk_blocks,
-                                 suppress=suppress)
+                                 suppress=suppress, bulk_track=a.bulk_track)
     dataio.write_wav_pcm16(a.out, res)
     if a.echo_path:
         np.save(a.echo_path, h)
     print('%s: %d samples, %d partitions (%d ms of echo tail)' % (a.out, len(res), a.partitions, a.partitions * HOP * 1000 // dataio.fs))
-    if found:
+    if found and a.bulk_track:
+        if not found[0]:
+            print('bulk delay: none found in %d blocks' % a.bulk_blocks)
+        for i, (k, hops) in enumerate(found[0]):
+            print('bulk delay: %s at hop %d: %d hops (%d ms) taken out ahead of the canceller'
+                  % ('moved' if i else 'locked', k, hops, hops * HOP * 1000 // dataio.fs))
+    elif found:
         print('bulk delay: %s' % ('none found in %d blocks' % a.bulk_blocks if found[0] < 0 else
                                   '%d hops (%d ms) taken out ahead of the canceller' % (found[0], found[0] * HOP * 1000 // dataio.fs)))
     if a.suppress:

@@ -6,22 +6,18 @@
 //   bulk_hop_kernel    : one workgroup per stream and call, looping over the call's hops
 //   bulk_set_kernel    : nele_bulk_set_delay, one thread per slot
 //   bulk_status_kernel : nele_bulk_status, one workgroup per slot
-// While a slot searches: wave 0 takes ONE complex transform for the two real ones ([x_prev, x] + i [0, d]); thread t owns slot t of
-// S_d, S_x and D'; then one wave per pair of blocks (q, q + 1) updates C_q, C_q+1 (16-byte accesses, 64 consecutive slots per
-// instruction) and, from hop Q on, takes their two r_q from one Hermitian-packed inverse transform and reduces the squares; an odd Q
-// leaves the last block a zero partner.  Pairs are (0, 1), (2, 3), ... whatever the ring position, every operand is the stream's own,
-// every sum has a fixed order: a slot's bits do not depend on the hop grouping, on B or on the other slots.  Once locked, a
-// workgroup-uniform branch leaves only the delay line.  State is read and written with plain loads and stores by the stream's own
+// While a slot searches, each hop runs the search step of csrc/bulk_search.h (shared with csrc/bulktrack.hip): every operand is the
+// stream's own, every sum has a fixed order: a slot's bits do not depend on the hop grouping, on B or on the other slots.  Once locked,
+// a workgroup-uniform branch leaves only the delay line.  State is read and written with plain loads and stores by the stream's own
 // workgroup; no atomics, nothing crosses workgroups.
 #include "common.h"
 #include "fft512.h"
 #include "slot_state.h"
+#include "bulk_search.h"
 #include "../../include/nele_hip_ext.h"
 
 namespace {
 
-#define BULK_BLK 256                                       // samples per hop = slots per spectrum
-#define BULK_MAXQ NELE_BULK_MAX_BLOCKS
 constexpr long long BULK_HDR_BYTES = SLOT_GEOM_HDR_BYTES;  // int [0] = max_streams, [1] = blocks (what nele_bulk_init was given)
 // per-stream record, byte offsets.  A cleared record is a fresh slot, so cand and delay are kept plus one (0 = none / searching).
 constexpr long long BULK_O_META = 0;                       // int [8]: BULK_M_*
@@ -51,49 +47,36 @@ struct BulkArgs {
 };
 
 __global__ __launch_bounds__(256) void bulk_hop_kernel(BulkArgs a) {
-    __shared__ double2 tw[256];
-    __shared__ double2 xws[4][FFTW_SLOTS];
-    __shared__ double2 specX[BULK_BLK];                    // X_0
-    __shared__ double2 specD[BULK_BLK];                    // D, then D'
-    __shared__ double ebuf[BULK_MAXQ];
-    __shared__ float xbuf[2 * BULK_BLK];                   // [x_prev, x]
-    __shared__ float dbuf[BULK_BLK];
+    __shared__ BulkSearchLds lds;
     __shared__ int s_delay;
-    const int b = blockIdx.x, t = threadIdx.x, w = t >> 6, lane = t & 63;
+    const int b = blockIdx.x, t = threadIdx.x;
     if (b >= a.S) return;
     if (a.active && !a.active[b]) return;                  // neither read nor written
     if (!slot_hdr_matches(a.state, a.S, a.Q)) return;      // not the state nele_bulk_init laid out for (S, Q): touch nothing
     const int Q = a.Q;
     unsigned char* rec = a.state + BULK_HDR_BYTES + (size_t)b * bulk_rec_bytes(Q);
     int* meta = reinterpret_cast<int*>(rec + BULK_O_META);
-    double* confp = reinterpret_cast<double*>(rec + BULK_O_CONF);
-    double* erec = reinterpret_cast<double*>(rec + BULK_O_E);
-    float* xprev = reinterpret_cast<float*>(rec + BULK_O_XPREV);
-    double* Sdp = reinterpret_cast<double*>(rec + BULK_O_SD);
-    double* Sxp = reinterpret_cast<double*>(rec + BULK_O_SX);
     float* line = reinterpret_cast<float*>(rec + BULK_O_LINE);
-    double2* ring = reinterpret_cast<double2*>(rec + bulk_o_x(Q));
-    double2* Cst = reinterpret_cast<double2*>(rec + bulk_o_c(Q));
+    BulkSearchRec R;
+    R.confp = reinterpret_cast<double*>(rec + BULK_O_CONF);
+    R.erec = reinterpret_cast<double*>(rec + BULK_O_E);
+    R.xprev = reinterpret_cast<float*>(rec + BULK_O_XPREV);
+    R.Sdp = reinterpret_cast<double*>(rec + BULK_O_SD);
+    R.Sxp = reinterpret_cast<double*>(rec + BULK_O_SX);
+    R.ring = reinterpret_cast<double2*>(rec + bulk_o_x(Q));
+    R.Cst = reinterpret_cast<double2*>(rec + bulk_o_c(Q));
     const bool slot0 = (t == 0);
-    const double one_m_smooth = 1.0 - NELE_BULK_SMOOTH;
-    double2* xw = xws[w];
 
-    int head = min(max(meta[BULK_M_HEAD], 0), Q - 1);
+    BulkSearchRegs g;
+    g.head = min(max(meta[BULK_M_HEAD], 0), Q - 1);
     int lhead = min(max(meta[BULK_M_LHEAD], 0), Q - 1);
-    int n = meta[BULK_M_N], cand = meta[BULK_M_CAND1] - 1, run = meta[BULK_M_RUN];
+    g.n = meta[BULK_M_N];
+    g.cand = meta[BULK_M_CAND1] - 1;
+    g.run = meta[BULK_M_RUN];
     int delay = min(meta[BULK_M_DELAY1], Q) - 1;           // workgroup-uniform throughout
     const bool searched = delay < 0;                       // the search state is read, and written back, only by a slot that came in searching
-    double sd = 0.0, sx = 0.0, sd_ny = 0.0, sx_ny = 0.0;   // S_d, S_x of bin t (thread 0: bins 0 and 256)
-    if (searched) {
-        fft512_fill_twiddles(tw);
-        xbuf[t] = xprev[t];
-        sd = Sdp[t];
-        sx = Sxp[t];
-        if (slot0) {
-            sd_ny = Sdp[BULK_BLK];
-            sx_ny = Sxp[BULK_BLK];
-        }
-    }
+    g.sd = g.sx = g.sd_ny = g.sx_ny = 0.0;
+    if (searched) bulk_search_load(lds, R, g, t);
     const float* micb = a.mic + (size_t)b * a.ld;
     const float* plb = a.played + (size_t)b * a.ld;
     float* outb = a.aligned + (size_t)b * a.ld;
@@ -106,146 +89,13 @@ __global__ __launch_bounds__(256) void bulk_hop_kernel(BulkArgs a) {
         lhead = (lhead + 1 == Q) ? 0 : lhead + 1;
         line[(size_t)lhead * BULK_BLK + t] = xv;
         if (delay < 0) {
-            // ---- 2a. X_0 = rfft512([x_prev, x]) and D = rfft512([0 x 256, d]) from one complex transform (wave 0)
-            xbuf[BULK_BLK + t] = xv;
-            dbuf[t] = micb[col + t];
-            __syncthreads();
-            if (w == 0) {
-                double2 v[8];
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    const int i = fftw_n(lane, r);
-                    v[r] = make_double2((double)xbuf[i], (i >= BULK_BLK) ? (double)dbuf[i - BULK_BLK] : 0.0);
-                }
-                fftw_wave_sync();                          // the wave's earlier reads of xw precede the transform's writes
-                fft512_wave<false>(v, xw, tw, lane);
-                fft512_wave_store(v, xw, lane);
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    double2 X, D;
-                    fft512_packed_split(xw, 64 * m + lane, X, D);
-                    specX[64 * m + lane] = X;
-                    specD[64 * m + lane] = D;
-                }
-            }
-            __syncthreads();
-            // ---- 2b. the ring moves up one place; S_d, S_x and D' = D / sqrt(S_d S_x + eps) (thread t: slot t)
-            xbuf[t] = xv;                                  // x_prev <- x (wave 0 has read xbuf; the next write of its upper half is behind a barrier)
-            head = (head == 0) ? Q - 1 : head - 1;
-            {
-                const double2 X0 = specX[t], D = specD[t];
-                ring[(size_t)head * BULK_BLK + t] = X0;
-                double2 Dw;
-                if (slot0) {
-                    sd = NELE_BULK_SMOOTH * sd + one_m_smooth * (D.x * D.x);
-                    sd_ny = NELE_BULK_SMOOTH * sd_ny + one_m_smooth * (D.y * D.y);
-                    sx = NELE_BULK_SMOOTH * sx + one_m_smooth * (X0.x * X0.x);
-                    sx_ny = NELE_BULK_SMOOTH * sx_ny + one_m_smooth * (X0.y * X0.y);
-                    Dw = make_double2(D.x / sqrt(sd * sx + NELE_BULK_EPS), D.y / sqrt(sd_ny * sx_ny + NELE_BULK_EPS));
-                } else {
-                    sd = NELE_BULK_SMOOTH * sd + one_m_smooth * (D.x * D.x + D.y * D.y);
-                    sx = NELE_BULK_SMOOTH * sx + one_m_smooth * (X0.x * X0.x + X0.y * X0.y);
-                    const double s = sqrt(sd * sx + NELE_BULK_EPS);
-                    Dw = make_double2(D.x / s, D.y / s);
-                }
-                specD[t] = Dw;
-            }
-            if (n < 0x7fffffff) n += 1;                    // (a slot that never locks: 2^31 hops are more than a year)
-            const bool evaluate = n >= Q;
-            __syncthreads();                               // D' and the ring's newest spectrum are the pair loop's operands
-            // ---- 2c. C_q <- lambda C_q + D' conj(X_q); e_q = sum of squares of irfft512(C_q)[0 .. 256): one wave per pair of blocks
-            for (int pr = w; 2 * pr < Q; pr += 4) {
-                const int q0 = 2 * pr, q1 = q0 + 1;
-                const bool two = q1 < Q;
-                int r0 = head + q0, r1 = head + q1;
-                if (r0 >= Q) r0 -= Q;
-                if (r1 >= Q) r1 -= Q;
-                const double2* Xa = ring + (size_t)r0 * BULK_BLK;
-                const double2* Xb = ring + (size_t)(two ? r1 : r0) * BULK_BLK;
-                double2* Ca = Cst + (size_t)q0 * BULK_BLK;
-                double2* Cb = Cst + (size_t)(two ? q1 : q0) * BULK_BLK;
-                fftw_wave_sync();                          // the previous pair's reads of xw precede these writes
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    const int k = 64 * m + lane;
-                    const double2 G = specD[k], xa = Xa[k], xb = Xb[k];
-                    double2 ca = Ca[k], cb = Cb[k], pa, pb;
-                    if (k == 0) {
-                        pa = make_double2(G.x * xa.x, G.y * xa.y);
-                        pb = make_double2(G.x * xb.x, G.y * xb.y);
-                    } else {
-                        pa = make_double2(G.x * xa.x + G.y * xa.y, G.y * xa.x - G.x * xa.y);
-                        pb = make_double2(G.x * xb.x + G.y * xb.y, G.y * xb.x - G.x * xb.y);
-                    }
-                    ca = make_double2(a.lambda * ca.x + pa.x, a.lambda * ca.y + pa.y);
-                    cb = make_double2(a.lambda * cb.x + pb.x, a.lambda * cb.y + pb.y);
-                    Ca[k] = ca;
-                    if (two) Cb[k] = cb;
-                    else cb = make_double2(0.0, 0.0);
-                    if (evaluate) {
-                        xw[k] = ca;
-                        xw[BULK_BLK + k] = cb;
-                    }
-                }
-                if (!evaluate) continue;                   // (workgroup-uniform) the first Q - 1 hops only fill the sums
-                fftw_wave_sync();
-                const double2 a0 = xw[0], b0 = xw[BULK_BLK];
-                double2 v[8];
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    const int i = fftw_n(lane, r);
-                    const int k = ((i <= 256) ? i : 512 - i) & 255;
-                    v[r] = fft512_packed_join(xw[k], xw[BULK_BLK + k], a0, b0, i);
-                }
-                fftw_wave_sync();
-                fft512_wave<true>(v, xw, tw, lane);        // v[m] = 512 (r_q0 + i r_q1)[64 m + lane]; m < 4: the lags 0 .. 255
-                double ea = 0.0, eb = 0.0;
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    const double ra = v[m].x * (1.0 / 512.0), rb = v[m].y * (1.0 / 512.0);
-                    ea += ra * ra;
-                    eb += rb * rb;
-                }
-                ea = wave_sum(ea);
-                eb = wave_sum(eb);
-                if (lane == 0) {
-                    ebuf[q0] = ea;
-                    if (two) ebuf[q1] = eb;
-                }
-            }
-            // ---- 2d. the decision (thread 0)
-            if (evaluate) {
-                __syncthreads();
-                if (t < Q) erec[t] = ebuf[t];
-                if (slot0) {
-                    int qs = 0;
-                    double best = ebuf[0];
-                    for (int q = 1; q < Q; ++q)
-                        if (ebuf[q] > best) {
-                            best = ebuf[q];
-                            qs = q;
-                        }
-                    double rest = 0.0;
-                    for (int q = 0; q < Q; ++q)
-                        if (q != qs) rest += ebuf[q];
-                    const double lead = best * (double)(Q - 1);
-                    const bool ok = best > 0.0 && lead >= a.ratio * rest;
-                    *confp = lead / rest;
-                    if (ok && qs == cand) {
-                        run += 1;
-                    } else if (ok) {
-                        cand = qs;
-                        run = 1;
-                    } else {
-                        cand = -1;
-                        run = 0;
-                    }
-                    s_delay = (run >= a.hold) ? max(qs - 1, 0) : -1;
-                }
+            // ---- 2. the search step; the lock is a run of `hold` hops (thread 0 decides)
+            int qs = 0;
+            if (bulk_search_step(lds, R, g, Q, xv, micb[col + t], a.lambda, a.ratio, t, qs)) {
+                if (slot0) s_delay = (g.run >= a.hold) ? max(qs - 1, 0) : -1;
                 __syncthreads();
                 delay = s_delay;
             }
-            // (not evaluated: the pair loop's reads of specD and the ring precede their next writes behind the next hop's first barrier)
         }
         // ---- 3. the output hop: zeros while searching, then the delay line's entry of `delay` hops ago
         float y = 0.0f;
@@ -258,22 +108,14 @@ __global__ __launch_bounds__(256) void bulk_hop_kernel(BulkArgs a) {
         }
         outb[col + t] = y;
     }
-    if (searched) {
-        xprev[t] = xbuf[t];
-        Sdp[t] = sd;
-        Sxp[t] = sx;
-        if (slot0) {
-            Sdp[BULK_BLK] = sd_ny;
-            Sxp[BULK_BLK] = sx_ny;
-        }
-    }
+    if (searched) bulk_search_store(lds, R, g, t);
     if (slot0) {
         meta[BULK_M_LHEAD] = lhead;
         if (searched) {
-            meta[BULK_M_HEAD] = head;
-            meta[BULK_M_N] = n;
-            meta[BULK_M_CAND1] = cand + 1;
-            meta[BULK_M_RUN] = run;
+            meta[BULK_M_HEAD] = g.head;
+            meta[BULK_M_N] = g.n;
+            meta[BULK_M_CAND1] = g.cand + 1;
+            meta[BULK_M_RUN] = g.run;
             meta[BULK_M_DELAY1] = delay + 1;
         }
         if (a.delay_hops) a.delay_hops[b] = delay;
