@@ -516,6 +516,28 @@ int nele_metric_siib_phase(const float* x, const float* y, int B, int L, void* w
  * 7 nprim int, 8 XL clean half [28][NA], 9 lam [420], 10 U [420][420], 11 mu clean half [420], 12 the eigensolver's repair flag.
  * Returns the number of sections (max_sections >= 13) or a negative status.  Host-only: no device work. */
 int nele_metric_siib_clean_sections(int B, int L, long long* out, int max_sections);
+/* Diagnostic (tests): the buffers of the back end (the lag-product path behind the clean front end) in a workspace, as byte ranges in
+ * the same convention.  Ten per-utterance sections, in this order (NA = the active-frame capacity of the padded length L; na = info[2]
+ * active frames of the row, ncols = na - 14 stacked frames; signal 0 = clean x, 1 = degraded y; stacked row a = 28 k + j):
+ *   0 info    int    [4]               {M, frames of the tiled signal, na, status}
+ *   1 rowstat double [2][28][2]        per (signal, band): minimum before masking, mean after masking
+ *   2 XL      double [2][28][NA]       masked log band energies of the active frames, row mean NOT yet removed (columns < na)
+ *   3 mu      double [2][420]          window means of the stacked, row-mean-free rows: mean_{t < ncols} v_j[t + k]
+ *   4 lagp    double [3][4][29][784]   [pair][frame segment][lag slot][28 j1 + j2]: partial sums over the segment's frames s of
+ *                                      a_j1[s] b_j2[s + D], pair 0 = (x, x), 1 = (y, y), 2 = (x, y).  Slot D + 14 holds lag D; pairs 0 and 1
+ *                                      fill slots 14 .. 28 (D >= 0) only.  The lag product is (seg0 + seg1) + (seg2 + seg3).
+ *   5 C       double [420][420]        covariance Sxx / (ncols - 1), full and exactly symmetric - VALID ONLY between phase 1 and phase 2:
+ *                                      the eigensolver destroys it
+ *   6 S2      double [2][420][420]     Syy, then (Sxy + Sxy^T) / 2, unscaled; the UPPER triangle (row <= column) only, the strict lower
+ *                                      triangle is never written and never read
+ *   7 lam     double [420]             eigenvalues of C, ascending (after phase 2)
+ *   8 U       double [420][420]        ROW k = eigenvector k, meaningful for the kept components lam[k] > 1e-10 lam[419] only: a 64-row
+ *                                      tile without a kept component is zero, the cut rows of a partly kept tile are unspecified
+ *   9 qpart   double [420][14]         kept components only: u_k^T S u_k per 64-column tile, 7 tiles of Syy then 7 of sym(Sxy); a 64-row
+ *                                      tile without a kept component is never written, the cut rows of a partly kept tile are unspecified
+ * Returns the number of sections (max_sections >= 10) or a negative status (NELE_ERR_UNSUPPORTED without the lag-product path).
+ * Host-only: no device work. */
+int nele_metric_siib_sections(int B, int L, long long* out, int max_sections);
 /* Same with per-utterance lengths (the frame-periodic shortcut for L % 200 == 0 is not taken then; results are identical). */
 int nele_metric_siib_var(const float* x, const float* y, const int* lengths, int B, int L, void* workspace, long long workspace_bytes,
                          float* raw, float* mapped, int* info, int phase, void* stream);

@@ -1330,12 +1330,10 @@ static WsArena siib_layout(int B, int L, SiibWs& w, void* base) {
     a.take(w.U, (size_t)B * SB_D * SB_D);
     a.take(w.eigws, (size_t)nele_eigh_workspace_bytes(B, SB_D));
     a.take(w.part, (size_t)B * SB_D * NTL * 3);
-    // Frame segments of the lag-product kernel: more workgroups at small batches.  NOTE (documented non-invariance): the partial sums
-    // of an utterance are added in segment order, so the association of its covariance sums - and with it the last bits of its score -
-    // depends on the batch-size class (B < 48 / < 128 / >= 128) it is scored in; the products and their order inside a segment do not.
-    // Folding the segments inside one workgroup (the same association for every B) costs the 29-lag kernel 58 more registers on top
-    // of 256 + 20 spilled; always writing four partials costs 0.84 GB of traffic per B = 256 call.  tests/test_metrics_gpu.py compares
-    // B = 1, 50 and 130 (equal at the float32 precision of the returned score).
+    // Workgroup groups the SL_NSEG = 4 frame segments of the lag-product kernel are dealt to: more workgroups at small batches.  The batch-size
+    // class (B < 48 / < 128 / >= 128) only decides WHO sums a segment: every utterance always has four partials in lagp, each summed from
+    // zero in frame order, and siib_assemble_kernel adds them as (s0 + s1) + (s2 + s3) - so lagp, mu, C and S2 of an utterance are the same
+    // bytes in every class (tests/test_siib_stages_gpu.py compares them at B = 1, 48 and 128; see SL_NSEG).
     const int nseg = B >= 128 ? 1 : (B >= 48 ? 2 : 4);
     w.Xs = w.px = w.lagp = w.mu = w.S2 = w.qpart = nullptr;
     if (siib_lag_path()) {
@@ -1374,6 +1372,18 @@ extern "C" int nele_metric_siib_clean_sections(int B, int L, long long* out, int
         s.rows(w.lam, w.U);
         s.half_rows(w.mu);                                                        // the clean half of [2][420]
         s.nested_elems(w.eigws, nele_eigh_flags_field(B, SB_D));                  // the eigensolver's repair flag of each utterance
+    });
+}
+
+// Diagnostic (tests/test_siib_stages_gpu.py through metrics.siib_stages): the buffers of the lag path behind the clean front end, as
+// per-utterance byte ranges in the convention above.  C is only meaningful between phase 1 and phase 2 (the eigensolver destroys it).
+extern "C" int nele_metric_siib_sections(int B, int L, long long* out, int max_sections) {
+    NELE_CHECK_ARG(B > 0 && out, "nele_metric_siib_sections: bad arguments");
+    if (!siib_lag_path()) return nele_set_error(NELE_ERR_UNSUPPORTED, "nele_metric_siib_sections: lag-product path only");
+    SiibWs w;
+    const WsArena a = siib_layout(B, L, w, nullptr);
+    return ws_sections("nele_metric_siib_sections", a, B, out, max_sections, [&](WsSections& s) {
+        s.rows(w.info, w.rowstat, w.XL, w.mu, w.lagp, w.C, w.S2, w.lam, w.U, w.qpart);
     });
 }
 

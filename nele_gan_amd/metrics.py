@@ -330,6 +330,62 @@ def siib_clean_stages(x, lengths=None):
     return out
 
 
+def siib_stages(x, y, lengths=None, phase2=True):
+    """Diagnostic: nele_metric_siib_var in two calls (phase 1, then phase 2) on a workspace of its own (every byte 0xFF before the first call:
+    what a kernel does not write reads as NaN / -1) -> dict of per-row numpy arrays, read through nele_metric_siib_sections.  Copied out
+    after phase 1 (C is destroyed by the eigensolver and can only be read here), with na = info[b, 2] active frames, ncols = na - 14 stacked
+    frames, signal 0 = clean x, 1 = degraded y, stacked row a = 28 k + j (k-th of 15 consecutive frames, band j):
+      'info1' [B, 4] int = (M clamped to 40, frames of the tiled signal, na, status) as phase 1 leaves it.
+      'rowstat'[b] [2, 28, 2] float64: per (signal, band) the minimum BEFORE masking and the mean AFTER masking.
+      'XL'[b] [2, 28, na] float64: masked log band energies of the active frames of x then y (columns = the CLEAN signal's active list), row
+          mean not yet removed: the consumers subtract rowstat[.., 1] on the fly, a_j[s] = XL[sig, j, s] - rowstat[sig, j, 1].
+      'mu'[b] [2, 420] float64: window means mean_{t < ncols} a_j[t + k] of the stacked rows.
+      'lagp'[b] [3, 4, 29, 28, 28] float64: [pair, frame segment, lag slot, j1, j2] partial sums over the segment's frames s of
+          a_j1[s] b_j2[s + D] (all s with both indices in [0, na)); pair 0 = (x, x), 1 = (y, y), 2 = (x, y).  Slot D + 14 holds lag D; pairs 0
+          and 1 fill slots 14 .. 28 only (slots 0 .. 13 stay 0xFF).  Segment seg covers frames [seg per, min(na, (seg + 1) per)) with
+          per = ceil(ceil(na / 4) / g) g, g = 45 for pairs 0, 1 and 58 for pair 2; an empty segment holds zeros.  The lag product is
+          (seg0 + seg1) + (seg2 + seg3).
+      'C'[b] [420, 420] float64: Sxx / (ncols - 1), full, exactly symmetric.
+      'S2'[b] [2, 420, 420] float64: Syy then (Sxy + Sxy^T) / 2, unscaled, UPPER triangle (row <= column) only: the strict lower triangle
+          is never written (0xFF) and never read.
+    Copied out after phase 2 on the same workspace:
+      'lam'[b] [420] float64 ascending; 'U'[b] [420, 420] float64, ROW k = eigenvector k, and 'qpart'[b] [420, 14] float64 (7 column-tile
+          partials of u_k^T Syy u_k, then 7 of u_k^T sym(Sxy) u_k) are meaningful for the KEPT components lam[k] > 1e-10 lam[419] only: in a
+          64-row tile without a kept component U is zero and qpart stays 0xFF (NaN); the cut rows of a partly kept tile are unspecified.
+      'raw' [B] float32 score, 'info' [B, 4] int as the call returns it.
+    phase2=False stops after phase 1 (no eigensolver): the dict then holds the phase-1 buffers only."""
+    sp = SiibSplit(x, y, lengths=lengths, owner={})
+    B, L = sp.x.shape
+    sp.ws.fill_(255)
+    buf = (c_longlong * 30)()
+    n = _lib.lib.nele_metric_siib_sections(B, L, buf, 10)
+    if n != 10:
+        _lib.check(n, 'nele_metric_siib_sections')
+    sec = [(int(buf[3 * k]), int(buf[3 * k + 1]), int(buf[3 * k + 2])) for k in range(10)]
+    sp.front()
+    info1, rowstat, XL, mu, lagp, C, S2 = _section_rows(sp.ws, sec[:7], B)
+    info1 = info1.view(np.int32).copy()
+    out = {'info1': info1}
+    out.update({k: [] for k in ('rowstat', 'XL', 'mu', 'lagp', 'C', 'S2')})
+    if phase2:
+        sp.back()
+        lam, U, qpart = _section_rows(sp.ws, sec[7:], B)
+        out.update({'info': sp.info.cpu().numpy(), 'raw': sp.raw.cpu().numpy(), 'lam': [], 'U': [], 'qpart': []})
+    for b in range(B):
+        na = max(int(info1[b, 2]), 0)
+        out['rowstat'].append(rowstat[b].view(np.float64).reshape(2, 28, 2).copy())
+        out['XL'].append(XL[b].view(np.float64).reshape(2, 28, -1)[:, :, :na].copy())
+        out['mu'].append(mu[b].view(np.float64).reshape(2, 420).copy())
+        out['lagp'].append(lagp[b].view(np.float64).reshape(3, 4, 29, 28, 28).copy())
+        out['C'].append(C[b].view(np.float64).reshape(420, 420).copy())
+        out['S2'].append(S2[b].view(np.float64).reshape(2, 420, 420).copy())
+        if phase2:
+            out['lam'].append(lam[b].view(np.float64).copy())
+            out['U'].append(U[b].view(np.float64).reshape(420, 420).copy())
+            out['qpart'].append(qpart[b].view(np.float64).reshape(420, 14).copy())
+    return out
+
+
 class _CleanSplit:
     """The clean-part protocol of SiibSplit, HaspiSplit and HasqiSplit.  A class names its CleanStateCache kind (its workspaces are
     KIND_split and, for a sub-batch, KIND_split_sub) and supplies, with whatever per-call arguments its clean_part() takes:

@@ -17,26 +17,8 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
 HERE = os.path.dirname(__file__)
 
-LENS = (64000, 63871, 9600, 64001, 40000)
-SPARSE = 3            # row of the sparse utterance
-
-
-def ragged_batch():
-    """Five utterances in one padded batch: frame-periodic (64 000), aperiodic (63 871), a short one at the largest replication factor
-    (9 600: M = 40, status bit 1), a sparse one, and 40 000.
-    The sparse one has fewer active frames than one 58-frame chunk of the old kernel: four non-zero samples in digital silence.  The
-    replication factor follows the ACTIVE duration, so such an utterance is tiled 40 times (the cap), and it stays under 58 frames only
-    while most copies give ONE active frame: 64 001 samples let the click drift by one sample per copy against the 200-sample frame
-    grid, from 20 samples before a frame start to 19 behind it - the second frame that covers it sees it under the first or last few
-    taps of its window, 40 dB down, except in the outermost copies.  y keeps its noise everywhere."""
-    from nele_gan_amd import synth
-    c, v = synth.batch(len(LENS), max(LENS), start=310)
-    c[SPARSE] = 0.0
-    c[SPARSE, 6380:6384] = np.float32([0.5, -0.35, 0.2, -0.1])
-    y = (0.8 * c + v).astype(np.float32)
-    for b, n in enumerate(LENS):
-        c[b, n:], y[b, n:] = 0.0, 0.0
-    return c, y
+# the batch lives in the plain case module (the stage tests' CPU premises use it too)
+from siib_cases import RAGGED_LENS as LENS, SPARSE, ragged_batch  # noqa: E402,F401
 
 
 _CHILD = r'''
