@@ -1,5 +1,5 @@
 """ctypes binding of libnele_hip.so (the C ABI of include/nele_hip.h and, for the entry points added after its fixed set,
-include/nele_hip_ext.h, include/nele_hip_res.h and include/nele_hip_track.h: one header per feature).
+include/nele_hip_ext.h).
 
 The HIP library IS the product path: if it is missing or fails to load this module raises; there
 is no CPU or eager-PyTorch fallback anywhere in the package.
@@ -9,10 +9,10 @@ import os
 
 import torch
 
-from . import _abi, _abi_ext, _abi_res, _abi_track
+from . import _abi, _abi_ext
 
-FUNCS = dict(_abi.FUNCS, **_abi_ext.FUNCS, **_abi_res.FUNCS, **_abi_track.FUNCS)          # name -> (restype, argtypes) of the four headers
-CONSTS = dict(_abi.CONSTS, **_abi_ext.CONSTS, **_abi_res.CONSTS, **_abi_track.CONSTS)
+FUNCS = dict(_abi.FUNCS, **_abi_ext.FUNCS)          # name -> (restype, argtypes) of the two headers
+CONSTS = dict(_abi.CONSTS, **_abi_ext.CONSTS)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('NELE_LIB') or os.path.join(_HERE, 'libnele_hip.so')     # NELE_LIB: another build of the same ABI (A/B measurements)
@@ -41,11 +41,11 @@ lib = _load()
 
 
 def _bind():
-    """Sets argtypes and restype of every entry point from _abi.FUNCS, _abi_ext.FUNCS, _abi_res.FUNCS and _abi_track.FUNCS (generated from
-    include/nele_hip.h, nele_hip_ext.h, nele_hip_res.h and nele_hip_track.h by tools/gen_abi.py) -> name -> argtypes."""
+    """Sets argtypes and restype of every entry point from _abi.FUNCS and _abi_ext.FUNCS (generated from include/nele_hip.h and
+    nele_hip_ext.h by tools/gen_abi.py) -> name -> argtypes."""
     missing = sorted(n for n in FUNCS if not hasattr(lib, n))
     if missing:
-        raise ImportError("nele_gan_amd: %s does not export %s (declared in include/nele_hip.h, nele_hip_ext.h, nele_hip_res.h or nele_hip_track.h) -- rebuild it with "
+        raise ImportError("nele_gan_amd: %s does not export %s (declared in include/nele_hip.h or nele_hip_ext.h) -- rebuild it with "
                           "`python -c 'import __graft_entry__ as g; g.build()'`" % (LIB_PATH, ', '.join(missing)))
     sigs = {}
     for name, (restype, argtypes) in FUNCS.items():

@@ -6,6 +6,8 @@ import torch
 
 from ._lib import norm_dev
 
+HOP = 256                                                  # samples per hop of every hop-wise slot class
+
 
 def to_dev(t, device):
     """host tensor -> device through pinned memory, without blocking the host"""
@@ -71,3 +73,28 @@ class SlotState:
 
     def _dev_rows(self, slots):
         return dev_rows(slots, self.device)
+
+    def _out(self, out, shape, dtype=torch.float32, what='out'):
+        """the caller's buffer once it has that shape and dtype, or a fresh one on the device"""
+        if out is None:
+            return torch.empty(shape, dtype=dtype, device=self.device)
+        if tuple(out.shape) != shape or out.dtype != dtype:
+            raise ValueError("%s.process: %s must be %s %s" % (type(self).__name__, what, str(dtype).split('.')[-1], shape))
+        return out
+
+    def _hop_args(self, a, b, names, active, out, what='out'):
+        """What every hop-wise process() does with its arguments: a, b [S, nh * 256] float32 (host, pinned host or device; ``names`` are
+        theirs in the messages), active a host bool sequence [S] or None, out a float32 buffer of that shape or None -> (shape, nh, a
+        and b on the device, the host mask or None, its bytes on the device or None, the checked or fresh output)."""
+        who = type(self).__name__
+        shape = tuple(np.shape(a))
+        if len(shape) != 2 or shape[0] != self.S or shape[1] % HOP or shape[1] == 0:
+            raise ValueError("%s.process: %s must be [%d, nh * 256]" % (who, names[0], self.S))
+        a = self._dev_f32(a, shape, names[0])
+        b = self._dev_f32(b, shape, names[1])
+        act = None if active is None else self._flags(active, "%s: active must hold one flag per stream" % who)
+        return shape, shape[1] // HOP, a, b, act, None if act is None else self._dev_bytes(act), self._out(out, shape, what=what)
+
+    def _count(self, act, nh):
+        """the host counter of the slots a call ran in"""
+        self.hops[slice(None) if act is None else act] += nh

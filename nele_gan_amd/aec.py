@@ -46,9 +46,6 @@ class EchoCanceller(SlotState):
         self._alloc(device, _lib.lib.nele_aec_state_bytes(self.S, self.P))
         call('nele_aec_init', ptr(self.state), c_longlong(self.nbytes), self.S, self.P, stream())
 
-    def _mask(self, flags, name):
-        return self._flags(flags, "EchoCanceller: %s must hold one flag per stream" % name)
-
     # ---- streaming
     def process(self, mic, played, active=None, adapt=None, want_echo=False, out=None):
         """mic, played [streams, nh * 256] float32 (host, pinned host or device) -> residual [streams, nh * 256] on the device: mic minus
@@ -58,23 +55,13 @@ class EchoCanceller(SlotState):
         cancel with the filter they have and do not move it.  out (beyond RealtimeEnhancer's signature): a residual buffer, or
         (residual, echo), on the device to write into - the way to keep an inactive slot's columns; without it the outputs are fresh
         tensors and an inactive slot's columns undefined.  Never blocks the host."""
-        shape = tuple(np.shape(mic))
-        if len(shape) != 2 or shape[0] != self.S or shape[1] % HOP or shape[1] == 0:
-            raise ValueError("EchoCanceller.process: mic must be [%d, nh * 256]" % self.S)
-        nh = shape[1] // HOP
-        d = self._dev_f32(mic, shape, 'mic')
-        x = self._dev_f32(played, shape, 'played')
-        act = None if active is None else self._mask(active, 'active')
-        ada = None if adapt is None else self._dev_bytes(self._mask(adapt, 'adapt'))
         res, echo = (out if isinstance(out, (tuple, list)) else (out, None)) if out is not None else (None, None)
-        res = torch.empty(shape, dtype=torch.float32, device=self.device) if res is None else res
-        echo = (torch.empty(shape, dtype=torch.float32, device=self.device) if echo is None else echo) if want_echo else None
-        for o in (res, echo):
-            if o is not None and (tuple(o.shape) != shape or o.dtype != torch.float32):
-                raise ValueError("EchoCanceller.process: out buffers must be float32 %s" % (shape,))
-        call('nele_aec_hop', ptr(self.state), c_longlong(self.nbytes), self.S, self.P, ptr(d), ptr(x), ptr(None if act is None else self._dev_bytes(act)),
-             ptr(ada), nh, self.mu, self.gamma, self.delta, ptr(res), ptr(echo), stream())
-        self.hops[slice(None) if act is None else act] += nh
+        shape, nh, d, x, act, flags, res = self._hop_args(mic, played, ('mic', 'played'), active, res, what='out buffers')
+        ada = None if adapt is None else self._dev_bytes(self._flags(adapt, "EchoCanceller: adapt must hold one flag per stream"))
+        echo = self._out(echo, shape, what='out buffers') if want_echo else None
+        call('nele_aec_hop', ptr(self.state), c_longlong(self.nbytes), self.S, self.P, ptr(d), ptr(x), ptr(flags), ptr(ada), nh, self.mu, self.gamma,
+             self.delta, ptr(res), ptr(echo), stream())
+        self._count(act, nh)
         return (res, echo) if want_echo else res
 
     def echo_path(self, slots=None):

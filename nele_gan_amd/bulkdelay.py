@@ -4,7 +4,8 @@ delay per stream slot in whole 256-sample hops - SCOT-weighted cross-spectra of 
 the GPU, without a host read-back - and hands `played` on late by it; ``AlignedEchoCanceller`` puts it in front of an
 ``EchoCanceller``, which then needs partitions for the room's tail plus two blocks only.  The kernels are in libnele_hip.so
 (csrc/bulkdelay.hip, the ``nele_bulk_*`` entry points of include/nele_hip_ext.h; the arithmetic is DESIGN.md section 16).  This module
-owns memory and bookkeeping only; there is no arithmetic in torch.
+owns memory and bookkeeping only; there is no arithmetic in torch.  nele_gan_amd/bulktrack.py builds the pair that follows a delay which
+moves after the lock on these two classes.
 
     bulk = BulkDelay(streams=256, blocks=32)                    # delays up to 32 * 256 - 1 samples (512 ms)
     aligned = bulk.process(mic_hops, played_hops)               # [256, nh * 256]: zeros while a slot searches, then `played` delayed
@@ -18,9 +19,8 @@ import torch
 
 from . import _lib
 from ._lib import c_longlong, call, ptr, stream
-from ._slots import SlotState, to_dev
+from ._slots import HOP, SlotState, to_dev
 
-HOP = 256
 MAX_BLOCKS = _lib.CONSTS['NELE_BULK_MAX_BLOCKS']
 
 
@@ -28,17 +28,28 @@ class BulkDelay(SlotState):
     """B independent delay searches.  blocks: Q in 2 .. 64, the search covers main-tap delays up to 256 Q - 1 samples; lam (0 < lam < 1):
     the decay per hop of the cross-spectrum sums; a slot locks once one block has held (Q - 1) times its energy >= ratio (> 1) times the
     sum of the others' for hold (>= 1) hops in a row, at that block less one."""
+    _ABI = 'nele_bulk'                                     # the entry points are _ABI + '_init', '_hop', ...
 
     def __init__(self, streams, blocks=32, lam=0.99, ratio=8.0, hold=16, device='cuda'):
-        super().__init__(streams)
+        self._settings(streams, blocks, lam, ratio, hold)
+        self._lay_out(device)
+
+    def _settings(self, streams, blocks, lam, ratio, hold):
+        SlotState.__init__(self, streams)
+        who = type(self).__name__
         self.Q = int(blocks)
         if not 2 <= self.Q <= MAX_BLOCKS:
-            raise ValueError("BulkDelay: blocks must be in 2 .. %d (got %d)" % (MAX_BLOCKS, self.Q))
+            raise ValueError("%s: blocks must be in 2 .. %d (got %d)" % (who, MAX_BLOCKS, self.Q))
         self.lam, self.ratio, self.hold = float(lam), float(ratio), int(hold)
         if not (0.0 < self.lam < 1.0) or not (1.0 < self.ratio < float('inf')) or self.hold < 1:
-            raise ValueError("BulkDelay: needs 0 < lam < 1, ratio > 1 and hold >= 1 (got %g, %g, %d)" % (self.lam, self.ratio, self.hold))
-        self._alloc(device, _lib.lib.nele_bulk_state_bytes(self.S, self.Q))
-        call('nele_bulk_init', ptr(self.state), c_longlong(self.nbytes), self.S, self.Q, stream())
+            raise ValueError("%s: needs 0 < lam < 1, ratio > 1 and hold >= 1 (got %g, %g, %d)" % (who, self.lam, self.ratio, self.hold))
+
+    def _lay_out(self, device):
+        self._alloc(device, getattr(_lib.lib, self._ABI + '_state_bytes')(self.S, self.Q))
+        self._call('init')
+
+    def _call(self, what, *args):
+        call('%s_%s' % (self._ABI, what), ptr(self.state), c_longlong(self.nbytes), self.S, self.Q, *args, stream())
 
     # ---- streaming
     def process(self, mic, played, active=None, out=None):
@@ -47,20 +58,9 @@ class BulkDelay(SlotState):
         inactive slots are neither read nor changed and their output columns are left as they were.  out: a buffer on the device to
         write into - the way to keep an inactive slot's columns; without it the output is a fresh tensor and an inactive slot's columns
         undefined.  Never blocks the host."""
-        shape = tuple(np.shape(mic))
-        if len(shape) != 2 or shape[0] != self.S or shape[1] % HOP or shape[1] == 0:
-            raise ValueError("BulkDelay.process: mic must be [%d, nh * 256]" % self.S)
-        nh = shape[1] // HOP
-        d = self._dev_f32(mic, shape, 'mic')
-        x = self._dev_f32(played, shape, 'played')
-        act = None if active is None else self._flags(active, "BulkDelay: active must hold one flag per stream")
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=self.device)
-        elif tuple(out.shape) != shape or out.dtype != torch.float32:
-            raise ValueError("BulkDelay.process: out must be float32 %s" % (shape,))
-        call('nele_bulk_hop', ptr(self.state), c_longlong(self.nbytes), self.S, self.Q, ptr(d), ptr(x),
-             ptr(None if act is None else self._dev_bytes(act)), nh, self.lam, self.ratio, self.hold, ptr(out), None, stream())
-        self.hops[slice(None) if act is None else act] += nh
+        _, nh, d, x, act, flags, out = self._hop_args(mic, played, ('mic', 'played'), active, out)
+        self._call('hop', ptr(d), ptr(x), ptr(flags), nh, self.lam, self.ratio, self.hold, ptr(out), None)
+        self._count(act, nh)
         return out
 
     def status(self):
@@ -70,33 +70,34 @@ class BulkDelay(SlotState):
               'hops_searched': torch.empty((self.S,), dtype=torch.int32, device=self.device),
               'energies': torch.empty((self.S, self.Q), dtype=torch.float64, device=self.device),
               'conf': torch.empty((self.S,), dtype=torch.float64, device=self.device)}
-        call('nele_bulk_status', ptr(self.state), c_longlong(self.nbytes), self.S, self.Q, ptr(st['delay']), ptr(st['hops_searched']),
-             ptr(st['energies']), ptr(st['conf']), stream())
+        self._call('status', ptr(st['delay']), ptr(st['hops_searched']), ptr(st['energies']), ptr(st['conf']))
         return st
 
     def delays(self):
         """-> int32 [streams] on the device: each slot's delay in hops, -1 while it searches"""
         d = torch.empty((self.S,), dtype=torch.int32, device=self.device)
-        call('nele_bulk_status', ptr(self.state), c_longlong(self.nbytes), self.S, self.Q, ptr(d), None, None, None, stream())
+        self._call('status', ptr(d), None, None, None)
         return d
 
     def set_delay(self, slots, hops):
-        """Lock the given slots at delays the integrator knows: hops, one int in 0 .. blocks - 1 for all of them or one per slot.  No
-        search runs in them afterwards; their delay lines are kept."""
+        """Lock the given slots at delays the integrator knows: hops, one int in 0 .. blocks - 1 for all of them or one per slot.  Their
+        delay lines are kept.  ``BulkDelay``: no search runs in them afterwards.  ``TrackingBulkDelay``: their background search starts
+        from a cleared state; the counters are kept."""
         slots = np.asarray(slots, dtype=np.int64).reshape(-1)
         h = np.broadcast_to(np.asarray(hops, dtype=np.int64).reshape(-1), slots.shape) if np.size(hops) in (1, slots.size) else None
         if h is None or (h < 0).any() or (h >= self.Q).any():
-            raise ValueError("BulkDelay.set_delay: hops must be one value, or one per slot, in 0 .. %d" % (self.Q - 1))
+            raise ValueError("%s.set_delay: hops must be one value, or one per slot, in 0 .. %d" % (type(self).__name__, self.Q - 1))
         m = self._slots_mask(slots)
         full = np.zeros(self.S, dtype=np.int32)
         full[slots] = h
         flags, delays = self._dev_bytes(m), to_dev(torch.from_numpy(full), self.device)     # both alive until the call has been enqueued
-        call('nele_bulk_set_delay', ptr(self.state), c_longlong(self.nbytes), self.S, self.Q, ptr(flags), ptr(delays), stream())
+        self._call('set_delay', ptr(flags), ptr(delays))
 
     def reset(self, slots):
-        """Restart the given slots (an empty delay line, the search from its beginning); the other slots are not touched."""
+        """Restart the given slots (an empty delay line, the search from its beginning, a tracker's counters zero); the other slots are
+        not touched."""
         m = self._slots_mask(slots)
-        call('nele_bulk_reset', ptr(self.state), c_longlong(self.nbytes), self.S, self.Q, ptr(self._dev_bytes(m)), stream())
+        self._call('reset', ptr(self._dev_bytes(m)))
         self.hops[m] = 0
 
 
@@ -105,15 +106,19 @@ class AlignedEchoCanceller:
     searches the canceller is given zeros to cancel: its residual is the microphone and its weights stay where they are, so nothing
     has to be reset when the lock comes.  Stands wherever an EchoCanceller does (``EchoCancellingEnhancer``,
     ``RateAdaptedEnhancer``)."""
+    _BULK = 'delay search'                                 # what the messages call the first stage
 
     def __init__(self, bulk, aec):
         if bulk.S != aec.S:
-            raise ValueError("AlignedEchoCanceller: the delay search has %d streams, the canceller %d" % (bulk.S, aec.S))
+            raise ValueError("%s: the %s has %d streams, the canceller %d" % (type(self).__name__, self._BULK, bulk.S, aec.S))
         self.bulk, self.aec, self.S, self.device, self.P = bulk, aec, aec.S, aec.device, aec.P
+
+    def _aligned(self, mic, played, active):
+        return self.bulk.process(mic, played, active=active)
 
     def process(self, mic, played, active=None, adapt=None, want_echo=False, out=None):
         """EchoCanceller.process on `played` delayed by what the search has found (zeros until then)"""
-        return self.aec.process(mic, self.bulk.process(mic, played, active=active), active=active, adapt=adapt, want_echo=want_echo, out=out)
+        return self.aec.process(mic, self._aligned(mic, played, active), active=active, adapt=adapt, want_echo=want_echo, out=out)
 
     def echo_path(self, slots=None):
         """EchoCanceller.echo_path: the path from the ALIGNED `played` to the microphone"""

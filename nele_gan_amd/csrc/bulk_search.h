@@ -1,5 +1,5 @@
-// The bulk-delay search of DESIGN.md section 16, step 2, as csrc/bulkdelay.hip (nele_bulk_hop) and csrc/bulktrack.hip (nele_track_hop)
-// both run it: one definition, so that a tracker's background search and a first search are the same operations in the same order.
+// The bulk-delay search of DESIGN.md section 16, step 2, as both modes of csrc/bulkdelay.hip's hop kernel (nele_bulk_hop, nele_track_hop)
+// run it: one definition, so that a tracker's background search and a first search are the same operations in the same order.
 // For one workgroup of 256 threads that owns one stream slot.  While a slot searches: wave 0 takes ONE complex transform for the two
 // real ones ([x_prev, x] + i [0, d]); thread t owns slot t of S_d, S_x and D'; then one wave per pair of blocks (q, q + 1) updates C_q,
 // C_q+1 (16-byte accesses, 64 consecutive slots per instruction) and, from hop Q on, takes their two r_q from one Hermitian-packed

@@ -14,7 +14,7 @@
 #include "common.h"
 #include "fft512.h"
 #include "slot_state.h"
-#include "../../include/nele_hip_res.h"
+#include "../../include/nele_hip_ext.h"
 
 namespace {
 

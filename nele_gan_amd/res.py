@@ -2,7 +2,7 @@
 stays small and some echo stays in its residual.  ``ResidualEchoSuppressor`` is the second stage, a spectral post-filter per stream slot
 driven by the canceller's own echo estimate: it removes the part of the residual's power that is coherent with that estimate, so that
 the spectrum ``RealtimeEnhancer`` reads as `noise` approaches the noise's.  256-sample hops, sqrt-Hann 512-sample frames, float64
-transforms, in libnele_hip.so (csrc/res.hip, the ``nele_res_*`` entry points of include/nele_hip_res.h; the arithmetic is DESIGN.md
+transforms, in libnele_hip.so (csrc/res.hip, the ``nele_res_*`` entry points of include/nele_hip_ext.h; the arithmetic is DESIGN.md
 section 17).  This module owns memory and bookkeeping only; there is no arithmetic in torch.
 
     res = ResidualEchoSuppressor(streams=256)
@@ -44,24 +44,12 @@ class ResidualEchoSuppressor(SlotState):
         [streams] or None (all): inactive slots are neither read nor changed and their output columns are left as they were.  out: a
         buffer, or (buffer, gains buffer), on the device to write into - the way to keep an inactive slot's columns; without it the
         outputs are fresh tensors and an inactive slot's columns undefined.  Never blocks the host."""
-        shape = tuple(np.shape(residual))
-        if len(shape) != 2 or shape[0] != self.S or shape[1] % HOP or shape[1] == 0:
-            raise ValueError("ResidualEchoSuppressor.process: residual must be [%d, nh * 256]" % self.S)
-        nh = shape[1] // HOP
-        e = self._dev_f32(residual, shape, 'residual')
-        y = self._dev_f32(echo, shape, 'echo')
-        act = None if active is None else self._flags(active, "ResidualEchoSuppressor: active must hold one flag per stream")
         o, g = (out if isinstance(out, (tuple, list)) else (out, None)) if out is not None else (None, None)
-        o = torch.empty(shape, dtype=torch.float32, device=self.device) if o is None else o
-        if tuple(o.shape) != shape or o.dtype != torch.float32:
-            raise ValueError("ResidualEchoSuppressor.process: out must be float32 %s" % (shape,))
-        gshape = (self.S, nh, NBINS)
-        g = (torch.empty(gshape, dtype=torch.float64, device=self.device) if g is None else g) if want_gains else None
-        if g is not None and (tuple(g.shape) != gshape or g.dtype != torch.float64):
-            raise ValueError("ResidualEchoSuppressor.process: the gains buffer must be float64 %s" % (gshape,))
-        call('nele_res_hop', ptr(self.state), c_longlong(self.nbytes), self.S, ptr(e), ptr(y), ptr(None if act is None else self._dev_bytes(act)),
-             nh, self.beta, self.gmin, ptr(o), ptr(g), stream())
-        self.hops[slice(None) if act is None else act] += nh
+        _, nh, e, y, act, flags, o = self._hop_args(residual, echo, ('residual', 'echo'), active, o)
+        g = self._out(g, (self.S, nh, NBINS), torch.float64, 'the gains buffer') if want_gains else None
+        call('nele_res_hop', ptr(self.state), c_longlong(self.nbytes), self.S, ptr(e), ptr(y), ptr(flags), nh, self.beta, self.gmin, ptr(o), ptr(g),
+             stream())
+        self._count(act, nh)
         return (o, g) if want_gains else o
 
     def reset(self, slots):

@@ -341,6 +341,37 @@ def test_set_delay_shifts_played_by_whole_hops():
     assert st['hops_searched'].tolist() == [0, 0, 0, nh] and st['delay'].tolist() == [0, 1, Q - 1, -1] and not y[3].any()
 
 
+def test_a_locked_slot_runs_the_delay_line_and_leaves_its_search_state():
+    """B = 2, Q = 3, hold 8: slot 0 locks (where the reference does), slot 1 searches on beside it.  Through 8 more hops in two calls
+    slot 0's hops_searched, energies and conf are the bits they were at the lock, and so is its record apart from the delay line and
+    its head: a plain search that comes into a call locked neither loads nor stores search state.  aligned is `played` late by the
+    delay."""
+    B, Q, hold, extra = 2, 3, 8, 8
+    ss = [scen(Q, i) for i in range(B)]
+    r = BulkRef(Q, ratio=RATIO, hold=hold)
+    _, lock = r.run(ss[0]['mic'][:32 * HOP], ss[0]['played'][:32 * HOP])
+    assert lock is not None and r.delay >= 0
+    n = lock + 1
+    assert n + extra <= 40
+    mics, pls = [s['mic'][:(n + extra) * HOP] for s in ss], [s['played'][:(n + extra) * HOP] for s in ss]
+    bd = _bulk(B, Q, hold=hold)
+    y0 = feed(bd, [m[:n * HOP] for m in mics], [p[:n * HOP] for p in pls], 7)
+    at_lock, rec = _status(bd), _record(bd, 0).cpu().numpy()
+    assert at_lock['delay'].tolist() == [r.delay, -1] and at_lock['hops_searched'].tolist() == [n, n] and at_lock['energies'][0].all()
+    y1 = feed(bd, [m[n * HOP:] for m in mics], [p[n * HOP:] for p in pls], extra // 2)
+    st, rec1 = _status(bd), _record(bd, 0).cpu().numpy()
+    for k in ('delay', 'hops_searched', 'energies', 'conf'):
+        assert np.array_equal(st[k][0], at_lock[k][0]), k
+    assert st['delay'][1] == -1 and st['hops_searched'][1] == n + extra          # the neighbour went on searching in the same calls
+    line = slice(6144, 6144 + 4 * HOP * Q)                                       # DESIGN.md section 16's record: the delay line; int [1] is its head
+    assert np.array_equal(rec[:4], rec1[:4]) and np.array_equal(rec[8:line.start], rec1[8:line.start])
+    assert np.array_equal(rec[line.stop:], rec1[line.stop:]) and not np.array_equal(rec[line], rec1[line])
+    y = np.concatenate([y0, y1], axis=1)
+    want = np.concatenate([np.zeros(r.delay * HOP, np.float32), pls[0]])[:(n + extra) * HOP]
+    want[:lock * HOP] = 0.0
+    assert np.array_equal(y[0], want) and y[0].any() and not y[1].any()
+
+
 # ---------------------------------------------------------------------------------------------------------------------- the composite
 def _reduction(echo, y, a=164, b=264):
     sl = slice(a * HOP, b * HOP)

@@ -1,12 +1,8 @@
-"""CPU: the residual-echo suppressor's C ABI (nele_res_* of include/nele_hip_res.h: declared, exported by both libraries, bound,
-generated files current, state-size arithmetic, bad arguments rejected without a GPU), the numpy reference tests/res_ref.py on its own
+"""CPU: the residual-echo suppressor's C ABI (nele_res_* of include/nele_hip_ext.h: exported by both libraries, state-size arithmetic,
+bad arguments rejected without a GPU; the header and the binding as a whole: tests/test_abi_ext_cpu.py), the numpy reference tests/res_ref.py on its own
 against DESIGN.md section 17's pass-through and suppression figures, and SuppressedEchoCanceller's bookkeeping on stubs."""
 import ctypes
-import importlib.util
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -29,80 +25,11 @@ def _err():
     return _lib().nele_last_error_string()
 
 
-def _gen_abi():
-    spec = importlib.util.spec_from_file_location('gen_abi', os.path.join(ROOT, 'tools', 'gen_abi.py'))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def _res_header():
-    return open(os.path.join(ROOT, 'include', 'nele_hip_res.h')).read()
-
-
 # ------------------------------------------------------------------------------------------------------------------------ the C ABI
-def test_the_third_header_parses_and_says_what_it_is_for():
-    gen = _gen_abi()
-    src = _res_header()
-    protos = {p[0]: p for p in gen.prototypes(src)}
-    assert sorted(protos) == sorted(ENTRY_POINTS)
-    assert gen.consts(src) == {'NELE_RES_SMOOTH': 0.9, 'NELE_RES_EPS': 1e-10}
-    assert protos['nele_res_hop'][3] == ['state', 'state_bytes', 'max_streams', 'residual', 'echo', 'active', 'nh', 'beta', 'gmin', 'out', 'gains',
-                                         'stream']
-    opening = src[:src.index('#ifndef')]
-    assert 'nele_hip.h' in opening and 'nele_hip_ext.h' in opening and 'one header per feature' in opening
-    for other in ('nele_hip.h', 'nele_hip_ext.h'):
-        text = open(os.path.join(ROOT, 'include', other)).read()
-        assert not set(ENTRY_POINTS) & set(re.findall(r'\b(nele_[a-z0-9_]+)\s*\(', text)), other
-
-
 def test_both_libraries_export_the_entry_points():
     for name in ('libnele_hip.so', 'libnele_hip_ab.so'):
         lib = ctypes.CDLL(os.path.join(ROOT, 'nele_gan_amd', name))
         assert [s for s in ENTRY_POINTS if not hasattr(lib, s)] == [], name
-
-
-def test_the_binding_has_the_headers_arity_and_the_generated_files_are_current():
-    from nele_gan_amd import _abi, _abi_ext, _abi_res, _lib
-    src = re.sub(r'/\*.*?\*/', '', _res_header(), flags=re.S)
-    found = re.findall(r'^([a-z][a-z *]*?)\s*\b(nele_[A-Za-z0-9_]+)\s*\(([^)]*)\)\s*;', src, flags=re.M)      # read here, not by the generator
-    assert sorted(f[1] for f in found) == sorted(ENTRY_POINTS) == sorted(_abi_res.FUNCS)
-    restypes = {'int': ctypes.c_int, 'longlong': ctypes.c_longlong}
-    for ret, name, params in found:
-        fn = getattr(_lib.lib, name)
-        nargs = 0 if params.strip() == 'void' else params.count(',') + 1
-        assert len(fn.argtypes) == nargs == len(_abi_res.FUNCS[name][1]) == len(_lib._SIGS[name]), name
-        assert fn.restype is restypes[ret.replace(' ', '')], name
-    assert not set(_abi_res.FUNCS) & (set(_abi.FUNCS) | set(_abi_ext.FUNCS))
-    for k, v in _abi_res.CONSTS.items():
-        assert _lib.CONSTS[k] == v
-    assert subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'gen_abi.py'), '--check']).returncode == 0
-    for name in ENTRY_POINTS:                                                    # not plan operations: the operation ids do not move
-        assert _lib.lib.nele_plan_op_id(name.encode()) == -1
-
-
-def test_check_mode_covers_the_fourth_generated_file_and_skips_an_absent_header(tmp_path):
-    """gen_abi.py --check fails when _abi_res.py alone is stale; in a tree without include/nele_hip_res.h the tool neither asks for
-    _abi_res.py nor writes it (run on copies of the tree's inputs and outputs)"""
-    import shutil
-    rels = ('tools/gen_abi.py', 'include/nele_hip.h', 'include/nele_hip_ext.h', 'include/nele_hip_res.h', 'nele_gan_amd/_abi.py',
-            'nele_gan_amd/_abi_ext.py', 'nele_gan_amd/_abi_res.py', 'nele_gan_amd/csrc/plan_ops.inc')
-    for rel in rels:
-        os.makedirs(os.path.dirname(str(tmp_path / rel)), exist_ok=True)
-        shutil.copy(os.path.join(ROOT, rel), str(tmp_path / rel))
-    tool = str(tmp_path / 'tools' / 'gen_abi.py')
-    assert subprocess.run([sys.executable, tool, '--check']).returncode == 0
-    with open(str(tmp_path / 'nele_gan_amd' / '_abi_res.py'), 'a') as f:
-        f.write('# stale\n')
-    assert subprocess.run([sys.executable, tool, '--check']).returncode == 1
-    assert subprocess.run([sys.executable, tool], stdout=subprocess.DEVNULL).returncode == 0
-    for rel in rels[4:]:
-        assert open(str(tmp_path / rel)).read() == open(os.path.join(ROOT, rel)).read(), rel
-    os.remove(str(tmp_path / 'include' / 'nele_hip_res.h'))
-    os.remove(str(tmp_path / 'nele_gan_amd' / '_abi_res.py'))
-    assert subprocess.run([sys.executable, tool, '--check']).returncode == 0
-    assert subprocess.run([sys.executable, tool], stdout=subprocess.DEVNULL).returncode == 0
-    assert not os.path.exists(str(tmp_path / 'nele_gan_amd' / '_abi_res.py'))
 
 
 def test_state_bytes_are_a_header_plus_one_record_per_stream():

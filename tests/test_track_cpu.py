@@ -1,13 +1,10 @@
-"""CPU: the delay tracker's C ABI (nele_track_* of include/nele_hip_track.h: declared, exported by both libraries, bound, generated files
-current, state-size arithmetic, bad arguments rejected without a GPU), the Python classes' refusals, the numpy reference
+"""CPU: the delay tracker's C ABI (nele_track_* of include/nele_hip_ext.h: exported by both libraries, state-size arithmetic - the
+bulk-delay search's, record for record - bad arguments rejected without a GPU; the header and the binding as a whole:
+tests/test_abi_ext_cpu.py), the Python classes' refusals, the numpy reference
 tests/track_ref.py on its own against DESIGN.md section 18's table (jumps followed, nothing moved without one), TrackedEchoCanceller's
 bookkeeping on stubs, and the echo reduction of the reference chain behind a move with and without the canceller's restart."""
 import ctypes
-import importlib.util
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -32,82 +29,11 @@ def _err():
     return _lib().nele_last_error_string()
 
 
-def _gen_abi():
-    spec = importlib.util.spec_from_file_location('gen_abi', os.path.join(ROOT, 'tools', 'gen_abi.py'))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def _track_header():
-    return open(os.path.join(ROOT, 'include', 'nele_hip_track.h')).read()
-
-
 # ------------------------------------------------------------------------------------------------------------------------ the C ABI
-def test_the_fourth_header_parses_and_says_what_it_is_for():
-    gen = _gen_abi()
-    src = _track_header()
-    protos = {p[0]: p for p in gen.prototypes(src)}
-    assert sorted(protos) == sorted(ENTRY_POINTS)
-    consts = gen.consts(src)
-    assert consts['NELE_TRACK_INFO'] == 8 and sorted(v for k, v in consts.items() if k.startswith('NELE_TRACK_I_')) == list(range(8))
-    assert protos['nele_track_hop'][3] == ['state', 'state_bytes', 'max_streams', 'blocks', 'mic', 'played', 'active', 'nh', 'lambda', 'ratio',
-                                           'hold', 'patience', 'rest', 'aligned', 'moved', 'stream']
-    opening = src[:src.index('#ifndef')]
-    assert all(h in opening for h in ('nele_hip.h', 'nele_hip_ext.h', 'nele_hip_res.h')) and 'one header per feature' in opening
-    for other in ('nele_hip.h', 'nele_hip_ext.h', 'nele_hip_res.h'):
-        text = open(os.path.join(ROOT, 'include', other)).read()
-        assert not set(ENTRY_POINTS) & set(re.findall(r'\b(nele_[a-z0-9_]+)\s*\(', text)), other
-
-
 def test_both_libraries_export_the_entry_points():
     for name in ('libnele_hip.so', 'libnele_hip_ab.so'):
         lib = ctypes.CDLL(os.path.join(ROOT, 'nele_gan_amd', name))
         assert [s for s in ENTRY_POINTS if not hasattr(lib, s)] == [], name
-
-
-def test_the_binding_has_the_headers_arity_and_the_generated_files_are_current():
-    from nele_gan_amd import _abi, _abi_ext, _abi_res, _abi_track, _lib
-    src = re.sub(r'/\*.*?\*/', '', _track_header(), flags=re.S)
-    found = re.findall(r'^([a-z][a-z *]*?)\s*\b(nele_[A-Za-z0-9_]+)\s*\(([^)]*)\)\s*;', src, flags=re.M)      # read here, not by the generator
-    assert sorted(f[1] for f in found) == sorted(ENTRY_POINTS) == sorted(_abi_track.FUNCS)
-    restypes = {'int': ctypes.c_int, 'longlong': ctypes.c_longlong}
-    for ret, name, params in found:
-        fn = getattr(_lib.lib, name)
-        nargs = 0 if params.strip() == 'void' else params.count(',') + 1
-        assert len(fn.argtypes) == nargs == len(_abi_track.FUNCS[name][1]) == len(_lib._SIGS[name]), name
-        assert fn.restype is restypes[ret.replace(' ', '')], name
-    assert not set(_abi_track.FUNCS) & (set(_abi.FUNCS) | set(_abi_ext.FUNCS) | set(_abi_res.FUNCS))
-    for k, v in _abi_track.CONSTS.items():
-        assert _lib.CONSTS[k] == v
-    assert subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'gen_abi.py'), '--check']).returncode == 0
-    for name in ENTRY_POINTS:                                                    # not plan operations: the operation ids do not move
-        assert _lib.lib.nele_plan_op_id(name.encode()) == -1
-
-
-def test_check_mode_covers_the_fifth_generated_file_and_skips_an_absent_header(tmp_path):
-    """gen_abi.py --check fails when _abi_track.py alone is stale; in a tree without include/nele_hip_track.h the tool neither asks for
-    _abi_track.py nor writes it (run on copies of the tree's inputs and outputs)"""
-    import shutil
-    rels = ('tools/gen_abi.py', 'include/nele_hip.h', 'include/nele_hip_ext.h', 'include/nele_hip_res.h', 'include/nele_hip_track.h',
-            'nele_gan_amd/_abi.py', 'nele_gan_amd/_abi_ext.py', 'nele_gan_amd/_abi_res.py', 'nele_gan_amd/_abi_track.py',
-            'nele_gan_amd/csrc/plan_ops.inc')
-    for rel in rels:
-        os.makedirs(os.path.dirname(str(tmp_path / rel)), exist_ok=True)
-        shutil.copy(os.path.join(ROOT, rel), str(tmp_path / rel))
-    tool = str(tmp_path / 'tools' / 'gen_abi.py')
-    assert subprocess.run([sys.executable, tool, '--check']).returncode == 0
-    with open(str(tmp_path / 'nele_gan_amd' / '_abi_track.py'), 'a') as f:
-        f.write('# stale\n')
-    assert subprocess.run([sys.executable, tool, '--check']).returncode == 1
-    assert subprocess.run([sys.executable, tool], stdout=subprocess.DEVNULL).returncode == 0
-    for rel in rels[5:]:
-        assert open(str(tmp_path / rel)).read() == open(os.path.join(ROOT, rel)).read(), rel
-    os.remove(str(tmp_path / 'include' / 'nele_hip_track.h'))
-    os.remove(str(tmp_path / 'nele_gan_amd' / '_abi_track.py'))
-    assert subprocess.run([sys.executable, tool, '--check']).returncode == 0
-    assert subprocess.run([sys.executable, tool], stdout=subprocess.DEVNULL).returncode == 0
-    assert not os.path.exists(str(tmp_path / 'nele_gan_amd' / '_abi_track.py'))
 
 
 def test_state_bytes_are_a_header_plus_one_record_per_stream():
@@ -125,6 +51,15 @@ def test_state_bytes_are_a_header_plus_one_record_per_stream():
         assert lib.nele_track_state_bytes(B, Q) == -1
     for Q in (1, 65, -3):
         assert lib.nele_track_stream_record_bytes(Q) == -1
+
+
+def test_the_tracker_and_the_plain_search_share_one_record_layout():
+    """one layout for both sets of entry points: the sizes are what each has always returned, 6144 + 9216 Q bytes a record"""
+    lib = _lib()
+    for Q in range(2, 65):
+        assert lib.nele_track_stream_record_bytes(Q) == lib.nele_bulk_stream_record_bytes(Q) == 6144 + 9216 * Q
+        for B in (1, 3, 1 << 20):
+            assert lib.nele_track_state_bytes(B, Q) == lib.nele_bulk_state_bytes(B, Q) == 256 + B * (6144 + 9216 * Q)
 
 
 def test_bad_arguments_are_rejected_without_a_gpu():

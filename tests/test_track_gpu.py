@@ -1,4 +1,4 @@
-"""GPU: the delay tracker (nele_gan_amd/bulktrack.py, csrc/bulktrack.hip) against tests/track_ref.py - the numpy restatement of DESIGN.md
+"""GPU: the delay tracker (nele_gan_amd/bulktrack.py, the tracking mode of csrc/bulkdelay.hip) against tests/track_ref.py - the numpy restatement of DESIGN.md
 section 18 - through jumps of the bulk delay; its first search and its background searches against nele_bulk_hop (bitwise: they are
 the same code); its streaming contract (grouping, batch, slots, skipped calls, reset, set_delay: bitwise); rest and patience; and the
 composite with the echo canceller, alone and on the command line.
@@ -338,6 +338,36 @@ def test_reset_and_set_delay_touch_one_slot():
     assert np.array_equal(y[2], want) and not np.array_equal(y[2], y_[2])
     assert tuple(int(st[k][2]) for k in INTS) == (r.delay, r.hops, r.age, r.sleep, r.moves, r.confirms, r.gaveups, r.last_move)
     assert st['hops'][2] == HOPS
+
+
+def test_set_delay_keeps_a_plain_search_state_and_clears_a_trackers():
+    """the one place where the two modes of the shared kernels differ on purpose.  B = 2, Q = 3, two searching hops, set_delay([0], 1):
+    nele_bulk_set_delay writes the delay and nothing else (hops_searched is still 2, the record apart from that integer is unchanged);
+    nele_track_set_delay also clears the search (age 0, awake, a zero search state) and keeps the counters and the hop count"""
+    B, Q = 2, 3
+    ss = [scen(Q, i) for i in range(B)]
+    mic = torch.from_numpy(np.stack([s['mic'][:2 * HOP] for s in ss]))
+    played = torch.from_numpy(np.stack([s['played'][:2 * HOP] for s in ss]))
+    bd, tr = _bulk(B, Q), _track(B, Q)
+    bd.process(mic, played)
+    tr.process(mic, played)
+    before = {'bulk': _record(bd, 0).cpu().numpy(), 'track': _record(tr, 0).cpu().numpy(), 'st': _status(tr)}
+    assert before['st']['age'].tolist() == [2, 2] and np.array_equal(before['bulk'][:24], before['track'][:24]) and before['bulk'][256 + 512:].any()
+    bd.set_delay([0], 1)
+    tr.set_delay([0], 1)
+    st = {k: v.cpu().numpy() for k, v in bd.status().items()}
+    assert st['hops_searched'].tolist() == [2, 2] and st['delay'].tolist() == [1, -1]
+    rec = _record(bd, 0).cpu().numpy()
+    assert np.array_equal(rec[:20], before['bulk'][:20]) and np.array_equal(rec[24:], before['bulk'][24:])      # int [5] is the delay plus one
+    st = _status(tr)
+    assert (st['age'][0], st['sleep'][0], st['delay'][0], st['hops'][0]) == (0, 0, 1, 2)
+    for k in ('moves', 'confirms', 'gaveups', 'last_move'):
+        assert st[k][0] == before['st'][k][0], k
+    assert all(st[k][1] == before['st'][k][1] for k in INTS) and st['age'][1] == 2
+    rec = _record(tr, 0).cpu().numpy()
+    line = slice(6144, 6144 + 4 * HOP * Q)                                       # DESIGN.md section 16's record: the delay line is kept,
+    assert np.array_equal(rec[line], before['track'][line]) and rec[line].any()  # x_prev, S_d, S_x, the ring and C_q are zero
+    assert not rec[256 + 512:line.start].any() and not rec[line.stop:].any()
 
 
 # ------------------------------------------------------------------------------------------------------------------ rest and patience

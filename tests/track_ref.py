@@ -1,6 +1,6 @@
 """The delay tracker of DESIGN.md section 18 restated in numpy, one stream at a time: the delay line of section 16, and behind it
 section 16's search (tests/bulk_ref.py's BulkRef, used for its search state and step alone) started again from a cleared state after
-every lock, confirmation, move and give-up.  Written from that section, not from csrc/bulktrack.hip; tests/test_track_cpu.py checks it
+every lock, confirmation, move and give-up.  Written from that section, not from csrc/bulkdelay.hip; tests/test_track_cpu.py checks it
 on its own, tests/test_track_gpu.py holds the kernel to it."""
 import numpy as np
 

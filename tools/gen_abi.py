@@ -7,12 +7,7 @@
 and from include/nele_hip_ext.h (the entry points added after nele_hip.h's fixed set; same parser, same type map)
   nele_gan_amd/_abi_ext.py         FUNCS and CONSTS of that header, bound by _lib.py beside _abi.py's.  None of them is a plan operation:
                                    plan_ops.inc and the operation ids come from nele_hip.h alone.
-Each further header of FURTHER_HEADERS (one per feature added since) gives one more file of the same kind, bound by _lib.py beside the
-other two,
-  nele_gan_amd/_abi_res.py         FUNCS and CONSTS of include/nele_hip_res.h;
-  nele_gan_amd/_abi_track.py       FUNCS and CONSTS of include/nele_hip_track.h;
-a further header that is absent from the tool's own tree is skipped, with its output.
-Run after changing a header; tests/test_capi_symbols.py, tests/test_bulk_cpu.py, tests/test_res_cpu.py and tests/test_track_cpu.py check that all are current.
+Run after changing a header; tests/test_capi_symbols.py and tests/test_abi_ext_cpu.py check that all three are current.
     python tools/gen_abi.py            # rewrite the files
     python tools/gen_abi.py --check    # exit 1 when a committed file differs
 A code is the ctypes type's name without its 'c_'.  The map is fixed: a scalar type outside it stops the tool (never a default)."""
@@ -23,7 +18,6 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NOT_PLAN_OPS = ('nele_compute_band_E',)     # never in the table (the table's first generator skipped the capital); kept out so that the
                                              # operation ids of a built library stay as they are
-FURTHER_HEADERS = (('nele_hip_res.h', '_abi_res.py'), ('nele_hip_track.h', '_abi_track.py'))     # (header under include/, generated file under nele_gan_amd/)
 SCALARS = {'int': 'int', 'unsigned': 'uint', 'long long': 'longlong', 'unsigned long long': 'ulonglong', 'float': 'float',
            'double': 'double'}
 
@@ -141,13 +135,9 @@ if __name__ == '__main__':
     outputs = ((os.path.join(ROOT, 'nele_gan_amd', 'csrc', 'plan_ops.inc'), emit_plan_ops()),
                (os.path.join(ROOT, 'nele_gan_amd', '_abi.py'), emit_abi()),
                (os.path.join(ROOT, 'nele_gan_amd', '_abi_ext.py'), emit_abi('nele_hip_ext.h')))
-    outputs += tuple((os.path.join(ROOT, 'nele_gan_amd', out), emit_abi(header)) for header, out in FURTHER_HEADERS
-                     if os.path.exists(os.path.join(ROOT, 'include', header)))
     if '--check' in sys.argv:
         sys.exit(0 if all(os.path.exists(path) and open(path).read() == text for path, text in outputs) else 1)
     for path, text in outputs:
         open(path, 'w').write(text)
     print('wrote %s (%d operations), %s (%d entry points) and %s (%d entry points)'
           % (outputs[0][0], outputs[0][1].count('PLAN_OP('), outputs[1][0], len(funcs()), outputs[2][0], len(funcs(_header('nele_hip_ext.h')))))
-    for path, text in outputs[3:]:
-        print('wrote %s (%d entry points)' % (path, text.count("': ('")))
