@@ -11,12 +11,13 @@ is DESIGN.md section 14).  This module owns memory and bookkeeping only; there i
     loop = EchoCancellingEnhancer(RealtimeEnhancer(...), aec)  # closes the loop: what process() returns is what the loudspeaker plays
     out = loop.process(clean_hops, mic_hops)                   # during the next call's capture
 
-    python -m nele_gan_amd.aec --mic mic.wav --played far.wav --out residual.wav [--partitions 8] [--echo-path h.npy] [--bulk-blocks 32 [--bulk-track]]
-                               [--suppress [--res-beta 2.0] [--res-gmin 0.1]]
+    python -m nele_gan_amd.aec --mic mic.wav --played far.wav --out residual.wav [--partitions 8] [--echo-path h.npy] [--bulk-blocks 32 [--bulk-track]
+                               [--drift [--drift-ppm PPM]]] [--suppress [--res-beta 2.0] [--res-gmin 0.1]]
 
 A bulk delay (the device's playback and capture buffers) is found and taken out ahead of the canceller by nele_gan_amd/bulkdelay.py
 (``AlignedEchoCanceller``; --bulk-blocks on the command line), and followed when it moves later by nele_gan_amd/bulktrack.py
-(``TrackedEchoCanceller``; --bulk-track).  The echo the canceller leaves is suppressed behind it by
+(``TrackedEchoCanceller``; --bulk-track); clock drift between playback and capture is followed by nele_gan_amd/drift.py
+(``DriftTrackedEchoCanceller``; --drift).  The echo the canceller leaves is suppressed behind it by
 nele_gan_amd/res.py (``SuppressedEchoCanceller``; --suppress on the command line).
 """
 import numpy as np
@@ -155,7 +156,34 @@ class EchoCancellingEnhancer:
 
 
 # ------------------------------------------------------------------------------------------------------------------ command line
-def cancel_file(mic, played, partitions=8, mu=0.5, gamma=4.0, delta=1e-2, device='cuda', bulk_blocks=None, suppress=None, bulk_track=False):
+def _cancel_file_drift(d, x, L, aec, partitions, device, bulk_blocks, suppress, bulk_track, drift_ppm):
+    """cancel_file with drift: search, drift.DriftCompensator and canceller (drift.DriftTrackedEchoCanceller), hop by hop"""
+    from .bulkdelay import BulkDelay
+    from .bulktrack import TrackingBulkDelay
+    from .drift import DriftCompensator, DriftTrackedEchoCanceller
+    bulk = (TrackingBulkDelay if bulk_track else BulkDelay)(1, blocks=bulk_blocks, device=device)
+    comp = DriftCompensator(1, blocks=bulk_blocks, device=device)
+    if drift_ppm:
+        comp.set_rate([0], drift_ppm)
+    chain = DriftTrackedEchoCanceller(bulk, comp, aec)
+    if suppress is not None:
+        from .res import ResidualEchoSuppressor, SuppressedEchoCanceller
+        chain = SuppressedEchoCanceller(chain, ResidualEchoSuppressor(1, beta=suppress[0], gmin=suppress[1], device=device))
+    dd, xd = to_dev(torch.from_numpy(d), bulk.device), to_dev(torch.from_numpy(x), bulk.device)
+    res, events, last = [], [], -1
+    for k in range(d.shape[1] // HOP):
+        res.append(chain.process(dd[:, k * HOP:(k + 1) * HOP].contiguous(), xd[:, k * HOP:(k + 1) * HOP].contiguous()))
+        if bulk_track:
+            now = int(bulk.delays()[0].item())
+            if now != last:
+                events.append((k, now))
+                last = now
+    found = events if bulk_track else int(bulk.delays()[0].item())
+    return torch.cat(res, dim=1)[0, :L].cpu().numpy(), chain.echo_path()[0].cpu().numpy(), found, float(comp.status()['drift_ppm'][0].item())
+
+
+def cancel_file(mic, played, partitions=8, mu=0.5, gamma=4.0, delta=1e-2, device='cuda', bulk_blocks=None, suppress=None, bulk_track=False,
+                drift=False, drift_ppm=0.0):
     """mic, played: float32 arrays of one length L -> (residual [L] float32, echo path [partitions * 256] float64): the whole hops through
     one EchoCanceller call, the last L % 256 samples zero-padded to one more hop and cut again.  bulk_blocks: search that many blocks
     for a bulk delay and cancel against `played` delayed by it (bulkdelay.AlignedEchoCanceller); the return value gains a third
@@ -163,17 +191,24 @@ def cancel_file(mic, played, partitions=8, mu=0.5, gamma=4.0, delta=1e-2, device
     when it moves (bulktrack.TrackedEchoCanceller); the file then goes through hop by hop, the delay is read back after every hop, and
     the third element is the list of (hop, delay in hops) of the lock and of every move (empty: none found).  suppress: (beta, gmin)
     of a res.ResidualEchoSuppressor behind the canceller (res.SuppressedEchoCanceller): the residual is the suppressed one, one hop late as process() returns it - its first 256 samples
-    are the canceller's own residual and the file's last hop does not come out."""
+    are the canceller's own residual and the file's last hop does not come out.  drift (with bulk_blocks): a drift.DriftCompensator
+    between the search and the canceller follows the clock drift between `played` and `mic` (drift.DriftTrackedEchoCanceller); the file
+    goes through hop by hop and the return value gains a fourth element, the final drift estimate in ppm; drift_ppm: the estimate
+    it starts from."""
     mic = np.ascontiguousarray(mic, dtype=np.float32).reshape(-1)
     played = np.ascontiguousarray(played, dtype=np.float32).reshape(-1)
     if mic.shape != played.shape or mic.size == 0:
         raise ValueError("aec: --mic and --played must have one length (got %d and %d samples)" % (mic.size, played.size))
+    if drift and bulk_blocks is None:
+        raise ValueError("aec: drift needs bulk_blocks: the compensator stands on the whole-hop delay the search finds")
     L = mic.size
     nh = (L + HOP - 1) // HOP
     d = np.zeros((1, nh * HOP), dtype=np.float32)
     x = np.zeros((1, nh * HOP), dtype=np.float32)
     d[0, :L], x[0, :L] = mic, played
     aec = EchoCanceller(1, partitions=partitions, mu=mu, gamma=gamma, delta=delta, device=device)
+    if drift:
+        return _cancel_file_drift(d, x, L, aec, partitions, device, bulk_blocks, suppress, bulk_track, drift_ppm)
     if bulk_blocks is not None and bulk_track:
         from .bulktrack import TrackedEchoCanceller, TrackingBulkDelay
         bulk = TrackingBulkDelay(1, blocks=bulk_blocks, device=device)
@@ -215,6 +250,11 @@ def build_parser():
                          '(default: no search)')
     ap.add_argument('--bulk-track', action='store_true',
                     help='with --bulk-blocks: go on searching behind the lock and follow the delay when it moves (nele_gan_amd/bulktrack.py)')
+    ap.add_argument('--drift', action='store_true',
+                    help='with --bulk-blocks: follow the clock drift between --played and --mic ahead of the canceller (nele_gan_amd/drift.py) '
+                         'and print the final estimate')
+    ap.add_argument('--drift-ppm', type=float, default=None, metavar='PPM',
+                    help='with --drift: the estimate to start from, how fast the capture clock runs, within +-1000 (default 0)')
     ap.add_argument('--suppress', action='store_true',
                     help='suppress the echo the canceller leaves (nele_gan_amd/res.py); the output is then one 256-sample hop late')
     ap.add_argument('--res-beta', type=float, default=2.0, help='with --suppress: the over-subtraction factor, >= 0')
@@ -247,9 +287,16 @@ def main(argv=None):
         ap.error('needs --res-beta >= 0 and 0 < --res-gmin <= 1')
     if a.bulk_track and a.bulk_blocks is None:
         ap.error('--bulk-track needs --bulk-blocks')
+    if a.drift and a.bulk_blocks is None:
+        ap.error('--drift needs --bulk-blocks: the compensator stands on the whole-hop delay the search finds')
+    if a.drift_ppm is not None and not a.drift:
+        ap.error('--drift-ppm needs --drift (and --bulk-blocks)')
+    if a.drift_ppm is not None and not abs(a.drift_ppm) <= 1000.0:
+        ap.error('--drift-ppm must be within +-1000')
     suppress = (a.res_beta, a.res_gmin) if a.suppress else None
+    drift = {'drift': True, 'drift_ppm': a.drift_ppm or 0.0} if a.drift else {}
     res, h, *found = cancel_file(sig[0], sig[1], partitions=a.partitions, mu=a.mu, gamma=a.gamma, delta=a.delta, bulk_blocks=a.bulk_blocks,
-                                 suppress=suppress, bulk_track=a.bulk_track)
+                                 suppress=suppress, bulk_track=a.bulk_track, **drift)
     dataio.write_wav_pcm16(a.out, res)
     if a.echo_path:
         np.save(a.echo_path, h)
@@ -263,6 +310,8 @@ def main(argv=None):
     elif found:
         print('bulk delay: %s' % ('none found in %d blocks' % a.bulk_blocks if found[0] < 0 else
                                   '%d hops (%d ms) taken out ahead of the canceller' % (found[0], found[0] * HOP * 1000 // dataio.fs)))
+    if a.drift:
+        print('clock drift: %.1f ppm (how fast the capture clock runs against the playback clock) followed ahead of the canceller' % found[1])
     if a.suppress:
         print('residual echo suppressed (beta %g, gmin %g): the output is one hop (%d ms) late' % (a.res_beta, a.res_gmin, HOP * 1000 // dataio.fs))
     return 0
