@@ -5,7 +5,8 @@
  * as void*, status 0 / -1 .. -5 with nele_last_error_string(), fixed-order reductions).  tools/gen_abi.py generates
  * nele_gan_amd/_abi_ext2.py from this file as it generates _abi.py and _abi_ext.py from the other two; nele_gan_amd/_lib.py binds all
  * three.  None of these is a job-table operation.
- * So far: the real-time echo path's clock-drift compensator (nele_drift_*).
+ * The real-time echo path's clock-drift compensator (nele_drift_*): eight entry points, which tests/test_abi_ext2_cpu.py counts.  Later
+ * entry points go into include/nele_hip_ext3.h.
  */
 #ifndef NELE_HIP_EXT2_H
 #define NELE_HIP_EXT2_H

@@ -5,7 +5,7 @@
 #include "common.h"
 
 #define SLOT_MAX_STREAMS (1 << 20)
-#define SLOT_GEOM_HDR_BYTES 256        // a geometry header: up to four ints (what _init was given), zeros behind them
+#define SLOT_GEOM_HDR_BYTES 256        // a geometry header: up to eight ints (what _init was given), zeros behind them
 
 constexpr long long slot_al(long long x) { return (x + 255) / 256 * 256; }
 
@@ -27,9 +27,10 @@ int slot_state_check(const char* name, const void* state, long long state_bytes,
 }
 
 // csrc/slot_state.hip: zero the records (rec_bytes each, a multiple of 256, behind hdr_bytes) of the slots with slots[b] != 0 (null: all
-// S); nhdr in 1 .. 4: also write the geometry header hdr[0 .. nhdr) at the start of the state, zeros up to SLOT_GEOM_HDR_BYTES.
+// S); nhdr in 1 .. 8: also write the geometry header hdr[0 .. nhdr) at the start of the state, zeros up to SLOT_GEOM_HDR_BYTES.
+// first: the value of a reset record's first int (the scheduled converter's lead; every other module's records start with a zero).
 __attribute__((visibility("hidden"))) int slot_state_reset(const char* name, void* state, long long hdr_bytes, long long rec_bytes, int S,
-                                                           const unsigned char* slots, int nhdr, const int* hdr, void* stream);
+                                                           const unsigned char* slots, int nhdr, const int* hdr, void* stream, int first = 0);
 
 // is this the state _init laid out for these parameters?  (a kernel that finds it is not touches nothing)
 __device__ __forceinline__ bool slot_hdr_matches(const unsigned char* state, int v0, int v1) {
@@ -39,4 +40,8 @@ __device__ __forceinline__ bool slot_hdr_matches(const unsigned char* state, int
 __device__ __forceinline__ bool slot_hdr_matches(const unsigned char* state, int v0, int v1, int v2, int v3) {
     const int* hdr = reinterpret_cast<const int*>(state);
     return hdr[0] == v0 && hdr[1] == v1 && hdr[2] == v2 && hdr[3] == v3;
+}
+__device__ __forceinline__ bool slot_hdr_matches(const unsigned char* state, int v0, int v1, int v2, int v3, int v4, int v5, int v6) {
+    const int* hdr = reinterpret_cast<const int*>(state);
+    return slot_hdr_matches(state, v0, v1, v2, v3) && hdr[4] == v4 && hdr[5] == v5 && hdr[6] == v6;
 }

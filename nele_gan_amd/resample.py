@@ -9,6 +9,9 @@ files at their own rate and asserts 16 kHz (dataloader.py:34-37): this is an add
                                                                        and DIR/resample_manifest.csv
     StreamResampler(streams, sr_in, sr_out, quality='high').process(x_hops) -> y_hops             live streams hop by hop between 16 kHz and
                                                                        8 .. 96 kHz (csrc/resample_stream.hip)
+    ScheduledStreamResampler(streams, sr_in, sr_out, quality='high').process(x) -> y              the same for every rate, 44.1 kHz and its
+                                                                       family among them, on a hop schedule (csrc/resample_sched.hip,
+                                                                       DESIGN.md section 20)
 
 ``quality``: 'high' = (zeros 32, Kaiser beta 12.0): stop band at most -119 dB from 1.15 x the new Nyquist frequency, pass-band ripple below
 0.001 dB up to 0.85 x; 'scipy' = (10, 5.0): resample_poly's own default (-43 dB); or a (zeros, beta) pair.  The taps are designed on the
@@ -217,6 +220,140 @@ class StreamResampler(SlotState):
         call('nele_resample_stream_reset', ptr(self.state), c_longlong(self.nbytes), self.S, self.up, self.down, self.K, ptr(self._dev_bytes(m)),
              stream())
         self.hops[m] = 0
+
+
+def sched_plan(sr_in, sr_out, quality='high'):
+    """The scheduled stream converter sr_in -> sr_out of DESIGN.md section 20 -> dict(up, down, zeros, beta, to16k, K, delay, L0, E, H,
+    rnum, period, hop_min, hop_max), from the library's host function nele_sched_stream_plan: no GPU call.  One side must be 16 000 Hz;
+    r = rnum / period device-side samples per hop."""
+    sr_in, sr_out = int(sr_in), int(sr_out)
+    up, down = ratio(sr_in, sr_out)
+    if STREAM_RATE not in (sr_in, sr_out):
+        raise ValueError("ScheduledStreamResampler: one side must be %d Hz, the rate of the real-time path (got %d -> %d); other pairs are "
+                         "converted offline, by Resampler / python -m nele_gan_amd.resample" % (STREAM_RATE, sr_in, sr_out))
+    zeros, beta = quality_params(quality)
+    to16k = int(sr_out == STREAM_RATE)
+    info = (c_int * _lib.CONSTS3['NELE_SCHED_INFO'])()
+    call('nele_sched_stream_plan', up, down, zeros, to16k, info)
+    at = lambda name: int(info[_lib.CONSTS3['NELE_SCHED_I_' + name]])
+    return {'up': up, 'down': down, 'zeros': zeros, 'beta': beta, 'to16k': to16k, 'K': at('K'), 'delay': at('D'), 'L0': at('L0'), 'E': at('E'),
+            'H': at('H'), 'rnum': at('RNUM'), 'period': at('P'), 'hop_min': at('HOP_MIN'), 'hop_max': at('HOP_MAX')}
+
+
+class ScheduledStreamResampler(SlotState):
+    """``streams`` independent live streams from sr_in to sr_out on a hop schedule (csrc/resample_sched.hip; the arithmetic is DESIGN.md
+    section 20): StreamResampler for every rate, 44.1 kHz and its family among them.  One side is 16 kHz, where a hop is 256 samples; on
+    the other side the hop at schedule position g has floor((g + 1) r) - floor(g r) samples, r = 256 sr_dev / 16000 (705, 706, 705, 706,
+    706 at 44.1 kHz), repeating with ``period``.  What a stream has emitted is, bit for bit, ``Resampler(sr_in, sr_out, quality)``'s
+    output for the whole signal fed so far, ``delay`` output samples late; flush() hands out the rest.
+
+    The schedule positions live here, on the host: ``positions[slot]``, and ``position``, where the last process() call ended - where
+    reset() starts a slot, so that a fresh stream joins the running ones in step.  A call runs its hops from one position: all its
+    active slots must stand there.  A slot that sat out k hops is in step again when k is a multiple of ``period``; until then it runs
+    in calls of its own or is reset.  This class owns memory and bookkeeping only; there is no arithmetic in torch."""
+
+    def __init__(self, streams, sr_in, sr_out, quality='high', device='cuda'):
+        super().__init__(streams)
+        self.sr_in, self.sr_out = int(sr_in), int(sr_out)
+        plan = sched_plan(sr_in, sr_out, quality)            # raises ValueError for an unsupported pair, before any GPU call
+        self.up, self.down, self.zeros, self.beta, self.to16k = plan['up'], plan['down'], plan['zeros'], plan['beta'], plan['to16k']
+        self.K, self.H, self.delay, self.period, self._rnum = plan['K'], plan['H'], plan['delay'], plan['period'], plan['rnum']
+        self.hop_min, self.hop_max = plan['hop_min'], plan['hop_max']
+        self.position = 0
+        self.positions = np.zeros(self.S, dtype=np.int64)
+        self._alloc(device, _lib.lib.nele_sched_stream_state_bytes(self.S, self.H))
+        self.table = torch.from_numpy(taps(self.up, self.down, self.zeros, self.beta, layout=1)).to(self.device)
+        call('nele_sched_stream_init', *self._geometry(), stream())
+
+    def _geometry(self):
+        return ptr(self.state), c_longlong(self.nbytes), self.S, self.up, self.down, self.K, self.to16k
+
+    # ---- the schedule
+    def _pos(self, pos):
+        pos = self.position if pos is None else int(pos)
+        if not 0 <= pos < self.period:
+            raise ValueError("%s: position %d outside 0 .. %d" % (type(self).__name__, pos, self.period - 1))
+        return pos
+
+    def _dev_width(self, nh, pos):
+        return (pos + nh) * self._rnum // self.period - pos * self._rnum // self.period
+
+    def width_in(self, nh, pos=None):
+        """input samples per row of a call of nh hops from schedule position pos (None: ``position``)"""
+        return self._dev_width(int(nh), self._pos(pos)) if self.to16k else int(nh) * TILE
+
+    def width_out(self, nh, pos=None):
+        """output samples per row of a call of nh hops from schedule position pos (None: ``position``)"""
+        return int(nh) * TILE if self.to16k else self._dev_width(int(nh), self._pos(pos))
+
+    def call_plan(self, width, act=None):
+        """(pos, nh) of a call whose rows are ``width`` input samples wide in the slots of the host mask ``act`` (None: all): the
+        position those slots stand at and the hops the width is from there.  ValueError names the slots that stand elsewhere, or says
+        that the width is not one of the schedule's."""
+        who = type(self).__name__
+        at = self.positions if act is None else self.positions[act]
+        pos = self.position if at.size == 0 else int(np.bincount(at).argmax())
+        if (at != pos).any():
+            idx = np.arange(self.S) if act is None else np.nonzero(act)[0]
+            raise ValueError("%s.process: slots %s stand at schedule positions %s, the call's other slots at %d: run them in calls of their own "
+                             "or reset them" % (who, idx[at != pos].tolist(), at[at != pos].tolist(), pos))
+        width = int(width)
+        nh = width * self.period // self._rnum if self.to16k else width // TILE      # widths grow strictly with nh: this or the next
+        for n in (nh, nh + 1):
+            if n >= 1 and self.width_in(n, pos) == width:
+                return pos, n
+        raise ValueError("%s.process: x must be [%d, width] with a width of the schedule from position %d - %d, %d, %d, .. (got %d)"
+                         % (who, self.S, pos, self.width_in(1, pos), self.width_in(2, pos), self.width_in(3, pos), width))
+
+    # ---- streaming
+    def process(self, x, active=None, out=None):
+        """x [streams, width_in(nh, pos)] float32 (host, pinned host or device), pos the position of the active slots -> y [streams,
+        width_out(nh, pos)] on the device.  active: host bool sequence [streams] or None (all): inactive slots are neither read nor
+        changed and their output columns are left as they were (undefined in a fresh tensor; give ``out``, a float32 device tensor of
+        the output's shape, to keep them).  Never blocks the host."""
+        who = type(self).__name__
+        shape = tuple(np.shape(x))
+        if len(shape) != 2 or shape[0] != self.S or shape[1] == 0:
+            raise ValueError("%s.process: x must be [%d, width] (got %s)" % (who, self.S, shape))
+        if isinstance(x, torch.Tensor) and x.dtype != torch.float32:
+            raise ValueError("%s: x must be float32" % who)
+        act = None if active is None else self._flags(active, "%s.process: active must hold one flag per stream (%d)" % (who, self.S))
+        pos, nh = self.call_plan(shape[1], act)
+        oshape = (self.S, self.width_out(nh, pos))
+        if out is None:
+            out = torch.empty(oshape, dtype=torch.float32, device=self.device)
+        elif not isinstance(out, torch.Tensor) or tuple(out.shape) != oshape or out.dtype != torch.float32 or not out.is_cuda \
+                or not out.is_contiguous():
+            raise ValueError("%s.process: out must be a contiguous float32 %s tensor on the device" % (who, oshape))
+        xd = self._dev_f32(x, shape, 'x')                     # every check is behind us: the first transfer
+        call('nele_sched_stream_hop', *self._geometry(), ptr(self.table), ptr(xd), c_longlong(shape[1]),
+             ptr(None if act is None else self._dev_bytes(act)), nh, pos, ptr(out), c_longlong(oshape[1]), stream())
+        which = slice(None) if act is None else act
+        self.hops[which] += nh
+        self.positions[which] = self.position = (pos + nh) % self.period
+        return out
+
+    def flush(self, slots):
+        """End the streams of ``slots`` (all at one position): one hop of zeros through those slots -> its first ``delay`` columns,
+        [len(slots), delay] - the outputs still inside the filter; with what was emitted that is the offline resampler's whole output.
+        Resets those slots to ``position``, which this call leaves where it was."""
+        slots = np.asarray(slots, dtype=np.int64).reshape(-1)
+        mask, position = self._slots_mask(slots), self.position
+        pos = int(self.positions[slots[0]]) if slots.size else position
+        y = self.process(torch.zeros((self.S, self.width_in(1, pos)), dtype=torch.float32, device=self.device), active=mask)
+        tail = y.index_select(0, self._dev_rows(slots))[:, :self.delay].contiguous()
+        self.position = position
+        self.reset(slots)
+        return tail
+
+    def reset(self, slots, position=None):
+        """Restart the given slots (a zero history) at schedule position ``position`` (None: ``position``, where the last process()
+        call ended); the other slots are not touched."""
+        pos = self._pos(position)
+        m = self._slots_mask(slots)
+        call('nele_sched_stream_reset', *self._geometry(), ptr(self._dev_bytes(m)), stream())
+        self.hops[m] = 0
+        self.positions[m] = pos
 
 
 _CACHE = {}

@@ -2,17 +2,24 @@
 csrc/resample_stream.hip) in front of and behind a ``RealtimeEnhancer`` or an ``EchoCancellingEnhancer``, which
 work at 16 kHz in hops of 256 samples.  Telephony is 8 kHz, browsers and sound cards 48 kHz; supported device rates are those at which
 a 16 ms hop is a whole number of samples (8, 12, 22, 24, 32, 48, 64, 96 kHz ..; not 44.1 kHz and its family - convert those offline with
-python -m nele_gan_amd.resample).  This module owns memory and bookkeeping only; there is no arithmetic in torch.
+python -m nele_gan_amd.resample).  ``ScheduledRateEnhancer`` is the same arrangement on ``ScheduledStreamResampler``
+(csrc/resample_sched.hip) for every rate, 44.1 kHz and its family among them: the hops at the device rate follow
+a schedule (705, 706, 705, 706, 706 samples at 44.1 kHz).  ``adapt`` picks the one that serves a rate.  This module owns memory and
+bookkeeping only; there is no arithmetic in torch.
 
-    rt48 = RateAdaptedEnhancer(RealtimeEnhancer(chkpt, streams=256), device_rate=48000)
+    rt48 = adapt(RealtimeEnhancer(chkpt, streams=256), device_rate=48000)
     out = rt48.process(clean_hops, noise_hops)                 # [256, nh * 768] each, at 48 kHz -> [256, nh * 768] at 48 kHz
+    rt44 = adapt(RealtimeEnhancer(chkpt, streams=256), device_rate=44100)
+    out = rt44.process(clean_hops, noise_hops)                 # [256, rt44.width(nh)] each, at 44.1 kHz -> the same shape
 """
+import fractions
+
 import numpy as np
 import torch
 
 from .aec import EchoCancellingEnhancer
 from .realtime import HOP, RealtimeEnhancer
-from .resample import STREAM_RATE, StreamResampler
+from .resample import STREAM_RATE, ScheduledStreamResampler, StreamResampler, stream_plan
 from ._slots import dev_f32, dev_rows, host_flags
 
 
@@ -29,9 +36,11 @@ class RateAdaptedEnhancer:
 
     Streams end through drain(): the inner path's finish() and its tails of less than a hop are not offered at the device rate."""
 
+    CONVERTER = StreamResampler
+
     def __init__(self, inner, device_rate, quality='high'):
         if not isinstance(inner, (RealtimeEnhancer, EchoCancellingEnhancer)):
-            raise ValueError("RateAdaptedEnhancer: inner must be a RealtimeEnhancer or an EchoCancellingEnhancer (got %s)" % type(inner).__name__)
+            raise ValueError("%s: inner must be a RealtimeEnhancer or an EchoCancellingEnhancer (got %s)" % (type(self).__name__, type(inner).__name__))
         self.inner, self.S = inner, inner.S
         self.device_rate = int(device_rate)
         self.device = inner.device if isinstance(inner, RealtimeEnhancer) else inner.aec.device
@@ -41,11 +50,14 @@ class RateAdaptedEnhancer:
             self.hop, self.latency = HOP, HOP
             return
         # both constructors raise ValueError for an unsupported rate before any GPU call
-        self.down = StreamResampler(2 * self.S, self.device_rate, STREAM_RATE, quality, self.device)
-        self.up = StreamResampler(self.S, STREAM_RATE, self.device_rate, quality, self.device)
+        self.down = self.CONVERTER(2 * self.S, self.device_rate, STREAM_RATE, quality, self.device)
+        self.up = self.CONVERTER(self.S, STREAM_RATE, self.device_rate, quality, self.device)
+        self._both = None                                  # [2 S, width]: the two signals stacked for the down-converter
+        self._set_latency()
+
+    def _set_latency(self):
         self.hop = self.down.hop_in
         self.latency = self.down.delay * self.hop // HOP + self.hop + self.up.delay
-        self._both = None                                  # [2 S, nh * hop]: the two signals stacked for the down-converter
 
     def _stack(self, clean, second, width):
         if self._both is None or self._both.shape[1] != width:
@@ -70,7 +82,10 @@ class RateAdaptedEnhancer:
             raise ValueError("RateAdaptedEnhancer.process: clean must be [%d, nh * %d] (got %s)" % (self.S, self.hop, shape))
         act = None if active is None else host_flags(active, self.S, "RateAdaptedEnhancer.process: active must hold one flag per stream (%d)" % self.S)
         self._per_call = shape[1] // self.hop
-        low = self.down.process(self._stack(clean, second, shape[1]), active=None if act is None else np.concatenate([act, act]))
+        return self._chain(clean, second, shape[1], act)
+
+    def _chain(self, clean, second, width, act):
+        low = self.down.process(self._stack(clean, second, width), active=None if act is None else np.concatenate([act, act]))
         out = self.inner.process(low[:self.S], low[self.S:], active=act)
         return self.up.process(out, active=act)
 
@@ -94,3 +109,87 @@ class RateAdaptedEnhancer:
             slots = np.asarray(slots, dtype=np.int64).reshape(-1)
             self.down.reset(np.concatenate([slots, slots + self.S]))
             self.up.reset(slots)
+
+
+class ScheduledRateEnhancer(RateAdaptedEnhancer):
+    """RateAdaptedEnhancer's arrangement on ScheduledStreamResampler: every device rate section 12 admits, 44.1 kHz and its family among
+    them.  Both converters follow the same hop schedule, so a call returns as many samples as it was given: ``width(nh)`` of them for nh
+    hops from where the active slots stand (705, 706, 705, 706, 706 per hop at 44.1 kHz).  ``latency`` is a fractions.Fraction in
+    device-rate samples, D_down r / 256 + r + D_up with r = 256 device_rate / 16000 samples per hop: 4414 / 5 = 882.8 samples = 20.02 ms
+    at 44.1 kHz with quality 'high'.
+
+    Around an EchoCancellingEnhancer the two converters are a constant extra delay of the echo path the canceller learns - D_up at the
+    device rate plus D_down at 16 kHz: each stream is the offline conversion of its whole signal, delayed, so nothing in it moves with
+    the schedule.
+
+    The slots' schedule positions are the converters' (``down.positions``, ``up.positions``): a call's active slots
+    must stand at one position, and reset(slots) starts slots where the last process() call ended."""
+
+    CONVERTER = ScheduledStreamResampler
+
+    def _set_latency(self):
+        r = fractions.Fraction(self.down._rnum, self.down.period)
+        self.hop = None                                    # no one hop length: width(nh)
+        self.latency = self.down.delay * r / HOP + r + self.up.delay
+
+    def width(self, nh, pos=None):
+        """samples per row, at the device rate, of a call of nh hops from schedule position pos (None: where the last call ended)"""
+        return nh * HOP if self.down is None else self.down.width_in(nh, pos)
+
+    def process(self, clean, second, active=None):
+        """As RateAdaptedEnhancer.process with clean, second [streams, width(nh, pos)], pos the position of the active slots -> the
+        enhanced signal of the same shape, ``latency`` samples behind ``clean``."""
+        if self.down is None:
+            return super().process(clean, second, active=active)
+        shape = tuple(np.shape(clean))
+        if len(shape) != 2 or shape[0] != self.S or shape[1] == 0:
+            raise ValueError("ScheduledRateEnhancer.process: clean must be [%d, width(nh)] (got %s)" % (self.S, shape))
+        act = None if active is None else host_flags(active, self.S, "ScheduledRateEnhancer.process: active must hold one flag per stream (%d)" % self.S)
+        _, nh = self.down.call_plan(shape[1], None if act is None else np.concatenate([act, act]))      # ValueError: not on the schedule
+        self.up.call_plan(nh * HOP, act)
+        self._per_call = nh
+        return self._chain(clean, second, shape[1], act)
+
+    def drain(self, slots):
+        """ceil(latency / r) hops of zeros through the given slots (all at one schedule position) -> their outputs [len(slots), the
+        width of those hops from there]: what is still delayed inside leaves this way (the other slots are not touched, and ``position``
+        of both converters stays where it was).  The zeros go in calls of as many hops as the last process() call, so those slots may
+        receive a few zero hops more than are returned.  reset() them before their next stream."""
+        if self.down is None:
+            return super().drain(slots)
+        slots = np.asarray(slots, dtype=np.int64).reshape(-1)
+        act = np.zeros(self.S, dtype=bool)
+        act[slots] = True
+        r = fractions.Fraction(self.down._rnum, self.down.period)
+        nh, per = -(-self.latency // r), self._per_call
+        kept = (self.down.position, self.up.position)
+        total = self.down.width_in(nh, int(self.down.positions[slots[0]]))
+        outs = []
+        for _ in range(-(-nh // per)):
+            zeros = torch.zeros((self.S, self.down.width_in(per, int(self.down.positions[slots[0]]))), dtype=torch.float32, device=self.device)
+            outs.append(self.process(zeros, zeros, active=act))
+        self.down.position, self.up.position = kept
+        rows = dev_rows(slots, self.device)
+        return torch.cat([o.index_select(0, rows) for o in outs], dim=1)[:, :total]
+
+    def reset(self, slots, position=None):
+        """Restart the given slots in the inner object and in both converters, at schedule position ``position`` (None: where the last
+        process() call ended)."""
+        self.inner.reset(slots)
+        if self.down is not None:
+            slots = np.asarray(slots, dtype=np.int64).reshape(-1)
+            self.down.reset(np.concatenate([slots, slots + self.S]), position)
+            self.up.reset(slots, position)
+
+
+def adapt(inner, device_rate, quality='high'):
+    """``inner`` at ``device_rate``: a RateAdaptedEnhancer where that class accepts the rate (a 16 ms hop is a whole number of samples;
+    16 kHz passes straight through), a ScheduledRateEnhancer otherwise (44.1 kHz and its family)."""
+    device_rate = int(device_rate)
+    if device_rate != STREAM_RATE:
+        try:
+            stream_plan(device_rate, STREAM_RATE, quality)
+            stream_plan(STREAM_RATE, device_rate, quality)
+        except ValueError:
+            return ScheduledRateEnhancer(inner, device_rate, quality)
+    return RateAdaptedEnhancer(inner, device_rate, quality)
