@@ -668,6 +668,15 @@ int nele_metric_haspi_quality_hl(const float* x, const float* y, const int* leng
  * Dloud, Dslope}; info [B][4] as nele_metric_haspi_quality (status bit 1 also for a digitally silent y); status bits 1 / 2 make the
  * row NaN.  nele_metric_hasqi_clean_sections: what phase 3 leaves, in the form of nele_metric_haspi_clean_sections (12 sections). */
 long long nele_metric_hasqi_workspace_bytes(int B, int L, int fs_in);
+/* Diagnostic (tests): the buffers a call of nele_metric_haspi_quality[_hl] or nele_metric_hasqi_var (phase 0, or 3 then 4) leaves in
+ * its workspace, as {offset, stride, bytes} like nele_metric_haspi_sections (nseg = segments of the PADDED length, nchunk = its scan chunks):
+ *    0 r24 float [2][n24p]   1 rinfo float [2][4]   2 bw double [2][32]   3 shift int [32]
+ *    4 env float [2][n24p][32] ADAPTED envelope, dB SL   5 cphi float [2][n24p][32] basilar-membrane motion (both before the group-delay shift)
+ *    6 sse   7 ssp double [2][nchunk][32] per-chunk sums of |u|^2 of the signal / the control bank, without the filter gain
+ *    8 sm double [2][nseg][32]   9 cov   10 msx   11 msy double [nseg][32]   12 segl double [2][nseg]   13 qinfo int [4]
+ *   14 sl double [2][32] eb_aveSL's band levels   15 corr double [2][64] (stride 0)   16 loss double [2][5][32] (stride 0)
+ * Returns the number of sections (max_sections >= 17) or a negative status.  Host-only: no device work. */
+int nele_metric_haspi_quality_sections(int B, int L, int fs_in, long long* out, int max_sections);
 int nele_metric_hasqi_clean_sections(int B, int L, int fs_in, long long* out, int max_sections);
 int nele_metric_hasqi_var(const float* x, const float* y, const int* lengths, int B, int L, int fs_in, const double* hl6_host,
                           int noise, unsigned long long seed, const long long* utt_ids, void* workspace, long long workspace_bytes,

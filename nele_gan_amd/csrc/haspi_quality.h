@@ -30,6 +30,7 @@ struct QualWs {
     double* corr;    // [2][64]           1 / xcorr(window, window, 24) for the full and the half window
     double* segl;    // [B][2][nseg]      segment loudness: of the smoothed reference envelope, of sqrt(msx)
     int* qinfo;      // [B][4]            {segments above threshold (eb_melcor), status bits, above threshold (covariance), histogram bins}
+    double* sl;      // [B][2][32]        eb_aveSL's band levels in dB SL of x then y (read by nele_metric_haspi_quality_sections only)
     int nseg;        // of the longest row
     unsigned long long seed;
     int noise;       // 0 none, 1 keyed by (seed, row of the batch), 2 keyed by (seed, ids[b]): see nele_metric_hasqi_var
@@ -481,6 +482,7 @@ __global__ __launch_bounds__(256) void hq_final_kernel(HaspiWs ws, QualWs q, dou
         double ls = HP_LEVEL + 20.0 * log10(fmax(ave, small));
         ls = fmax(ls, 0.0);
         SL[sig][ch] = fmax(ls + gain - lo.attnIHC, 0.0);
+        q.sl[((size_t)b * 2 + sig) * HP_NCH + ch] = SL[sig][ch];
     }
     __syncthreads();
     if (tid < 64) {
@@ -547,6 +549,7 @@ static WsArena quality_layout(int B, int L, int fs_in, HaspiWs& w, QualWs& q, vo
     a.take(q.corr, 128);
     a.take(q.segl, (size_t)B * 2 * nseg);
     a.take(q.qinfo, (size_t)B * 4);
+    a.take(q.sl, (size_t)B * 2 * HP_NCH);
     q.nseg = nseg;
     return a;
 }
@@ -554,6 +557,39 @@ static WsArena quality_layout(int B, int L, int fs_in, HaspiWs& w, QualWs& q, vo
 extern "C" long long nele_metric_haspi_quality_workspace_bytes(int B, int L, int fs_in) {
     HaspiWs w; QualWs q;
     return (long long)quality_layout(B, L, fs_in, w, q, nullptr).off;
+}
+
+// Diagnostic (tests): the buffers a call of nele_metric_haspi_quality[_hl] or nele_metric_hasqi_var (phase 0, or 3 then 4) leaves in its
+// workspace, as {offset, stride, bytes} like nele_metric_haspi_sections.  n24p = n24 of the padded length rounded up to 32, nseg =
+// hq_nseg(n24), nchunk = the scan chunks of the padded length; a shorter row fills the front of each plane, what lies behind is unspecified.
+//    0 r24   float  [2][n24p]          rms-normalised x then y at 24 kHz before the RMS-restore gain rinfo[2]
+//    1 rinfo float  [2][4]             {rms of the input, rms of the normalised input, restore gain, unused}
+//    2 bw    double [2][32]            adjusted bandwidths BWx, BWy
+//    3 shift int    [32]               group-delay shifts (from BWx)
+//    4 env   float  [2][n24p][32]      ADAPTED envelope in dB SL (hq_ihc_bm_kernel, in place), before the group-delay shift
+//    5 cphi  float  [2][n24p][32]      basilar-membrane motion (with the noise, if any), before the group-delay shift
+//    6 sse   double [2][nchunk][32]    per scan chunk: sum of the signal bank's |u|^2 without the filter gain
+//    7 ssp   double [2][nchunk][32]    the same of the control bank
+//    8 sm    double [2][nseg][32]      smoothed envelopes (eb_EnvSmooth); the segment planes have the stride of the PADDED length's nseg
+//    9 cov   double [nseg][32]         segment cross-covariance, clipped to [0, 1]
+//   10 msx   double [nseg][32]         2 x mean square of the reference BM segments
+//   11 msy   double [nseg][32]
+//   12 segl  double [2][nseg]          segment loudness of the smoothed reference envelope, of sqrt(msx)
+//   13 qinfo int    [4]                {segments above threshold (eb_melcor), status, above threshold (covariance), histogram bins}
+//   14 sl    double [2][32]            eb_aveSL's band levels in dB SL
+//   15 corr  double [2][64]            stride 0 (shared): 1 / xcorr(window, window, 24), full and half window, 49 entries each
+//   16 loss  double [2][5][32]         stride 0 (shared): attnOHC, BWmin, lowknee, CR, attnIHC of x then y
+// Returns the number of sections (17; max_sections must hold them) or a negative status.  Host-only: no device work.
+extern "C" int nele_metric_haspi_quality_sections(int B, int L, int fs_in, long long* out, int max_sections) {
+    NELE_CHECK_ARG(B > 0 && out, "nele_metric_haspi_quality_sections: bad arguments");
+    NELE_CHECK_ARG(fs_in >= 1000 && fs_in <= 24000 && L >= 2400, "nele_metric_haspi_quality_sections: bad signal geometry");
+    HaspiWs w;
+    QualWs q;
+    const WsArena a = quality_layout(B, L, fs_in, w, q, nullptr);
+    return ws_sections("nele_metric_haspi_quality_sections", a, B, out, max_sections, [&](WsSections& s) {
+        s.rows(w.r24, w.rinfo, w.bw, w.shift, w.env, w.cphi, w.sse, w.ssp, q.sm, q.cov, q.msx, q.msy, q.segl, q.qinfo, q.sl);
+        s.shared(q.corr, w.loss);
+    });
 }
 
 // x, y [B][L] float32 (reference, processed); lengths [B] or NULL; noise != 0: eb_BMaddnoise with the counter-based generator seeded

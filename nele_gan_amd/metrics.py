@@ -804,6 +804,85 @@ def batch_hasqi(x, y, fs=16000, lengths=None, noise=False, seed=0, utt_ids=None,
     return (out, sp.info) if return_info else out
 
 
+def haspi_quality_stages(x, y, fs, lengths=None, HL=None, itype=0, noise=False, seed=0, split=None, utt_ids=None):
+    """Diagnostic (tests only; nothing in training calls it): HASPI v1 / HASQI v2 on a workspace of its own (every byte 0xFF before the
+    call: what a kernel does not write reads as NaN / -1) -> (out float64 numpy, info int32 numpy [B, 4], stages): the workspace read
+    through nele_metric_haspi_quality_sections.  split=None: one nele_metric_haspi_quality[_hl] call, out [B, 12] (QUALITY_FIELDS);
+    split='phase0': one nele_metric_hasqi_var call at phase 0, split='3+4': its phase 3 then its phase 4 on the same workspace, out [B, 7]
+    (HASQI_FIELDS; both hear HL with itype 2).  noise: False | True | 'utterance' (the split forms, with utt_ids).
+    stages[name][b] is row b's array, cut to the row's own n24 samples at 24 kHz and nseg = 1 + n24 // 384 + (n24 - 192) // 384 segments:
+      'r24' [2, n24] float32 WITH the RMS-restore gain (as haspi_stages); 'rinfo' [2, 4] float32; 'bw' [2, 32]; 'shift' [32] int32;
+      'env' [2, n24, 32] float32 the ADAPTED envelope in dB SL and 'bm' [2, n24, 32] float32 the basilar-membrane motion, both BEFORE the
+      group-delay shift; 'sse' / 'ssp' [2, chunks of the row, 32] sums of |u|^2 of the signal / control bank without the filter gain;
+      'sm' [2, nseg, 32]; 'cov', 'msx', 'msy' [nseg, 32]; 'segl' [2, nseg]; 'qinfo' [4] int32; 'sl' [2, 32];
+    and, shared by the rows, 'corr' [2, 49] and 'loss' [2, 5, 32]."""
+    x, y, _ = _pair(x, y)
+    B, L = x.shape
+    fs = int(fs)
+    if split not in (None, 'phase0', '3+4'):
+        raise ValueError("haspi_quality_stages: split must be None, 'phase0' or '3+4'")
+    if noise not in _HASQI_NOISE:
+        raise ValueError("haspi_quality_stages: noise must be False, True or 'utterance'")
+    nz = _HASQI_NOISE[noise]
+    hl = _hl6(HL)
+    if split is None and nz == 2:
+        raise ValueError('haspi_quality_stages: per-utterance noise exists in the split entry point only')
+    if split is not None and hl is not None and itype != 2:
+        raise ValueError('haspi_quality_stages: nele_metric_hasqi_var hears the loss with itype 2 only')
+    ids = None
+    if nz == 2:
+        ids = torch.as_tensor(utt_ids).to(device=x.device, dtype=torch.int64).contiguous()
+    ws = torch.full((int(_lib.lib.nele_metric_haspi_quality_workspace_bytes(B, L, fs)),), 255, dtype=torch.uint8, device=x.device)
+    out = torch.full((B, len(QUALITY_FIELDS) if split is None else len(HASQI_FIELDS)), -1.0, dtype=torch.float64, device=x.device)
+    info = torch.full((B, 4), -1, dtype=torch.int32, device=x.device)
+    lens = _lens(lengths, x.device)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    if split is None:
+        if hl is None:
+            call('nele_metric_haspi_quality', ptr(x), ptr(y), ptr(lens), B, L, fs, nz, seed, -1.0, ptr(ws), ws.numel(), ptr(out), ptr(info), stream())
+        else:
+            call('nele_metric_haspi_quality_hl', ptr(x), ptr(y), ptr(lens), B, L, fs, nz, seed, -1.0, hl, int(itype), ptr(ws), ws.numel(), ptr(out),
+                 ptr(info), stream())
+    else:
+        for phase in ((0,) if split == 'phase0' else (3, 4)):
+            call('nele_metric_hasqi_var', ptr(x) if phase != 4 else None, ptr(y) if phase != 3 else None, ptr(lens), B, L, fs, hl, nz, seed, ptr(ids),
+                 ptr(ws), ws.numel(), ptr(out), ptr(info), phase, stream())
+    buf = (c_longlong * 51)()
+    n = _lib.lib.nele_metric_haspi_quality_sections(B, L, fs, buf, 17)
+    if n != 17:
+        _lib.check(n, 'nele_metric_haspi_quality_sections')
+    sec = [(int(buf[3 * k]), int(buf[3 * k + 1]), int(buf[3 * k + 2])) for k in range(17)]
+    r24, rinfo, bw, shift, env, bm, sse, ssp, sm, cov, msx, msy, segl, qinfo, sl = _section_rows(ws, sec[:15], B)
+    corr, loss = (ws[o:o + nb].cpu().numpy().view(np.float64).copy() for (o, _st, nb) in sec[15:])
+    lens = np.full(B, L) if lengths is None else np.minimum(np.asarray(torch.as_tensor(lengths).cpu()), L)
+    n24p = sec[0][2] // 8
+    lc = 1536                                            # GS_LC of csrc/haspi.hip; longer chunks beyond GS_MAXC = 160 of them
+    while -(-n24p // lc) > 160:
+        lc += 1536
+    st = {k: [] for k in ('r24', 'rinfo', 'bw', 'shift', 'env', 'bm', 'sse', 'ssp', 'sm', 'cov', 'msx', 'msy', 'segl', 'qinfo', 'sl')}
+    st['corr'] = corr.reshape(2, 64)[:, :49].copy()
+    st['loss'] = loss.reshape(2, 5, 32)
+    for b in range(B):
+        n24 = int(lens[b]) if fs == 24000 else int(np.ceil(float(int(lens[b])) * (24000.0 / fs)))
+        nseg, nchk = 1 + n24 // 384 + (n24 - 192) // 384, -(-n24 // lc)
+        ri = rinfo[b].view(np.float32).reshape(2, 4).copy()
+        st['rinfo'].append(ri)
+        st['r24'].append(ri[:, 2:3] * r24[b].view(np.float32).reshape(2, -1)[:, :n24])
+        st['bw'].append(bw[b].view(np.float64).reshape(2, 32).copy())
+        st['shift'].append(shift[b].view(np.int32).copy())
+        st['env'].append(env[b].view(np.float32).reshape(2, -1, 32)[:, :n24].copy())
+        st['bm'].append(bm[b].view(np.float32).reshape(2, -1, 32)[:, :n24].copy())
+        st['sse'].append(sse[b].view(np.float64).reshape(2, -1, 32)[:, :nchk].copy())
+        st['ssp'].append(ssp[b].view(np.float64).reshape(2, -1, 32)[:, :nchk].copy())
+        st['sm'].append(sm[b].view(np.float64).reshape(2, -1, 32)[:, :nseg].copy())
+        for k, a in (('cov', cov), ('msx', msx), ('msy', msy)):
+            st[k].append(a[b].view(np.float64).reshape(-1, 32)[:nseg].copy())
+        st['segl'].append(segl[b].view(np.float64).reshape(2, -1)[:, :nseg].copy())
+        st['qinfo'].append(qinfo[b].view(np.int32).copy())
+        st['sl'].append(sl[b].view(np.float64).reshape(2, 32).copy())
+    return out.cpu().numpy(), info.cpu().numpy(), st
+
+
 def _quality_checked(x, fx, y, fy, alpha=-1.0, HL=None, itype=0):
     if fx != fy:
         raise ValueError('haspi / hasqi_v2: both signals must have the same sampling rate here (the reference resamples each to 24 kHz)')

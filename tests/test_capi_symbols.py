@@ -96,7 +96,7 @@ def declared_prototypes():
 def test_every_entry_point_is_bound_with_the_headers_arity_and_return_type():
     from nele_gan_amd import _abi, _lib
     protos = declared_prototypes()
-    assert len(protos) == 199 and sorted(protos) == declared_symbols() == sorted(_abi.FUNCS)
+    assert len(protos) == 200 and sorted(protos) == declared_symbols() == sorted(_abi.FUNCS)
     restypes = {'int': ctypes.c_int, 'longlong': ctypes.c_longlong, 'constchar*': ctypes.c_char_p, 'float*': ctypes.c_void_p,
                 'void*': ctypes.c_void_p}
     for name, (ret, nargs) in protos.items():

@@ -25,8 +25,9 @@ def test_the_fixture_holds_every_case():
     good = [r for r in GOLDEN if r['max'] is not None and r['ret'] > 0]
     assert {r['fn']: r['ret'] for r in good} == {name: n for name, (_na, n) in gen.SECTIONS.items()}
     assert all(len(r['out']) == 3 * r['ret'] for r in good)
-    # the argument errors: one section short, a rate above 24 kHz, a signal below HASPI's minimum
-    assert sum(r['ret'] < 0 for r in GOLDEN) == len(gen.SECTIONS) + 2 * 3
+    # the argument errors: one section short; a rate above 24 kHz and a signal below HASPI's minimum for the four functions that take a rate
+    assert sum(na == 3 for (na, _n) in gen.SECTIONS.values()) == 4
+    assert sum(r['ret'] < 0 for r in GOLDEN) == len(gen.SECTIONS) + 2 * 4
 
 
 @pytest.mark.parametrize('name', ['libnele_hip.so', 'libnele_hip_ab.so'])

@@ -25,7 +25,8 @@ SIZES = {                                     # name -> number of leading int ar
     'nele_metric_haspi_quality_workspace_bytes': 3, 'nele_metric_hasqi_workspace_bytes': 3}
 SECTIONS = {                                  # name -> (number of leading int arguments, sections of a good call)
     'nele_metric_estoi_sections': (2, 6), 'nele_metric_siib_clean_sections': (2, 13), 'nele_metric_haspi_clean_sections': (3, 16),
-    'nele_metric_haspi_sections': (3, 15), 'nele_metric_hasqi_clean_sections': (3, 12), 'nele_metric_siib_sections': (2, 10)}
+    'nele_metric_haspi_sections': (3, 15), 'nele_metric_hasqi_clean_sections': (3, 12), 'nele_metric_siib_sections': (2, 10),
+    'nele_metric_haspi_quality_sections': (3, 17)}
 
 
 def cases():
