@@ -13,12 +13,14 @@ is DESIGN.md section 14).  This module owns memory and bookkeeping only; there i
 
     python -m nele_gan_amd.aec --mic mic.wav --played far.wav --out residual.wav [--partitions 8] [--echo-path h.npy] [--bulk-blocks 32 [--bulk-track]
                                [--drift [--drift-ppm PPM]]] [--suppress [--res-beta 2.0] [--res-gmin 0.1]]
+                               [--uplink uplink.wav [--uplink-gmin 0.1]]
 
 A bulk delay (the device's playback and capture buffers) is found and taken out ahead of the canceller by nele_gan_amd/bulkdelay.py
 (``AlignedEchoCanceller``; --bulk-blocks on the command line), and followed when it moves later by nele_gan_amd/bulktrack.py
 (``TrackedEchoCanceller``; --bulk-track); clock drift between playback and capture is followed by nele_gan_amd/drift.py
 (``DriftTrackedEchoCanceller``; --drift).  The echo the canceller leaves is suppressed behind it by
-nele_gan_amd/res.py (``SuppressedEchoCanceller``; --suppress on the command line).
+nele_gan_amd/res.py (``SuppressedEchoCanceller``; --suppress on the command line).  The near-end noise in the residual is suppressed for
+the uplink by nele_gan_amd/ns.py (``NoiseSuppressor``; --uplink).
 """
 import numpy as np
 import torch
@@ -110,9 +112,11 @@ class EchoCancellingEnhancer:
                              % (self.played.shape[1] // HOP, width // HOP))
         return self.played
 
-    def process(self, clean, mic, active=None, debug=None):
+    def process(self, clean, mic, active=None, debug=None, want_residual=False):
         """clean, mic [streams, nh * 256] float32 -> out [streams, nh * 256] (RealtimeEnhancer.process on the echo-cancelled mic).
-        The returned tensor is the caller's: the loop keeps its own copy of what was played.  debug: RealtimeEnhancer's RealtimeDebug."""
+        The returned tensor is the caller's: the loop keeps its own copy of what was played.  debug: RealtimeEnhancer's RealtimeDebug.
+        want_residual: -> (out, residual), the canceller's residual of this call as the enhancer read it - the near-end signal, what
+        the uplink carries (nele_gan_amd/ns.py's DuplexEnhancer suppresses its noise)."""
         shape = tuple(np.shape(mic))
         if len(shape) != 2 or shape[1] % HOP or shape[1] == 0:
             raise ValueError("EchoCancellingEnhancer.process: mic must be [%d, nh * 256]" % self.S)
@@ -124,7 +128,7 @@ class EchoCancellingEnhancer:
         else:
             rows = dev_rows(np.nonzero(np.asarray(active, dtype=bool).reshape(-1))[0], played.device)
             played.index_copy_(0, rows, out.index_select(0, rows))
-        return out
+        return (out, residual) if want_residual else out
 
     def finish(self, slots, clean_tail, mic_tail, tail_lengths, debug=None):
         """End the streams of ``slots`` (RealtimeEnhancer.finish): the tails [len(slots), <= 256] are padded to one hop, one canceller hop
@@ -259,6 +263,10 @@ def build_parser():
                     help='suppress the echo the canceller leaves (nele_gan_amd/res.py); the output is then one 256-sample hop late')
     ap.add_argument('--res-beta', type=float, default=2.0, help='with --suppress: the over-subtraction factor, >= 0')
     ap.add_argument('--res-gmin', type=float, default=0.1, help='with --suppress: the floor of the gain, in (0, 1]')
+    ap.add_argument('--uplink', default=None, metavar='WAV',
+                    help='also write the residual with its noise suppressed (nele_gan_amd/ns.py), PCM_16: what the far end hears, one '
+                         '256-sample hop later than --out')
+    ap.add_argument('--uplink-gmin', type=float, default=None, metavar='G', help='with --uplink: the gain of a bin without speech, in (0, 1] (default 0.1)')
     ap.add_argument('--mu', type=float, default=0.5)
     ap.add_argument('--gamma', type=float, default=4.0)
     ap.add_argument('--delta', type=float, default=1e-2)
@@ -293,11 +301,20 @@ def main(argv=None):
         ap.error('--drift-ppm needs --drift (and --bulk-blocks)')
     if a.drift_ppm is not None and not abs(a.drift_ppm) <= 1000.0:
         ap.error('--drift-ppm must be within +-1000')
+    if a.uplink_gmin is not None and a.uplink is None:
+        ap.error('--uplink-gmin needs --uplink')
+    if a.uplink_gmin is not None and not (0.0 < a.uplink_gmin <= 1.0):
+        ap.error('needs 0 < --uplink-gmin <= 1')
     suppress = (a.res_beta, a.res_gmin) if a.suppress else None
     drift = {'drift': True, 'drift_ppm': a.drift_ppm or 0.0} if a.drift else {}
     res, h, *found = cancel_file(sig[0], sig[1], partitions=a.partitions, mu=a.mu, gamma=a.gamma, delta=a.delta, bulk_blocks=a.bulk_blocks,
                                  suppress=suppress, bulk_track=a.bulk_track, **drift)
     dataio.write_wav_pcm16(a.out, res)
+    if a.uplink:
+        from .ns import suppress_file
+        gmin = 0.1 if a.uplink_gmin is None else a.uplink_gmin
+        dataio.write_wav_pcm16(a.uplink, suppress_file(res, gmin=gmin))
+        print('%s: the residual with its noise suppressed (gmin %g), one hop (%d ms) later than %s' % (a.uplink, gmin, HOP * 1000 // dataio.fs, a.out))
     if a.echo_path:
         np.save(a.echo_path, h)
     print('%s: %d samples, %d partitions (%d ms of echo tail)' % (a.out, len(res), a.partitions, a.partitions * HOP * 1000 // dataio.fs))

@@ -1,8 +1,8 @@
-// The per-bin steps of one IMCRA frame (noise_est/imcra.py), defined once for the four kernels that run them: imcra_band_kernel,
-// imcra_ind_kernel and imcra_track_kernel (features.hip) and rt_front_kernel (realtime.hip).  A step is the arithmetic of the lines it
-// names, in numpy's order of operations and with numpy's float32 / float64 staging (the including file is compiled with
-// -ffp-contract=off); the state goes in and out by reference to the caller's registers.  The loop over frames, the neighbour exchange, the
-// storage of the minima and the state's layout stay with each kernel.
+// The per-bin steps of one IMCRA frame (noise_est/imcra.py), defined once for the kernels that run them: imcra_band_kernel,
+// imcra_ind_kernel and imcra_track_kernel (features.hip), rt_front_kernel (realtime.hip) and ns_hop_kernel (ns.hip).  A step is the
+// arithmetic of the lines it names, in numpy's order of operations and with numpy's float32 / float64 staging (the including file is
+// compiled with -ffp-contract=off); the state goes in and out by reference to the caller's registers.  The loop over frames, the
+// neighbour exchange, the storage of the minima and the state's layout stay with each kernel.
 #pragma once
 #include "common.h"
 
@@ -83,15 +83,21 @@ __device__ __forceinline__ double imcra_prior_step(double Y2, double S, double t
 }
 
 // imcra.py:22-36, 432-441: speech-presence probability from r = imcra_prior_step's result, then the recursive PSD update; returns the
-// new (float64) lambda_D
-__device__ __forceinline__ double imcra_psd_step(double Y2, double Gamma, double xi, double r, double& ovL) {
+// new (float64) lambda_D and hands back the p that drove it.  CAP: p is held to IMCRA_P_UP as the reference's tracker holds it; the
+// noise suppressor (csrc/ns.hip) runs the uncapped form.
+template <bool CAP>
+__device__ __forceinline__ double imcra_psd_step_p(double Y2, double Gamma, double xi, double r, double& ovL, double& p) {
     const double nu = Gamma * xi / (1.0 + xi);
-    double p = 0.0;
+    p = 0.0;
     if (r >= 0.0) p = 1.0 / (1.0 + r * (1.0 + xi) * exp(-nu));
-    if (p > IMCRA_P_UP) p = IMCRA_P_UP;
+    if (CAP && p > IMCRA_P_UP) p = IMCRA_P_UP;
     const double tad = IMCRA_ALPHA_D + IMCRA_ONE_M_AD * p;
     ovL = tad * ovL + (1.0 - tad) * Y2;
     return IMCRA_BETA * ovL;
+}
+__device__ __forceinline__ double imcra_psd_step(double Y2, double Gamma, double xi, double r, double& ovL) {
+    double p;
+    return imcra_psd_step_p<true>(Y2, Gamma, xi, r, ovL, p);
 }
 
 // imcra.py:443-481, what every form of the minima store (LDS rows, eight registers, the stream record) decides alike: the store is
