@@ -8,6 +8,8 @@
 //                     so no cross-workgroup reduction is needed for the channel sums
 //   rt_head_kernel    one workgroup per stream: cLN of the last layer, fc1 / fc2, exp(3.2 tanh), energy normalisation (prefix or fixed),
 //                     then the resynthesis of one output hop (band-gain interpolation, iFFT, Hann window, overlap-add / window sum-square)
+//   rt_rule_kernel    (nele_rt_rule_*) in place of the layer and head kernels: SII-optimal band gains (siiopt.h) on the front's row, then
+//                     the head's course from the mask on - two launches per hop, no weights
 // Every stream owns a fixed record of the state buffer; inactive or finished slots return at once.  A slot's arithmetic never depends on
 // the other slots or on how its hops were grouped into calls: bit-reproducible per slot.
 // This file is compiled with -ffp-contract=off (Makefile EXACT): the feature and IMCRA arithmetic mirrors numpy's operation order.
@@ -16,7 +18,10 @@
 #include "featmath.h"
 #include "imcra.h"
 #include "slot_state.h"
+#include "siiopt.h"
 #include "../../include/nele_hip.h"
+
+int siiopt_check(const char* name, const double* gamma, double lam, double strength);      // siiopt.hip
 
 namespace {
 
@@ -428,6 +433,56 @@ __global__ __launch_bounds__(256) void rt_layer_kernel(RtArgs a, const void* __r
     }
 }
 
+// ============================================================================================ from the mask on (head and rule kernels)
+// Frame f of slot b, wave 0, lane = band: the mask value mk -> alpha^2 by the prefix or the fixed normalisation, into the record's
+// alpha^2 row of the frame's parity and the debug outputs.  SP / SMP: the slot's running float64 sums (prefix normalisation).
+__device__ __forceinline__ void rt_mask_tail(const RtArgs& a, int b, int f, int lane, float mk, const float* cbr, float* a2r, double& SP,
+                                             double& SMP) {
+    float a2;
+    if (a.beta2) {
+        a2 = mk * a.beta2[b];
+    } else {                                                 // prefix energy normalisation, float64 running sums
+        const double p = (double)nele_powi_f32(cbr[(f & 1) * 64 + lane], 6.0f);
+        SP += wave_sum(p);
+        SMP += wave_sum((double)mk * p);
+        const double ratio = SMP > 0.0 ? SP / SMP : 1.0;
+        a2 = (float)((double)mk * ratio);
+    }
+    a2r[(f & 1) * 64 + lane] = a2;
+    if (a.dbg_mask && f < a.dbg_frames) a.dbg_mask[((size_t)b * a.dbg_frames + f) * 64 + lane] = mk;
+    if (a.dbg_alpha2 && f < a.dbg_frames) a.dbg_alpha2[((size_t)b * a.dbg_frames + f) * 64 + lane] = a2;
+}
+
+// Output hop fa = fb - 1 of slot b, fb the newest frame: second half of frame fa + first half of frame fb (features.hip
+// gain_istft_kernel).  The whole workgroup of 256 threads, after a barrier behind the last rt_mask_tail.
+__device__ __forceinline__ void rt_resynth(const RtArgs& a, int b, const unsigned char* rec, Fft512Lds& s, int tid, int fb) {
+    const int fa = fb - 1;
+    const float* a2r = reinterpret_cast<const float*>(rec + RT_O_A2);
+    const float* a2a = a2r + (fa & 1) * 64;
+    const float* a2b = a2r + (fb & 1) * 64;
+    const float2* specr = reinterpret_cast<const float2*>(rec + RT_O_SPEC);
+    const float2* Xa = specr + (fa & 1) * NELE_NBINS;
+    const float2* Xb = specr + (fb & 1) * NELE_NBINS;
+    fft512_init_twiddles(s);
+    for (int kk = tid; kk < NELE_NBINS; kk += 256) {
+        const double ga = band_gain_sqrt(a2a, kk), gb = band_gain_sqrt(a2b, kk);
+        const float2 xa = Xa[kk], xb = Xb[kk];
+        double ar = ga * (double)xa.x, ai = ga * (double)xa.y;
+        double br = gb * (double)xb.x, bi = gb * (double)xb.y;
+        if (kk == 0 || kk == NELE_NBINS - 1) { ai = 0.0; bi = 0.0; }
+        s.x[fft512_brev(kk)] = make_double2(ar - bi, ai + br);
+        if (kk >= 1 && kk <= 255) s.x[fft512_brev(NELE_NFFT - kk)] = make_double2(ar + bi, br - ai);
+    }
+    __syncthreads();
+    fft512_run<true>(s);
+    {
+        const int n = tid;
+        const double x1 = s.x[n + 256].x * (1.0 / 512.0);
+        const double x2 = s.x[n].y * (1.0 / 512.0);
+        a.out[(size_t)b * a.ld + n] = istft_ola(x1, x2, hann512(n + 256), hann512(n));
+    }
+}
+
 // ============================================================================================ head + normalisation + resynthesis
 template <bool BF16>
 __global__ __launch_bounds__(256) void rt_head_kernel(RtArgs a, const float* __restrict__ params) {
@@ -476,19 +531,7 @@ __global__ __launch_bounds__(256) void rt_head_kernel(RtArgs a, const float* __r
             o = o + params[RT_FC2B + lane];
             const float mk = expf(3.2f * tanhf(o));
             msk[lane] = mk;
-            float a2;
-            if (a.beta2) {
-                a2 = mk * a.beta2[b];
-            } else {                                                 // prefix energy normalisation, float64 running sums
-                const double p = (double)nele_powi_f32(cbr[(f & 1) * 64 + lane], 6.0f);
-                SP += wave_sum(p);
-                SMP += wave_sum((double)mk * p);
-                const double ratio = SMP > 0.0 ? SP / SMP : 1.0;
-                a2 = (float)((double)mk * ratio);
-            }
-            a2r[(f & 1) * 64 + lane] = a2;
-            if (a.dbg_mask && f < a.dbg_frames) a.dbg_mask[((size_t)b * a.dbg_frames + f) * 64 + lane] = mk;
-            if (a.dbg_alpha2 && f < a.dbg_frames) a.dbg_alpha2[((size_t)b * a.dbg_frames + f) * 64 + lane] = a2;
+            rt_mask_tail(a, b, f, lane, mk, cbr, a2r, SP, SMP);
         }
         __syncthreads();
     }
@@ -498,31 +541,43 @@ __global__ __launch_bounds__(256) void rt_head_kernel(RtArgs a, const float* __r
         nsum[0] = SP; nsum[1] = SMP;
     }
     if (!emit) return;
-    // ---- output hop fa = newest frame - 1: second half of frame fa + first half of frame fa + 1 (features.hip gain_istft_kernel)
-    const int fb = f0 + nf - 1, fa = fb - 1;
-    const float* a2a = a2r + (fa & 1) * 64;
-    const float* a2b = a2r + (fb & 1) * 64;
-    const float2* specr = reinterpret_cast<const float2*>(rec + RT_O_SPEC);
-    const float2* Xa = specr + (fa & 1) * NELE_NBINS;
-    const float2* Xb = specr + (fb & 1) * NELE_NBINS;
-    fft512_init_twiddles(s);
-    for (int kk = tid; kk < NELE_NBINS; kk += 256) {
-        const double ga = band_gain_sqrt(a2a, kk), gb = band_gain_sqrt(a2b, kk);
-        const float2 xa = Xa[kk], xb = Xb[kk];
-        double ar = ga * (double)xa.x, ai = ga * (double)xa.y;
-        double br = gb * (double)xb.x, bi = gb * (double)xb.y;
-        if (kk == 0 || kk == NELE_NBINS - 1) { ai = 0.0; bi = 0.0; }
-        s.x[fft512_brev(kk)] = make_double2(ar - bi, ai + br);
-        if (kk >= 1 && kk <= 255) s.x[fft512_brev(NELE_NFFT - kk)] = make_double2(ar + bi, br - ai);
+    rt_resynth(a, b, rec, s, tid, f0 + nf - 1);
+}
+
+// ============================================================================================ the rule in the generator's place
+// SII-optimal band gains (siiopt.h) on the front's 128-wide row, then rt_head_kernel's course from the mask on.
+// One workgroup per stream; wave 0 runs the frames (lane = band).  Sbar [64] float64 is the rule's only state: it lies where the
+// generator's layer-1 history ring does, which nothing touches in this mode (nele_rt_reset zeroes it with the record).
+constexpr long long RT_O_SBAR = rt_act_off(1);
+static_assert(RT_O_SBAR % 8 == 0 && RT_O_SBAR + 8 * 64 <= rt_act_off(2), "Sbar inside the idle layer-1 ring");
+__global__ __launch_bounds__(256) void rt_rule_kernel(RtArgs a, const double* __restrict__ gamma, double lam, double strength) {
+    __shared__ Fft512Lds s;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    if (b >= a.S) return;
+    unsigned char* rec = rt_rec(a, b);
+    const RtHead* hd = rt_head(rec);
+    const int nf = hd->nf, f0 = hd->f0, emit = hd->emit;
+    if (nf == 0) return;
+    if (tid < 64) {
+        const float* cbr = reinterpret_cast<const float*>(rec + RT_O_CB);
+        float* a2r = reinterpret_cast<float*>(rec + RT_O_A2);
+        double* nsum = reinterpret_cast<double*>(rec + RT_O_NSUM);
+        double* sbar = reinterpret_cast<double*>(rec + RT_O_SBAR);
+        const float* act0 = rt_act(rec, 0);
+        const double g = gamma[lane];
+        double SP = 0.0, SMP = 0.0, Sbar = 0.0;
+        if (f0 > 0) { SP = nsum[0]; SMP = nsum[1]; Sbar = sbar[lane]; }
+        for (int f = f0; f < f0 + nf; ++f) {
+            const float* row = act0 + (f % RT_RING) * 128;
+            const float mk = siiopt_frame(Sbar, row[lane], row[64 + lane], g, f, lam, strength);
+            rt_mask_tail(a, b, f, lane, mk, cbr, a2r, SP, SMP);
+        }
+        sbar[lane] = Sbar;
+        if (tid == 0) { nsum[0] = SP; nsum[1] = SMP; }
     }
+    if (!emit) return;
     __syncthreads();
-    fft512_run<true>(s);
-    {
-        const int n = tid;
-        const double x1 = s.x[n + 256].x * (1.0 / 512.0);
-        const double x2 = s.x[n].y * (1.0 / 512.0);
-        a.out[(size_t)b * a.ld + n] = istft_ola(x1, x2, hann512(n + 256), hann512(n));
-    }
+    rt_resynth(a, b, rec, s, tid, f0 + nf - 1);
 }
 
 // ============================================================================================ weights, reset
@@ -651,5 +706,59 @@ extern "C" int nele_rt_finish(void* state, long long state_bytes, int max_stream
     if (precision == NELE_PREC_BF16) rt_launch_chain<true>(a, as_stream(stream));
     else rt_launch_chain<false>(a, as_stream(stream));
     NELE_CHECK_LAUNCH("nele_rt_finish");
+    return NELE_OK;
+}
+
+// ---- the rule in the generator's place (include/nele_hip_ext5.h): rt_front_kernel, then rt_rule_kernel - two launches per hop
+extern "C" int nele_rt_rule_hop(void* state, long long state_bytes, int max_streams, const double* gamma, double lam, double strength,
+                                const float* clean, const float* noise, const unsigned char* active, int nh, const float* beta2, float* out,
+                                float* dbg_band, float* dbg_noise, float* dbg_mask, float* dbg_alpha2, int dbg_frames, void* stream) {
+    int st = rt_check("nele_rt_rule_hop", state, state_bytes, max_streams, NELE_PREC_F32);
+    if (st) return st;
+    if ((st = siiopt_check("nele_rt_rule_hop", gamma, lam, strength))) return st;
+    NELE_CHECK_ARG(clean && noise && out, "nele_rt_rule_hop: null clean / noise / out");
+    NELE_CHECK_ARG(nh >= 1, "nele_rt_rule_hop: nh=%d must be >= 1", nh);
+    NELE_CHECK_ARG(dbg_frames >= 0 && (dbg_frames > 0 || !(dbg_band || dbg_noise || dbg_mask || dbg_alpha2)),
+                   "nele_rt_rule_hop: dbg_frames=%d with debug outputs", dbg_frames);
+    RtArgs a{};
+    a.state = (unsigned char*)state;
+    a.S = max_streams;
+    a.ld = (long long)nh * NELE_HOP;
+    a.active = active;
+    a.beta2 = beta2;
+    a.dbg_band = dbg_band; a.dbg_noise = dbg_noise; a.dbg_mask = dbg_mask; a.dbg_alpha2 = dbg_alpha2; a.dbg_frames = dbg_frames;
+    for (int h = 0; h < nh; ++h) {
+        a.clean = clean + (size_t)h * NELE_HOP;
+        a.noise = noise + (size_t)h * NELE_HOP;
+        a.out = out + (size_t)h * NELE_HOP;
+        hipLaunchKernelGGL(rt_front_kernel, dim3(a.S), dim3(RT_FRONT_THREADS), 0, as_stream(stream), a);
+        hipLaunchKernelGGL(rt_rule_kernel, dim3(a.S), dim3(256), 0, as_stream(stream), a, gamma, lam, strength);
+    }
+    NELE_CHECK_LAUNCH("nele_rt_rule_hop");
+    return NELE_OK;
+}
+
+extern "C" int nele_rt_rule_finish(void* state, long long state_bytes, int max_streams, const double* gamma, double lam, double strength,
+                                   const float* clean_tail, const float* noise_tail, const int* tail_lengths, const float* beta2, float* out,
+                                   float* dbg_band, float* dbg_noise, float* dbg_mask, float* dbg_alpha2, int dbg_frames, void* stream) {
+    int st = rt_check("nele_rt_rule_finish", state, state_bytes, max_streams, NELE_PREC_F32);
+    if (st) return st;
+    if ((st = siiopt_check("nele_rt_rule_finish", gamma, lam, strength))) return st;
+    NELE_CHECK_ARG(clean_tail && noise_tail && tail_lengths && out, "nele_rt_rule_finish: null clean_tail / noise_tail / tail_lengths / out");
+    NELE_CHECK_ARG(dbg_frames >= 0 && (dbg_frames > 0 || !(dbg_band || dbg_noise || dbg_mask || dbg_alpha2)),
+                   "nele_rt_rule_finish: dbg_frames=%d with debug outputs", dbg_frames);
+    RtArgs a{};
+    a.state = (unsigned char*)state;
+    a.S = max_streams;
+    a.ld = NELE_HOP;
+    a.clean = clean_tail;
+    a.noise = noise_tail;
+    a.tail = tail_lengths;
+    a.beta2 = beta2;
+    a.out = out;
+    a.dbg_band = dbg_band; a.dbg_noise = dbg_noise; a.dbg_mask = dbg_mask; a.dbg_alpha2 = dbg_alpha2; a.dbg_frames = dbg_frames;
+    hipLaunchKernelGGL(rt_front_kernel, dim3(a.S), dim3(RT_FRONT_THREADS), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(rt_rule_kernel, dim3(a.S), dim3(256), 0, as_stream(stream), a, gamma, lam, strength);
+    NELE_CHECK_LAUNCH("nele_rt_rule_finish");
     return NELE_OK;
 }

@@ -333,15 +333,24 @@ def score_rooms(clean_path, noise_path, enhanced_names, bank, batch=32, metrics=
     return res
 
 
-BASELINES = ('clean', 'ssdrc')
+BASELINES = ('clean', 'ssdrc', 'siiopt')
 
 
-def baseline_files(tag, clean_files, work_dir, batch=32):
+def baseline_files(tag, clean_files, work_dir, batch=32, noise_path=None):
     """The files a baseline is scored from, named like the clean files: 'clean' - the unprocessed speech itself; 'ssdrc' - SSDRC of every
-    clean file (ssdrc.py), written as PCM_16 under ``work_dir/baseline_ssdrc/MultiEnh/`` like every enhanced file that is scored."""
+    clean file (ssdrc.py), written as PCM_16 under ``work_dir/baseline_ssdrc/MultiEnh/`` like every enhanced file that is scored;
+    'siiopt' - the SII-optimal rule (siiopt.py) on every clean file against its noise file under ``noise_path``, likewise under
+    ``work_dir/baseline_siiopt/MultiEnh/``."""
     import os
     if tag == 'clean':
         return list(clean_files)
+    if tag == 'siiopt':
+        if noise_path is None:
+            raise ValueError("baseline 'siiopt' adapts to the noise: it needs noise_path")
+        from . import siiopt as _siiopt
+        root = os.path.join(work_dir, 'baseline_siiopt')
+        _siiopt.siiopt_corpus(clean_files, noise_path, root, batch=batch)
+        return [os.path.join(root, 'MultiEnh', f.split('/')[-1]) for f in clean_files]
     if tag != 'ssdrc':
         raise ValueError("baseline must be one of %s" % (BASELINES,))
     from . import ssdrc as _ssdrc
@@ -352,11 +361,11 @@ def baseline_files(tag, clean_files, work_dir, batch=32):
 
 def score_baseline(tag, clean_path, noise_path, clean_files, work_dir, groups=('Cafeteria', 'AirportAnnouncement'), bank=None, batch=32, quality=None,
                    out=None):
-    """eval_metrics.py:107-108: a baseline (``tag``: 'clean' or 'ssdrc') through the very path the generator's files take - score_enhanced
+    """eval_metrics.py:107-108: a baseline (``tag``: 'clean', 'ssdrc' or 'siiopt') through the very path the generator's files take - score_enhanced
     per noise group and, with ``bank``, score_rooms per RIR.  -> (score_enhanced's dict, score_rooms' dict or None)."""
     import sys
     out = sys.stdout if out is None else out
-    names = baseline_files(tag, clean_files, work_dir, batch=batch)
+    names = baseline_files(tag, clean_files, work_dir, batch=batch, noise_path=noise_path)
     out.write('baseline %s\n' % tag)
     res = score_enhanced(clean_path, noise_path, names, groups=groups, quality=quality, out=out)
     rooms = score_rooms(clean_path, noise_path, names, bank, batch=batch, out=out) if bank is not None else None
@@ -371,6 +380,9 @@ def main(argv=None):
     from . import dataio
     ap = argparse.ArgumentParser(prog='python -m nele_gan_amd.inference', description=main.__doc__)
     ap.add_argument('--chkpt', default=None, help="checkpoint with an 'enhance-model' entry (reference checkpoints load unchanged); default: random weights")
+    ap.add_argument('--rule', choices=('siiopt',), default=None, help="instead of --chkpt: a training-free rule in the generator's place - 'siiopt', SII-optimal band gains "
+                                                                      "on the noise estimate (no checkpoint needed)")
+    ap.add_argument('--rule-strength', type=float, default=0.5, help='with --rule siiopt: exponent on the optimal gain, in (0, 1]')
     ap.add_argument('--clean', required=True)
     ap.add_argument('--noise', required=True)
     ap.add_argument('--output', default='./output_inference')
@@ -384,7 +396,8 @@ def main(argv=None):
     ap.add_argument('--rir', default=None, help="with --score: folder of 16 kHz room impulse responses; the files are also scored in the room their name gives "
                                                 "('<utt>#<rir>#...wav'), reported per RIR")
     ap.add_argument('--baseline', action='append', choices=BASELINES, default=None,
-                    help="with --score: also score a baseline beside the generator - 'ssdrc' (SSDRC of the clean files) or 'clean' (the unprocessed speech); may repeat")
+                    help="with --score: also score a baseline beside the generator - 'ssdrc' (SSDRC of the clean files), 'siiopt' (SII-optimal band gains against the noise "
+                         "files) or 'clean' (the unprocessed speech); may repeat")
     from . import roomsynth as _rs
     _rs.add_cli_arguments(ap)
     from . import quality as _q
@@ -396,9 +409,18 @@ def main(argv=None):
         ap.error('--baseline needs --score')
     if a.score_quality and not a.score:
         ap.error('--score-quality needs --score')
+    if a.rule and a.chkpt:
+        ap.error('--rule takes the place of --chkpt; pass one of them')
     _q.backends_from_cli(a)
-    e = Enhancer(a.chkpt, norm=a.norm)
-    e.G.precision = a.precision
+    if a.rule:
+        from . import siiopt as _siiopt
+        try:
+            e = Enhancer(G=_siiopt.SiiOptRule(a.rule_strength), norm=a.norm)
+        except ValueError as err:
+            ap.error(str(err))
+    else:
+        e = Enhancer(a.chkpt, norm=a.norm)
+        e.G.precision = a.precision
     files = sorted(dataio.get_filepaths(a.clean))
     noise = a.noise.rstrip('/') + '/'
     out = enhance_files(e, files, noise, a.output, batch=a.batch)

@@ -57,16 +57,25 @@ class RealtimeEnhancer(SlotState):
     is 'prefix' whatever the checkpoint records.  The matching training and offline modes - the same arithmetic bit for bit - are
     ``train_nele.GanTrainer(norm='prefix')`` and ``inference.Enhancer(norm='prefix')``.
 
+    rule: a ``siiopt.SiiOptRule`` in the generator's place: no checkpoint, no ``G`` and no weights - per hop the
+    front kernel and one rule kernel (``nele_rt_rule_hop``); ``precision`` then means nothing.  ``process``, ``finish``, ``reset`` and
+    ``RealtimeDebug`` are what they are with a generator, and every wrapper of this class takes the object as it is.
+
     Host bookkeeping: ``hops[s]`` (hops received), ``emitted[s]`` (output samples produced), ``finished[s]``."""
 
-    def __init__(self, chkpt_path=None, G=None, streams=1, precision='bf16', norm='prefix', device='cuda'):
+    def __init__(self, chkpt_path=None, G=None, streams=1, precision='bf16', norm='prefix', device='cuda', rule=None):
         if precision not in _PREC:
             raise ValueError("RealtimeEnhancer: precision must be 'f32' or 'bf16' (got %r)" % (precision,))
+        if rule is not None and (chkpt_path is not None or G is not None):
+            raise ValueError("RealtimeEnhancer: rule takes the generator's place; pass no chkpt_path and no G with it")
+        if rule is not None and not hasattr(rule, 'rt_args'):
+            raise ValueError("RealtimeEnhancer: rule must be a siiopt.SiiOptRule")
         super().__init__(streams)
         self._alloc(device, _lib.lib.nele_rt_state_bytes(self.S))
         self.precision = precision
         self.prec = _PREC[precision]
-        if G is None:
+        self.rule = rule
+        if G is None and rule is None:
             G = M.Generator_Conv1D_cLN()
             if chkpt_path is not None:
                 G.load_state_dict(torch.load(chkpt_path, map_location='cpu')['enhance-model'])
@@ -82,7 +91,10 @@ class RealtimeEnhancer(SlotState):
         self.emitted = np.zeros(self.S, dtype=np.int64)
         self.finished = np.zeros(self.S, dtype=bool)
         self._params = None
-        self._load(G, init=True)
+        if rule is not None:
+            call('nele_rt_reset', ptr(self.state), c_longlong(self.nbytes), self.S, None, stream())
+        else:
+            self._load(G, init=True)
 
     # ---- weights
     def _load(self, G, init):
@@ -95,7 +107,15 @@ class RealtimeEnhancer(SlotState):
 
     def update_weights(self, G):
         """Take the current parameters of generator G (e.g. after a training step); the streams' state is kept."""
+        if self.rule is not None:
+            raise ValueError("RealtimeEnhancer.update_weights: this enhancer runs a rule, it has no weights")
         self._load(G, init=False)
+
+    def _entry(self, what):
+        """-> (entry point, the arguments between max_streams and the signals): the generator's precision or the rule's parameters"""
+        if self.rule is not None:
+            return 'nele_rt_rule_' + what, self.rule.rt_args(self.device)
+        return 'nele_rt_' + what, [self.prec]
 
     # ---- streaming
     def process(self, clean, noise, active=None, debug=None):
@@ -113,8 +133,8 @@ class RealtimeEnhancer(SlotState):
         act = None if active is None else self._dev_bytes(act_host)
         out = torch.empty((self.S, nh * HOP), dtype=torch.float32, device=self.device)
         dbg = debug.args() if debug is not None else _nodbg()
-        call('nele_rt_hop', ptr(self.state), c_longlong(self.nbytes), self.S, self.prec, ptr(c), ptr(n), ptr(act), nh, ptr(self.beta2),
-             ptr(out), *dbg, stream())
+        fn, how = self._entry('hop')
+        call(fn, ptr(self.state), c_longlong(self.nbytes), self.S, *how, ptr(c), ptr(n), ptr(act), nh, ptr(self.beta2), ptr(out), *dbg, stream())
         advance(self.hops, self.emitted, act_host & ~self.finished, nh)
         return out
 
@@ -142,8 +162,8 @@ class RealtimeEnhancer(SlotState):
         t = torch.from_numpy(tails).pin_memory().to(self.device, non_blocking=True)
         out = torch.empty((self.S, HOP), dtype=torch.float32, device=self.device)
         dbg = debug.args() if debug is not None else _nodbg()
-        call('nele_rt_finish', ptr(self.state), c_longlong(self.nbytes), self.S, self.prec, ptr(c), ptr(n), ptr(t), ptr(self.beta2), ptr(out),
-             *dbg, stream())
+        fn, how = self._entry('finish')
+        call(fn, ptr(self.state), c_longlong(self.nbytes), self.S, *how, ptr(c), ptr(n), ptr(t), ptr(self.beta2), ptr(out), *dbg, stream())
         self.emitted[slots] += HOP
         self.finished[slots] = True
         return out.index_select(0, torch.from_numpy(slots).to(self.device))

@@ -273,7 +273,8 @@ class _PendingBatch:
 class GanTrainer:
     # Defaults of what the constructor, enable_clean_cache() or fit() set on the instance - class attributes, so that a trainer assembled
     # without the constructor (the epoch tests' doubles) has them too.
-    multienh = None                 # fit(multienh='ssdrc'): a batch without 'drc' then gets ssdrc.ssdrc(clean) as its pre-enhanced example
+    multienh = None                 # fit(multienh='ssdrc'): a batch without 'drc' then gets ssdrc.ssdrc(clean) as its pre-enhanced example;
+                                    # 'siiopt': the SII-optimal rule's output for the batch's clean and noise rows (siiopt.pre_enhance)
     room = None
     quality_scorer = None
     # a device-side quality scorer's chain (quality.HasqiScorer) rides on the metric stream of this metric - 'estoi': the features / ESTOI
@@ -1511,7 +1512,7 @@ class GanTrainer:
         for.  -> _PendingBatch"""
         lens, frames = b.get('lengths'), f.get('frames')
         dl = b.get('drc_lengths', lens)
-        lazy = self.multienh == 'ssdrc' and b.get('drc') is None   # the pre-enhanced example is made here, when it is needed
+        lazy = self.multienh in ('ssdrc', 'siiopt') and b.get('drc') is None   # the pre-enhanced example is made here, when it is needed
         kw = self._batch_kw(b)
         # With the clean-signal cache on, the pre-enhanced examples' D items are kept per utterance key (_PreEnhancedItems); a batch whose
         # utterances are all known skips the DRC file's STFT and its three metric calls altogether.
@@ -1522,7 +1523,14 @@ class GanTrainer:
         # it - nothing of them is kept
         dcache = self._drc_cache if b.get('noise_key') is None else None
         drc_items, miss = dcache.lookup(dkeys) if (dkeys is not None and dcache is not None) else (None, None)
-        if lazy and (drc_items is None or miss):
+        if lazy and self.multienh == 'siiopt' and (drc_items is None or miss):
+            # the rule's output for these clean and noise rows as a PCM_16 file of it reads back (siiopt.py): bit-identical to the folder
+            # route; 256 * (n // 256) samples per row
+            from . import siiopt as _siiopt
+            drc, dl = _siiopt.pre_enhance(b['clean'], b['noise'], lens)
+            lh0 = b.get('lengths_host')
+            b = dict(b, drc=drc, drc_lengths=dl, drc_lengths_host=None if lh0 is None else (np.asarray(lh0) // 256) * 256)
+        elif lazy and (drc_items is None or miss):
             # SSDRC of the clean rows as a PCM_16 file of it reads back (ssdrc.py): bit-identical to the folder route; utterances whose
             # pre-enhanced D items are all cached need none
             from . import ssdrc as _ssdrc
@@ -1617,12 +1625,14 @@ class GanTrainer:
         ``multienh='ssdrc'`` (``train_enh_path`` is then None): the pre-enhanced example of every training utterance is the SSDRC of its
         clean signal, computed on the GPU (ssdrc.py) instead of read from a folder - bit-identical to reading the files
         ``python -m nele_gan_amd.ssdrc`` writes; with ``mixer`` a run needs clean speech and a noise pool alone.
+        ``multienh='siiopt'``: likewise the output of the SII-optimal rule (siiopt.py) for each batch's clean AND noise
+        rows - an example that depends on the noise - bit-identical to the files ``python -m nele_gan_amd.siiopt`` writes.
         The shuffles use Python's global generator, seeded by the constructor like train_nele.py:28."""
         from . import dataio
-        if multienh not in (None, 'ssdrc'):
-            raise ValueError("fit: multienh must be None or 'ssdrc'")
+        if multienh not in (None, 'ssdrc', 'siiopt'):
+            raise ValueError("fit: multienh must be None, 'ssdrc' or 'siiopt'")
         if multienh is not None and train_enh_path is not None:
-            raise ValueError("fit: multienh='ssdrc' makes the pre-enhanced examples itself; pass no train_enh_path")
+            raise ValueError("fit: multienh=%r makes the pre-enhanced examples itself; pass no train_enh_path" % (multienh,))
         self.multienh = multienh
         if rir_bank is not None:
             if self.room is None:
@@ -1837,8 +1847,9 @@ def build_parser():
     ap.add_argument('--rir', default=None, help="folder of 16 kHz room impulse responses: targets are taken in the room a file's name gives ('<utt>#<rir>#...wav'; "
                                                 "no such RIR: anechoic)")
     ap.add_argument('--resample', action='store_true', help='resample --noise-pool files and --rir responses that are not at 16 kHz on the GPU instead of stopping on them')
-    ap.add_argument('--multienh', choices=('folder', 'ssdrc'), default='folder', help="pre-enhanced examples: the files under Train/MultiEnh (when the folder exists), "
-                                                                                       "or 'ssdrc': SSDRC of the clean files computed on the GPU (Train/MultiEnh is not read)")
+    ap.add_argument('--multienh', choices=('folder', 'ssdrc', 'siiopt'), default='folder',
+                    help="pre-enhanced examples: the files under Train/MultiEnh (when the folder exists), or 'ssdrc': SSDRC of the clean files, or "
+                         "'siiopt': the SII-optimal rule on the clean and noise files, both computed on the GPU (Train/MultiEnh is not read)")
     from . import roomsynth as _rs
     _rs.add_cli_arguments(ap)
     from . import quality as _q
@@ -1895,6 +1906,7 @@ def main(argv=None):
     enh_path = enh if (a.multienh == 'folder' and os.path.isdir(enh)) else None
     if ndist.rank() == 0:
         print('%d training files, %d validation files, %s' % (len(train), len(valid), 'pre-enhanced examples: SSDRC of the clean files' if a.multienh == 'ssdrc' else
+                                                              'pre-enhanced examples: SII-optimal band gains against the noise' if a.multienh == 'siiopt' else
                                                               'pre-enhanced examples: ' + enh if enh_path else 'no pre-enhanced examples'))
 
     def report(res):
@@ -1917,7 +1929,7 @@ def main(argv=None):
         tr.fit(train, None if mixer is not None else root + '/Train/Noise/', valid, valid_noise, train_enh_path=enh_path,
                epochs=a.epochs, sampling=a.sampling, valid_samples=a.valid_samples, batch=a.batch, output_path=a.output, pt_dir=a.chkpt, log_path=a.log,
                first_epoch=a.first_epoch, clean_cache=not a.no_cache, on_epoch=report, mixer=mixer,
-               rir_bank=bank, multienh='ssdrc' if a.multienh == 'ssdrc' else None)
+               rir_bank=bank, multienh=a.multienh if a.multienh in ('ssdrc', 'siiopt') else None)
     finally:
         if world > 1:
             import torch.distributed as tdist

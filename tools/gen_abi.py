@@ -14,8 +14,10 @@ and, when the tree has it, from include/nele_hip_ext3.h (the entry points added 
   nele_gan_amd/_abi_ext3.py        likewise, into dicts of their own again; a tree without that header is written and checked without it.
 and, when the tree has it, from include/nele_hip_ext4.h (the entry points added after nele_hip_ext3.h's fixed set)
   nele_gan_amd/_abi_ext4.py        likewise.
+and, when the tree has it, from include/nele_hip_ext5.h (the entry points added after nele_hip_ext4.h's fixed set)
+  nele_gan_amd/_abi_ext5.py        likewise.
 Run after changing a header; tests/test_capi_symbols.py, tests/test_abi_ext_cpu.py, tests/test_abi_ext2_cpu.py,
-tests/test_abi_ext3_cpu.py and tests/test_abi_ext4_cpu.py check that all are current.
+tests/test_abi_ext3_cpu.py, tests/test_abi_ext4_cpu.py and tests/test_abi_ext5_cpu.py check that all are current.
     python tools/gen_abi.py            # rewrite the files
     python tools/gen_abi.py --check    # exit 1 when a committed file differs
 A code is the ctypes type's name without its 'c_'.  The map is fixed: a scalar type outside it stops the tool (never a default)."""
@@ -152,6 +154,10 @@ if __name__ == '__main__':
     fifth = os.path.exists(os.path.join(ROOT, 'include', 'nele_hip_ext4.h'))     # likewise
     if fifth:
         outputs += ((os.path.join(ROOT, 'nele_gan_amd', '_abi_ext4.py'), emit_abi('nele_hip_ext4.h')),)
+    sixth = os.path.exists(os.path.join(ROOT, 'include', 'nele_hip_ext5.h'))     # likewise
+    n_before_sixth = len(outputs)
+    if sixth:
+        outputs += ((os.path.join(ROOT, 'nele_gan_amd', '_abi_ext5.py'), emit_abi('nele_hip_ext5.h')),)
     if '--check' in sys.argv:
         sys.exit(0 if all(os.path.exists(path) and open(path).read() == text for path, text in outputs) else 1)
     for path, text in outputs:
@@ -161,6 +167,8 @@ if __name__ == '__main__':
     if third:
         print('wrote %s (%d entry points)' % (outputs[3][0], len(funcs(_header('nele_hip_ext2.h')))))
     if fourth:
-        print('wrote %s (%d entry points)' % (outputs[-2 if fifth else -1][0], len(funcs(_header('nele_hip_ext3.h')))))
+        print('wrote %s (%d entry points)' % (outputs[:n_before_sixth][-2 if fifth else -1][0], len(funcs(_header('nele_hip_ext3.h')))))
     if fifth:
-        print('wrote %s (%d entry points)' % (outputs[-1][0], len(funcs(_header('nele_hip_ext4.h')))))
+        print('wrote %s (%d entry points)' % (outputs[n_before_sixth - 1][0], len(funcs(_header('nele_hip_ext4.h')))))
+    if sixth:
+        print('wrote %s (%d entry points)' % (outputs[-1][0], len(funcs(_header('nele_hip_ext5.h')))))
