@@ -427,6 +427,7 @@ static int gap_mlp_bwd_impl(const float* dscore, const float* score, const float
                             int oh0, int ow0, float* dz3, float* dz2, float* dz1, float* dpooled, void* gbuf, int gbuf_bf16, void* stream,
                             int act_bf16 = 0) {
     NELE_CHECK_ARG(dscore && score && h1 && h2 && mlp_host && dz3 && dz2 && dz1 && dpooled && B > 0, "nele_gap_mlp_bwd: bad arguments");
+    NELE_CHECK_ARG(nout >= 1 && nout <= 4, "nele_gap_mlp_bwd: nout=%d (mlp_bwd_kernel holds dz3 in a 4-float LDS array)", nout);
     const float* const* mlp = mlp_host;
     MlpW w = {mlp[0], mlp[1], mlp[2], mlp[3], mlp[4], mlp[5], mlp[6], mlp[7], mlp[8]};
     hipStream_t s = as_stream(stream);
