@@ -1,6 +1,7 @@
-// Per-stream slot state as csrc/realtime.hip, csrc/aec.hip and csrc/resample_stream.hip lay it out: a header, then one 256-byte-aligned
-// record per slot, all in one caller-owned allocation.  Here, once: the alignment, the checks every entry point starts with, the reset
-// (one kernel, csrc/slot_state.hip) and the geometry header that the canceller's and the converter's kernels compare against.
+// Per-stream slot state as csrc/realtime.hip, csrc/aec.hip, csrc/resample_stream.hip and csrc/highband.hip lay it out: a header, then
+// one 256-byte-aligned record per slot, all in one caller-owned allocation.  Here, once: the alignment, the checks every entry point
+// starts with, the reset (one kernel, csrc/slot_state.hip) and the geometry header that the canceller's and the converters' kernels
+// compare against.
 #pragma once
 #include "common.h"
 
@@ -40,6 +41,10 @@ __device__ __forceinline__ bool slot_hdr_matches(const unsigned char* state, int
 __device__ __forceinline__ bool slot_hdr_matches(const unsigned char* state, int v0, int v1, int v2, int v3) {
     const int* hdr = reinterpret_cast<const int*>(state);
     return hdr[0] == v0 && hdr[1] == v1 && hdr[2] == v2 && hdr[3] == v3;
+}
+__device__ __forceinline__ bool slot_hdr_matches(const unsigned char* state, int v0, int v1, int v2, int v3, int v4, int v5) {
+    const int* hdr = reinterpret_cast<const int*>(state);
+    return slot_hdr_matches(state, v0, v1, v2, v3) && hdr[4] == v4 && hdr[5] == v5;
 }
 __device__ __forceinline__ bool slot_hdr_matches(const unsigned char* state, int v0, int v1, int v2, int v3, int v4, int v5, int v6) {
     const int* hdr = reinterpret_cast<const int*>(state);

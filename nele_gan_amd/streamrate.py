@@ -11,6 +11,12 @@ bookkeeping only; there is no arithmetic in torch.
     out = rt48.process(clean_hops, noise_hops)                 # [256, nh * 768] each, at 48 kHz -> [256, nh * 768] at 48 kHz
     rt44 = adapt(RealtimeEnhancer(chkpt, streams=256), device_rate=44100)
     out = rt44.process(clean_hops, noise_hops)                 # [256, rt44.width(nh)] each, at 44.1 kHz -> the same shape
+    full = adapt(RealtimeEnhancer(chkpt, streams=256), device_rate=48000, highband=True)
+    out = full.process(clean_hops, noise_hops)                 # the same shapes; what clean_hops holds above 8 kHz is in the output
+
+Without ``highband`` the output is band-limited to the 8 kHz the enhancer works on.  With it a ``HighBandUp`` (nele_gan_amd/highband.py,
+csrc/highband.hip) stands in the up-converter's place and adds, in the same launch, the part of ``clean`` that
+the 16 kHz path cannot carry, delayed by ``latency``.
 """
 import fractions
 
@@ -18,6 +24,8 @@ import numpy as np
 import torch
 
 from .aec import EchoCancellingEnhancer
+from .drc import CompressedEnhancer
+from .highband import HighBandUp, highband_plan
 from .realtime import HOP, RealtimeEnhancer
 from .resample import STREAM_RATE, ScheduledStreamResampler, StreamResampler, stream_plan
 from ._slots import dev_f32, dev_rows, host_flags
@@ -34,30 +42,54 @@ class RateAdaptedEnhancer:
     the device rate plus D_down at 16 kHz, 64 samples at 16 kHz for 48 kHz 'high': leave room for it in the canceller's partitions (DESIGN.md
     section 14).
 
+    ``highband``: None - the output holds the band up to 8 kHz only; True or a float g - a HighBandUp stands in the up-converter's place
+    and the output also holds g (1 for True) times what ``clean`` has above that band, time-aligned: one fused launch where the
+    up-converter's was.  ``latency`` is then the HighBandUp's ``lag`` for the hops the inner object's output is behind its input: 1 for a
+    RealtimeEnhancer, 2 for an EchoCancellingEnhancer whose ``rt`` is a CompressedEnhancer.  The canceller never sees the carried band -
+    the microphone's down-converter removes it - and a compressor inside the loop acts on the low band only.  ValueError before any GPU
+    call at rates that leave no band to carry or at which the path's delay is not a whole number of samples.
+
     Streams end through drain(): the inner path's finish() and its tails of less than a hop are not offered at the device rate."""
 
     CONVERTER = StreamResampler
 
-    def __init__(self, inner, device_rate, quality='high'):
+    def __init__(self, inner, device_rate, quality='high', highband=None):
         if not isinstance(inner, (RealtimeEnhancer, EchoCancellingEnhancer)):
             raise ValueError("%s: inner must be a RealtimeEnhancer or an EchoCancellingEnhancer (got %s)" % (type(self).__name__, type(inner).__name__))
         self.inner, self.S = inner, inner.S
         self.device_rate = int(device_rate)
         self.device = inner.device if isinstance(inner, RealtimeEnhancer) else inner.aec.device
         self._per_call = 1                                 # hops of the last call (an EchoCancellingEnhancer fixes them for its life)
+        self.highband = None if highband is None or highband is False else float(highband)     # g; True is 1.0
         if self.device_rate == STREAM_RATE:
             self.down = self.up = self._both = None
             self.hop, self.latency = HOP, HOP
             return
+        if self.highband is not None:
+            self._check_highband(quality)                  # ValueError before any GPU call
         # both constructors raise ValueError for an unsupported rate before any GPU call
         self.down = self.CONVERTER(2 * self.S, self.device_rate, STREAM_RATE, quality, self.device)
-        self.up = self.CONVERTER(self.S, STREAM_RATE, self.device_rate, quality, self.device)
+        if self.highband is None:
+            self.up = self.CONVERTER(self.S, STREAM_RATE, self.device_rate, quality, self.device)
+        else:
+            self.up = HighBandUp(self.S, self.device_rate, self._lag_hops(), quality, self.device)
+            self.up.gain.fill_(self.highband)
         self._both = None                                  # [2 S, width]: the two signals stacked for the down-converter
         self._set_latency()
 
+    def _lag_hops(self):
+        """hops by which the inner object's output is behind its input"""
+        rt = self.inner.rt if isinstance(self.inner, EchoCancellingEnhancer) else self.inner
+        return 2 if isinstance(rt, CompressedEnhancer) else 1
+
+    def _check_highband(self, quality):
+        if not np.isfinite(self.highband):
+            raise ValueError("%s: highband must be None, True or a finite gain (got %r)" % (type(self).__name__, self.highband))
+        highband_plan(self.device_rate, self._lag_hops(), quality)
+
     def _set_latency(self):
         self.hop = self.down.hop_in
-        self.latency = self.down.delay * self.hop // HOP + self.hop + self.up.delay
+        self.latency = self.down.delay * self.hop // HOP + self.hop + self.up.delay if self.highband is None else self.up.lag
 
     def _stack(self, clean, second, width):
         if self._both is None or self._both.shape[1] != width:
@@ -87,7 +119,9 @@ class RateAdaptedEnhancer:
     def _chain(self, clean, second, width, act):
         low = self.down.process(self._stack(clean, second, width), active=None if act is None else np.concatenate([act, act]))
         out = self.inner.process(low[:self.S], low[self.S:], active=act)
-        return self.up.process(out, active=act)
+        if self.highband is None:
+            return self.up.process(out, active=act)
+        return self.up.process(out, low[:self.S], self._both[:self.S], active=act)       # rows of the two buffers: no copy
 
     def drain(self, slots):
         """ceil(latency / hop) hops of zeros through the given slots -> their outputs [len(slots), ceil(latency / hop) * hop]: what is
@@ -126,6 +160,11 @@ class ScheduledRateEnhancer(RateAdaptedEnhancer):
     must stand at one position, and reset(slots) starts slots where the last process() call ended."""
 
     CONVERTER = ScheduledStreamResampler
+
+    def _check_highband(self, quality):
+        raise ValueError("ScheduledRateEnhancer: highband is not offered on a hop schedule: the latency there is not a whole number of "
+                         "samples (4414/5 at 44.1 kHz), and an exact complement of the low band needs a fractional delay of the input, "
+                         "which is not built")
 
     def _set_latency(self):
         r = fractions.Fraction(self.down._rnum, self.down.period)
@@ -182,14 +221,15 @@ class ScheduledRateEnhancer(RateAdaptedEnhancer):
             self.up.reset(slots, position)
 
 
-def adapt(inner, device_rate, quality='high'):
+def adapt(inner, device_rate, quality='high', highband=None):
     """``inner`` at ``device_rate``: a RateAdaptedEnhancer where that class accepts the rate (a 16 ms hop is a whole number of samples;
-    16 kHz passes straight through), a ScheduledRateEnhancer otherwise (44.1 kHz and its family)."""
+    16 kHz passes straight through), a ScheduledRateEnhancer otherwise (44.1 kHz and its family).  ``highband``: RateAdaptedEnhancer's;
+    a ValueError at the rates of a ScheduledRateEnhancer."""
     device_rate = int(device_rate)
     if device_rate != STREAM_RATE:
         try:
             stream_plan(device_rate, STREAM_RATE, quality)
             stream_plan(STREAM_RATE, device_rate, quality)
         except ValueError:
-            return ScheduledRateEnhancer(inner, device_rate, quality)
-    return RateAdaptedEnhancer(inner, device_rate, quality)
+            return ScheduledRateEnhancer(inner, device_rate, quality, highband)
+    return RateAdaptedEnhancer(inner, device_rate, quality, highband)

@@ -18,8 +18,11 @@ and, when the tree has it, from include/nele_hip_ext5.h (the entry points added 
   nele_gan_amd/_abi_ext5.py        likewise.
 and, when the tree has it, from include/nele_hip_ext6.h (the entry points added after nele_hip_ext5.h's fixed set)
   nele_gan_amd/_abi_ext6.py        likewise.
+and, when the tree has it, from include/nele_hip_ext7.h (the entry points added after nele_hip_ext6.h's fixed set)
+  nele_gan_amd/_abi_ext7.py        likewise.
 Run after changing a header; tests/test_capi_symbols.py, tests/test_abi_ext_cpu.py, tests/test_abi_ext2_cpu.py,
-tests/test_abi_ext3_cpu.py, tests/test_abi_ext4_cpu.py, tests/test_abi_ext5_cpu.py and tests/test_abi_ext6_cpu.py check that all are current.
+tests/test_abi_ext3_cpu.py, tests/test_abi_ext4_cpu.py, tests/test_abi_ext5_cpu.py, tests/test_abi_ext6_cpu.py and tests/test_abi_ext7_cpu.py check that
+all are current.
     python tools/gen_abi.py            # rewrite the files
     python tools/gen_abi.py --check    # exit 1 when a committed file differs
 A code is the ctypes type's name without its 'c_'.  The map is fixed: a scalar type outside it stops the tool (never a default)."""
@@ -164,6 +167,10 @@ if __name__ == '__main__':
     n_before_seventh = len(outputs)
     if seventh:
         outputs += ((os.path.join(ROOT, 'nele_gan_amd', '_abi_ext6.py'), emit_abi('nele_hip_ext6.h')),)
+    eighth = os.path.exists(os.path.join(ROOT, 'include', 'nele_hip_ext7.h'))    # likewise
+    n_before_eighth = len(outputs)
+    if eighth:
+        outputs += ((os.path.join(ROOT, 'nele_gan_amd', '_abi_ext7.py'), emit_abi('nele_hip_ext7.h')),)
     if '--check' in sys.argv:
         sys.exit(0 if all(os.path.exists(path) and open(path).read() == text for path, text in outputs) else 1)
     for path, text in outputs:
@@ -179,4 +186,6 @@ if __name__ == '__main__':
     if sixth:
         print('wrote %s (%d entry points)' % (outputs[n_before_seventh - 1][0], len(funcs(_header('nele_hip_ext5.h')))))
     if seventh:
-        print('wrote %s (%d entry points)' % (outputs[-1][0], len(funcs(_header('nele_hip_ext6.h')))))
+        print('wrote %s (%d entry points)' % (outputs[n_before_eighth - 1][0], len(funcs(_header('nele_hip_ext6.h')))))
+    if eighth:
+        print('wrote %s (%d entry points)' % (outputs[-1][0], len(funcs(_header('nele_hip_ext7.h')))))
