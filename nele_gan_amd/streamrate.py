@@ -16,7 +16,12 @@ bookkeeping only; there is no arithmetic in torch.
 
 Without ``highband`` the output is band-limited to the 8 kHz the enhancer works on.  With it a ``HighBandUp`` (nele_gan_amd/highband.py,
 csrc/highband.hip) stands in the up-converter's place and adds, in the same launch, the part of ``clean`` that
-the 16 kHz path cannot carry, delayed by ``latency``.
+the 16 kHz path cannot carry, delayed by ``latency``.  ``highband`` is offered where a hop is a whole number of samples;
+``adapt_fullband`` gives full-band output at every device rate above 16 kHz, 44.1 kHz and its family among them: there a
+``FullBandScheduledEnhancer`` with a ``ScheduledHighBandUp`` (csrc/highband_sched.hip) in the up-converter's place.
+
+    full44 = adapt_fullband(RealtimeEnhancer(chkpt, streams=256), device_rate=44100)
+    out = full44.process(clean_hops, noise_hops)               # [256, full44.width(nh)] each -> the same shape, 883 samples behind clean_hops
 """
 import fractions
 
@@ -25,7 +30,7 @@ import torch
 
 from .aec import EchoCancellingEnhancer
 from .drc import CompressedEnhancer
-from .highband import HighBandUp, highband_plan
+from .highband import HighBandUp, ScheduledHighBandUp, highband_plan, highband_sched_plan
 from .realtime import HOP, RealtimeEnhancer
 from .resample import STREAM_RATE, ScheduledStreamResampler, StreamResampler, stream_plan
 from ._slots import dev_f32, dev_rows, host_flags
@@ -52,6 +57,7 @@ class RateAdaptedEnhancer:
     Streams end through drain(): the inner path's finish() and its tails of less than a hop are not offered at the device rate."""
 
     CONVERTER = StreamResampler
+    HIGHBAND = HighBandUp
 
     def __init__(self, inner, device_rate, quality='high', highband=None):
         if not isinstance(inner, (RealtimeEnhancer, EchoCancellingEnhancer)):
@@ -72,7 +78,7 @@ class RateAdaptedEnhancer:
         if self.highband is None:
             self.up = self.CONVERTER(self.S, STREAM_RATE, self.device_rate, quality, self.device)
         else:
-            self.up = HighBandUp(self.S, self.device_rate, self._lag_hops(), quality, self.device)
+            self.up = self.HIGHBAND(self.S, self.device_rate, self._lag_hops(), quality, self.device)
             self.up.gain.fill_(self.highband)
         self._both = None                                  # [2 S, width]: the two signals stacked for the down-converter
         self._set_latency()
@@ -164,7 +170,8 @@ class ScheduledRateEnhancer(RateAdaptedEnhancer):
     def _check_highband(self, quality):
         raise ValueError("ScheduledRateEnhancer: highband is not offered on a hop schedule: the latency there is not a whole number of "
                          "samples (4414/5 at 44.1 kHz), and an exact complement of the low band needs a fractional delay of the input, "
-                         "which is not built")
+                         "which is not built (FullBandScheduledEnhancer and adapt_fullband carry the band on a hop schedule: they delay "
+                         "the up-converter instead)")
 
     def _set_latency(self):
         r = fractions.Fraction(self.down._rnum, self.down.period)
@@ -219,6 +226,44 @@ class ScheduledRateEnhancer(RateAdaptedEnhancer):
             slots = np.asarray(slots, dtype=np.int64).reshape(-1)
             self.down.reset(np.concatenate([slots, slots + self.S]), position)
             self.up.reset(slots, position)
+
+
+class FullBandScheduledEnhancer(ScheduledRateEnhancer):
+    """ScheduledRateEnhancer with a ScheduledHighBandUp in the up-converter's place: the output also holds ``gain`` times what ``clean``
+    has above the 8 kHz the enhancer works on, time-aligned, at every device rate above 16 kHz - 44.1 kHz and its family among them.  One
+    fused launch where the up-converter's was.  ``latency`` is a whole number of device-rate samples, the ScheduledHighBandUp's ``lag``
+    for the hops the inner object's output is behind its input (883 at 44.1 kHz with quality 'high' where ScheduledRateEnhancer has
+    4414/5: the up-converter runs ``up.shift`` / 160 of a sample late).  16 kHz passes straight through; ValueError before any allocation
+    for a rate below 16 kHz, which has no band to carry, and for a gain that is not finite."""
+
+    HIGHBAND = ScheduledHighBandUp
+
+    def __init__(self, inner, device_rate, quality='high', gain=1.0):
+        if gain is None or isinstance(gain, bool):
+            raise ValueError("FullBandScheduledEnhancer: gain must be a finite number (got %r)" % (gain,))
+        super().__init__(inner, device_rate, quality, float(gain))
+
+    def _check_highband(self, quality):
+        if not np.isfinite(self.highband):
+            raise ValueError("FullBandScheduledEnhancer: gain must be a finite number (got %r)" % self.highband)
+        highband_sched_plan(self.device_rate, self._lag_hops(), quality)
+
+    def _set_latency(self):
+        self.hop = None                                    # no one hop length: width(nh)
+        self.latency = self.up.lag
+
+
+def adapt_fullband(inner, device_rate, quality='high', gain=1.0):
+    """``inner`` at ``device_rate`` with the band above 8 kHz carried, ``gain`` times what ``clean`` holds there: RateAdaptedEnhancer(..,
+    highband=gain) where that class accepts the rate, a FullBandScheduledEnhancer otherwise (44.1 kHz and its family; a rate at which
+    the path's delay is a fraction of a sample).  16 kHz passes straight through; ValueError for a rate below 16 kHz (no band to carry)."""
+    device_rate = int(device_rate)
+    if device_rate > STREAM_RATE:
+        try:
+            highband_plan(device_rate, 1, quality)
+        except ValueError:
+            return FullBandScheduledEnhancer(inner, device_rate, quality, gain)
+    return RateAdaptedEnhancer(inner, device_rate, quality, float(gain))
 
 
 def adapt(inner, device_rate, quality='high', highband=None):

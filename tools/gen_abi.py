@@ -20,8 +20,10 @@ and, when the tree has it, from include/nele_hip_ext6.h (the entry points added 
   nele_gan_amd/_abi_ext6.py        likewise.
 and, when the tree has it, from include/nele_hip_ext7.h (the entry points added after nele_hip_ext6.h's fixed set)
   nele_gan_amd/_abi_ext7.py        likewise.
+and, when the tree has it, from include/nele_hip_ext8.h (the entry points added after nele_hip_ext7.h's fixed set)
+  nele_gan_amd/_abi_ext8.py        likewise.
 Run after changing a header; tests/test_capi_symbols.py, tests/test_abi_ext_cpu.py, tests/test_abi_ext2_cpu.py,
-tests/test_abi_ext3_cpu.py, tests/test_abi_ext4_cpu.py, tests/test_abi_ext5_cpu.py, tests/test_abi_ext6_cpu.py and tests/test_abi_ext7_cpu.py check that
+tests/test_abi_ext3_cpu.py, tests/test_abi_ext4_cpu.py, tests/test_abi_ext5_cpu.py, tests/test_abi_ext6_cpu.py, tests/test_abi_ext7_cpu.py and tests/test_abi_ext8_cpu.py check that
 all are current.
     python tools/gen_abi.py            # rewrite the files
     python tools/gen_abi.py --check    # exit 1 when a committed file differs
@@ -171,6 +173,10 @@ if __name__ == '__main__':
     n_before_eighth = len(outputs)
     if eighth:
         outputs += ((os.path.join(ROOT, 'nele_gan_amd', '_abi_ext7.py'), emit_abi('nele_hip_ext7.h')),)
+    ninth = os.path.exists(os.path.join(ROOT, 'include', 'nele_hip_ext8.h'))     # likewise
+    n_before_ninth = len(outputs)
+    if ninth:
+        outputs += ((os.path.join(ROOT, 'nele_gan_amd', '_abi_ext8.py'), emit_abi('nele_hip_ext8.h')),)
     if '--check' in sys.argv:
         sys.exit(0 if all(os.path.exists(path) and open(path).read() == text for path, text in outputs) else 1)
     for path, text in outputs:
@@ -188,4 +194,6 @@ if __name__ == '__main__':
     if seventh:
         print('wrote %s (%d entry points)' % (outputs[n_before_eighth - 1][0], len(funcs(_header('nele_hip_ext6.h')))))
     if eighth:
-        print('wrote %s (%d entry points)' % (outputs[-1][0], len(funcs(_header('nele_hip_ext7.h')))))
+        print('wrote %s (%d entry points)' % (outputs[n_before_ninth - 1][0], len(funcs(_header('nele_hip_ext7.h')))))
+    if ninth:
+        print('wrote %s (%d entry points)' % (outputs[-1][0], len(funcs(_header('nele_hip_ext8.h')))))
