@@ -50,7 +50,8 @@ class RateAdaptedEnhancer:
     ``highband``: None - the output holds the band up to 8 kHz only; True or a float g - a HighBandUp stands in the up-converter's place
     and the output also holds g (1 for True) times what ``clean`` has above that band, time-aligned: one fused launch where the
     up-converter's was.  ``latency`` is then the HighBandUp's ``lag`` for the hops the inner object's output is behind its input: 1 for a
-    RealtimeEnhancer, 2 for an EchoCancellingEnhancer whose ``rt`` is a CompressedEnhancer.  The canceller never sees the carried band -
+    RealtimeEnhancer, 2 for an EchoCancellingEnhancer whose ``rt`` is a CompressedEnhancer, and the ``lag_hops`` of a
+    limiter.LimitedEnhancer there (3 around a CompressedEnhancer; the carried band is added behind the limiter and is not limited).  The canceller never sees the carried band -
     the microphone's down-converter removes it - and a compressor inside the loop acts on the low band only.  ValueError before any GPU
     call at rates that leave no band to carry or at which the path's delay is not a whole number of samples.
 
@@ -86,6 +87,8 @@ class RateAdaptedEnhancer:
     def _lag_hops(self):
         """hops by which the inner object's output is behind its input"""
         rt = self.inner.rt if isinstance(self.inner, EchoCancellingEnhancer) else self.inner
+        if hasattr(rt, 'lag_hops'):                        # a limiter.LimitedEnhancer says so itself
+            return int(rt.lag_hops)
         return 2 if isinstance(rt, CompressedEnhancer) else 1
 
     def _check_highband(self, quality):
