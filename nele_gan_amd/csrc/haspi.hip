@@ -766,6 +766,12 @@ __device__ __forceinline__ void hp_ihc_step(const IhcC& k, double V0, double& V1
 // (:1080-1088) and pass 1 of the IHC adaptation ride along - the same arithmetic as haspi_gain_lp_sl_kernel on the same float32-rounded
 // |u|^2, so the result is bit-identical, but the envelope goes to memory once (as dB SL) instead of |u|^2 out, |u|^2 + control in, dB SL
 // out: 8.7 instead of 16 bytes per (sample, channel) over the two kernels.  The IHC chunks are the scan chunks then (ws.lcg = ws.lc).
+// The per-sample envelopes (ctl, env: 3.1 GB each per launch at B = 256) are written once and read once, by a later kernel, with
+// gigabytes of other traffic in between: no cache level can keep them.  Their stores and loads carry the nontemporal hint, so that they
+// stream past the caches instead of displacing what the kernels do reuse (see profiles/haspi_order/README.md for what that is worth).
+__device__ __forceinline__ void hp_store_once(hp_env_t* p, hp_env_t v) { __builtin_nontemporal_store(v, p); }
+__device__ __forceinline__ hp_env_t hp_load_once(const hp_env_t* p) { return __builtin_nontemporal_load(p); }
+
 template <bool SIGNAL, bool PASS2, bool BM = false, bool GAIN = false>
 __global__ __launch_bounds__(64) void haspi_bank_scan_kernel(HaspiWs ws, int sig0) {
     const int b = blockIdx.z, sig = sig0 + blockIdx.y, lane = threadIdx.x, ch = lane & 31;
@@ -824,16 +830,41 @@ __global__ __launch_bounds__(64) void haspi_bank_scan_kernel(HaspiWs ws, int sig
             }
         }
     }
-    for (int nb = n0; nb < n1; nb += GS_RC) {
-        double xc[GS_RC];
-        const hp_env_t* ctl_nb = ctl + (size_t)nb * HP_NCH;              // one 64-bit address per group, immediates per sample
-        hp_env_t* out_nb = out + (size_t)nb * HP_NCH;
-        float* cph_nb = BM ? cph + (size_t)nb * HP_NCH : nullptr;
+    // GAIN: the order of a group's memory operations.  Stores count in vmcnt like loads and the counter retires in issue order, so a
+    // load issued behind a group's stores is usable only once those stores are acknowledged.  The inputs of group g + 1 (xc, gc) are
+    // therefore requested at the END of group g, behind their last use - no register is added - and AHEAD of the group's stores; the
+    // first group's come from the prologue.  The waits of group g + 1 then leave the stores of group g in flight (vmcnt(16) and more
+    // in the disassembly); the stores they do require are a whole group old.  The group behind a chunk's last one would lie in another
+    // lane's chunk or behind the row: the last group requests itself again.  (The other instantiations keep their loads at the top of
+    // the group: measured, the control bank gains nothing from the new order, and the BM kernel's bits follow its block layout.)
+    constexpr bool AHEAD = GAIN;
+    double xc[GS_RC];
+    float gc[GAIN ? GS_RC : 1];
+    auto request = [&](int n) {
 #pragma unroll
         for (int u = 0; u < GS_RC / 2; ++u) {
-            const double2 v = *reinterpret_cast<const double2*>(xin + nb + 2 * u);
+            const double2 v = *reinterpret_cast<const double2*>(xin + n + 2 * u);
             xc[2 * u] = v.x; xc[2 * u + 1] = v.y;
         }
+        if (GAIN) {
+            const hp_env_t* ctl_n = ctl + (size_t)n * HP_NCH;            // one 64-bit address per group, immediates per sample
+#pragma unroll
+            for (int u = 0; u < GS_RC; ++u) gc[u] = hp_load_once(ctl_n + u * HP_NCH);
+        }
+    };
+    if (AHEAD) {
+        request(n0);
+        // The compiler's wait counts at the loop's head cover both ways into it: with the prologue's loads still pending there, every
+        // group would wait as the first one must (vmcnt(0), which drains the stores again).  Waiting here, once per chunk, leaves
+        // the loop with the counts of its own back edge.
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_waitcnt(0x0f70);                              // vmcnt(0)
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    for (int nb = n0; nb < n1; nb += GS_RC) {
+        hp_env_t* out_nb = out + (size_t)nb * HP_NCH;
+        float* cph_nb = BM ? cph + (size_t)nb * HP_NCH : nullptr;
+        if (!AHEAD) request(nb);
         float eo[GS_RC], co[BM ? GS_RC : 1];
         auto bank = [&](auto tail_tag) {                    // TAIL: the group that holds the row's end (only its samples < n24 count in ss)
             constexpr bool TAIL = decltype(tail_tag)::value;
@@ -854,9 +885,6 @@ __global__ __launch_bounds__(64) void haspi_bank_scan_kernel(HaspiWs ws, int sig
         };
         if (PASS2 && (!SIGNAL || BM) && nb + GS_RC > n24) bank(std::true_type{}); else bank(std::false_type{});
         if (GAIN) {
-            float gc[GS_RC];
-#pragma unroll
-            for (int u = 0; u < GS_RC; ++u) gc[u] = ctl_nb[u * HP_NCH];
 #pragma unroll
             for (int u = 0; u < GS_RC; ++u) {
                 float le = c_off + TEN_LOG10_2 * hp_log2f(gc[u]);
@@ -871,9 +899,14 @@ __global__ __launch_bounds__(64) void haspi_bank_scan_kernel(HaspiWs ws, int sig
                 hp_ihc_step(ik, (double)y, V1, V2);
             }
         }
+        if (AHEAD) {
+            __builtin_amdgcn_sched_barrier(0);                          // behind the last use of xc and gc ...
+            request(min(nb + GS_RC, n1 - GS_RC));                       // (n1 - n0 is a multiple of GS_RC)
+            __builtin_amdgcn_sched_barrier(0);                          // ... and ahead of the stores
+        }
         if (PASS2) {
 #pragma unroll
-            for (int u = 0; u < GS_RC; ++u) out_nb[u * HP_NCH] = eo[u];
+            for (int u = 0; u < GS_RC; ++u) { if (BM) out_nb[u * HP_NCH] = eo[u]; else hp_store_once(out_nb + u * HP_NCH, eo[u]); }
             if (BM) {
 #pragma unroll
                 for (int u = 0; u < GS_RC; ++u) cph_nb[u * HP_NCH] = co[u];
@@ -1357,7 +1390,7 @@ __global__ __launch_bounds__(128) void haspi_ihc_fir9_kernel(HaspiWs ws, int sig
                                                                //  and what it reads there is replaced before use)
     float nx[IF_G];                                            // the next group's samples are in flight while this group is processed
 #pragma unroll
-    for (int u = 0; u < IF_G; ++u) nx[u] = ep[u * HP_NCH];
+    for (int u = 0; u < IF_G; ++u) nx[u] = hp_load_once(ep + u * HP_NCH);
     float dl[IF_SLOTS * IF_G];                                 // the delay line: every index below is a compile-time constant
 #pragma unroll
     for (int q = 0; q < IF_SLOTS * IF_G; ++q) dl[q] = 0.f;
@@ -1369,7 +1402,7 @@ __global__ __launch_bounds__(128) void haspi_ihc_fir9_kernel(HaspiWs ws, int sig
 #pragma unroll
         for (int u = 0; u < IF_G; ++u) ex[u] = nx[u];
 #pragma unroll
-        for (int u = 0; u < IF_G; ++u) nx[u] = ep[(IF_G + u) * HP_NCH];
+        for (int u = 0; u < IF_G; ++u) nx[u] = hp_load_once(ep + (IF_G + u) * HP_NCH);
         double z = 0.0;
 #pragma unroll
         for (int u = 0; u < IF_G; ++u) {
