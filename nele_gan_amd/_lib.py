@@ -1,5 +1,5 @@
 """ctypes binding of libnele_hip.so (the C ABI of include/nele_hip.h and, for the entry points added after its fixed set,
-include/nele_hip_ext.h, after that one's, include/nele_hip_ext2.h, after that one's, include/nele_hip_ext3.h, after that one's, include/nele_hip_ext4.h, after that one's, include/nele_hip_ext5.h, after that one's, include/nele_hip_ext6.h, after that one's, include/nele_hip_ext7.h, after that one's, include/nele_hip_ext8.h and, after that one's, include/nele_hip_ext9.h).
+include/nele_hip_ext.h, after that one's, include/nele_hip_ext2.h, after that one's, include/nele_hip_ext3.h, after that one's, include/nele_hip_ext4.h, after that one's, include/nele_hip_ext5.h, after that one's, include/nele_hip_ext6.h, after that one's, include/nele_hip_ext7.h, after that one's, include/nele_hip_ext8.h, after that one's, include/nele_hip_ext9.h and, after that one's, include/nele_hip_ext10.h).
 
 The HIP library IS the product path: if it is missing or fails to load this module raises; there
 is no CPU or eager-PyTorch fallback anywhere in the package.
@@ -9,7 +9,7 @@ import os
 
 import torch
 
-from . import _abi, _abi_ext, _abi_ext2, _abi_ext3, _abi_ext4, _abi_ext5, _abi_ext6, _abi_ext7, _abi_ext8, _abi_ext9
+from . import _abi, _abi_ext, _abi_ext2, _abi_ext3, _abi_ext4, _abi_ext5, _abi_ext6, _abi_ext7, _abi_ext8, _abi_ext9, _abi_ext10
 
 FUNCS = dict(_abi.FUNCS, **_abi_ext.FUNCS)          # name -> (restype, argtypes) of the two headers
 CONSTS = dict(_abi.CONSTS, **_abi_ext.CONSTS)
@@ -29,6 +29,8 @@ FUNCS8 = dict(_abi_ext8.FUNCS)                      # the ninth header's, likewi
 CONSTS8 = dict(_abi_ext8.CONSTS)
 FUNCS9 = dict(_abi_ext9.FUNCS)                      # the tenth header's, likewise; their argtypes are in _SIGS9
 CONSTS9 = dict(_abi_ext9.CONSTS)
+FUNCS10 = dict(_abi_ext10.FUNCS)                    # the eleventh header's, likewise; their argtypes are in _SIGS10
+CONSTS10 = dict(_abi_ext10.CONSTS)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('NELE_LIB') or os.path.join(_HERE, 'libnele_hip.so')     # NELE_LIB: another build of the same ABI (A/B measurements)
@@ -58,7 +60,7 @@ lib = _load()
 
 def _bind(every):
     """Sets argtypes and restype of the entry points ``every`` (_abi*.FUNCS, generated from include/nele_hip.h, nele_hip_ext.h,
-    nele_hip_ext2.h, nele_hip_ext3.h, nele_hip_ext4.h, nele_hip_ext5.h, nele_hip_ext6.h, nele_hip_ext7.h, nele_hip_ext8.h and nele_hip_ext9.h by tools/gen_abi.py) -> name -> argtypes."""
+    nele_hip_ext2.h, nele_hip_ext3.h, nele_hip_ext4.h, nele_hip_ext5.h, nele_hip_ext6.h, nele_hip_ext7.h, nele_hip_ext8.h, nele_hip_ext9.h and nele_hip_ext10.h by tools/gen_abi.py) -> name -> argtypes."""
     missing = sorted(n for n in every if not hasattr(lib, n))
     if missing:
         raise ImportError("nele_gan_amd: %s does not export %s (declared in include/nele_hip*.h) -- "
@@ -79,6 +81,7 @@ _SIGS6 = _bind(FUNCS6)
 _SIGS7 = _bind(FUNCS7)
 _SIGS8 = _bind(FUNCS8)
 _SIGS9 = _bind(FUNCS9)
+_SIGS10 = _bind(FUNCS10)
 
 
 def check(status, name=''):

@@ -24,8 +24,10 @@ and, when the tree has it, from include/nele_hip_ext8.h (the entry points added 
   nele_gan_amd/_abi_ext8.py        likewise.
 and, when the tree has it, from include/nele_hip_ext9.h (the entry points added after nele_hip_ext8.h's fixed set)
   nele_gan_amd/_abi_ext9.py        likewise.
+and, when the tree has it, from include/nele_hip_ext10.h (the entry points added after nele_hip_ext9.h's fixed set)
+  nele_gan_amd/_abi_ext10.py       likewise.
 Run after changing a header; tests/test_capi_symbols.py, tests/test_abi_ext_cpu.py, tests/test_abi_ext2_cpu.py,
-tests/test_abi_ext3_cpu.py, tests/test_abi_ext4_cpu.py, tests/test_abi_ext5_cpu.py, tests/test_abi_ext6_cpu.py, tests/test_abi_ext7_cpu.py, tests/test_abi_ext8_cpu.py and tests/test_abi_ext9_cpu.py check that
+tests/test_abi_ext3_cpu.py, tests/test_abi_ext4_cpu.py, tests/test_abi_ext5_cpu.py, tests/test_abi_ext6_cpu.py, tests/test_abi_ext7_cpu.py, tests/test_abi_ext8_cpu.py, tests/test_abi_ext9_cpu.py and tests/test_abi_ext10_cpu.py check that
 all are current.
     python tools/gen_abi.py            # rewrite the files
     python tools/gen_abi.py --check    # exit 1 when a committed file differs
@@ -183,6 +185,10 @@ if __name__ == '__main__':
     n_before_tenth = len(outputs)
     if tenth:
         outputs += ((os.path.join(ROOT, 'nele_gan_amd', '_abi_ext9.py'), emit_abi('nele_hip_ext9.h')),)
+    eleventh = os.path.exists(os.path.join(ROOT, 'include', 'nele_hip_ext10.h'))  # likewise
+    n_before_eleventh = len(outputs)
+    if eleventh:
+        outputs += ((os.path.join(ROOT, 'nele_gan_amd', '_abi_ext10.py'), emit_abi('nele_hip_ext10.h')),)
     if '--check' in sys.argv:
         sys.exit(0 if all(os.path.exists(path) and open(path).read() == text for path, text in outputs) else 1)
     for path, text in outputs:
@@ -204,4 +210,6 @@ if __name__ == '__main__':
     if ninth:
         print('wrote %s (%d entry points)' % (outputs[n_before_tenth - 1][0], len(funcs(_header('nele_hip_ext8.h')))))
     if tenth:
-        print('wrote %s (%d entry points)' % (outputs[-1][0], len(funcs(_header('nele_hip_ext9.h')))))
+        print('wrote %s (%d entry points)' % (outputs[n_before_eleventh - 1][0], len(funcs(_header('nele_hip_ext9.h')))))
+    if eleventh:
+        print('wrote %s (%d entry points)' % (outputs[-1][0], len(funcs(_header('nele_hip_ext10.h')))))
